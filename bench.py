@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the north-star chain on MI355X: cf32 IQ -> 127-tap FIR, decimate by 5 -> 1024-pt FFT.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the fused chain kernel (redio_chain_enqueue) over one resident buffer of
 2^28 synthetic cf32 samples per GPU (BASELINE.json configs[1]).  Inputs are generated on the device
@@ -17,7 +17,12 @@ the per-launch HIP-event time has converged -- the medians of the last three win
 400 launches have run (~0.25 s).  Same kernel, same 2^28 samples, nothing skipped in the timed region; W and K keep their meaning.
 
 Rank 0 prints ONE JSON line.  `value` is exactly what the flags time (W warm-up launches, then K launches between
-two barriers).  `roofline` is for the dominant (only) kernel, chain_v4_kernel: algorithmic bytes = 9.6 B per input
+two barriers); `ms_per_step` is the wall time of one of those K launches.  A plain run does only that: set-up,
+pre-conditioning, warm-up, the K timed launches, `--dump-outputs DIR` if given (rank 0 writes the spectra of the last
+timed launch to DIR/spectra.npy, float32 [rows][1024][2]: every row up to 4096 of them, else a fixed seeded sample of
+rows plus the first and the last), and the line.  Every leg below that runs launches or CPU work of its own
+(`steady_state`, `reference_rounding`, `from_u8_bytes`, `stages`, `other_configs`, `cpu_baseline`) runs only with `--full`.
+`roofline` is for the dominant (only) kernel, chain_v4_kernel: algorithmic bytes = 9.6 B per input
 sample (8 B read + 8/5 B written) over the kernel's mean duration in the timed region, measured with HIP
 events on the launch stream; `launch_ms_series` are those per-launch times.  The chip raises its clock over the first
 ~100 launches of a burst, so after the headline the same launch is repeated `--steady` more times (default 1000) and
@@ -77,7 +82,33 @@ def parse():
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "r06_traffic.json"), help="file with {'traffic': bytes_per_launch, 'kernel': name} from the PMC passes")
     ap.add_argument("--no-precondition", action="store_true", help="skip the clock pre-conditioning launches (the cold-burst figure of rounds 1-3)")
     ap.add_argument("--precondition-max", type=int, default=400, help="cap on the pre-conditioning launches")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline (steady_state, reference_rounding, from_u8_bytes, stages, "
+                                                        "other_configs, cpu_baseline); without it the run sets up, warms up, times --steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the spectra the last step computed to DIR/spectra.npy "
+                                                          "(float32 [rows][1024][2], rank 0: every row up to 4096 of them, else 4096 rows drawn "
+                                                          "with a fixed seed plus the first and the last, 32 MiB)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_ROWS, DUMP_SEED = 4096, 0x5EED0D00   # --dump-outputs: at most 4096 + 2 rows of 8 KiB (32 MiB), the same rows for the same arguments
+
+
+def dump_outputs(d, out):
+    """--dump-outputs: what the caller of the timed path receives, the [nblk][1024] cf32 spectra of the last timed step, as float32 (re, im)
+    pairs in DIR/spectra.npy.  Every row when nblk <= DUMP_ROWS, else the first row, the last row and DUMP_ROWS rows drawn with DUMP_SEED,
+    in ascending order."""
+    import numpy as np
+    import torch
+    nblk = out.shape[0]
+    rows = np.arange(nblk)
+    if nblk > DUMP_ROWS:
+        rows = np.union1d(np.random.default_rng(DUMP_SEED).choice(nblk, DUMP_ROWS, replace=False), [0, nblk - 1])
+    sample = out[torch.as_tensor(rows, device=out.device)]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "spectra.npy"), torch.view_as_real(sample).cpu().numpy())
 
 
 def cpu_baseline(log2n, min_seconds=12.0):
@@ -626,9 +657,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out)
+
     # outside the timed region: the same launch repeated --steady more times, per-launch HIP events again
     steady = None
-    if a.steady > 0:
+    if a.full and a.steady > 0:
         sev = []
         for _ in range(a.steady + 1):
             e = C.c_void_p()
@@ -654,7 +688,7 @@ def main():
     # outside the timed region: the same launch with the reference's rounding (multiply and add rounded
     # separately, dsputils.rs:31) so that both arithmetic modes are on record from one run
     ref_ms = None
-    if not a.exact and not a.unfused:
+    if a.full and not a.exact and not a.unfused:
         ref_chain = R.Chain(taps, DECIM, NFFT, fused=False)
         e0, e1 = C.c_void_p(), C.c_void_p()
         R.check(lib.redio_event_create(C.byref(e0)))
@@ -675,7 +709,7 @@ def main():
     # outside the timed region: the same chain fed with the receiver's u8 I/Q bytes (redio_chain_enqueue_u8: data_to_samples folded
     # into the kernel's loader, 3.6 bytes per sample through HBM) -- a different input format, reported beside value, never as value
     u8_ms = None
-    if not a.exact and not a.unfused and not a.no_u8_leg and n % 2 == 0:
+    if a.full and not a.exact and not a.unfused and not a.no_u8_leg and n % 2 == 0:
         g = torch.Generator(device="cuda"); g.manual_seed(0x5EED0002 + rank)
         raw = torch.randint(0, 256, (2 * n,), dtype=torch.uint8, device="cuda", generator=g)
         e0, e1 = C.c_void_p(), C.c_void_p()
@@ -699,7 +733,7 @@ def main():
     # the decimating FIR alone (8 + 8/5 B per input sample) and the 1024-point transform alone on the decimated blocks (8 + 8 B per
     # sample it transforms) -- 20 warm-up + 50 timed launches each
     stages = None
-    if not a.exact and not a.unfused:
+    if a.full and not a.exact and not a.unfused:
         def timed(f, warm=20, reps=50):
             e0, e1 = C.c_void_p(), C.c_void_p()
             R.check(lib.redio_event_create(C.byref(e0)))
@@ -732,7 +766,7 @@ def main():
 
     # outside the timed region, rank 0 only: the other BASELINE configs (docstring of other_configs)
     others = None
-    if rank == 0 and not a.no_other_configs and not a.exact and not a.unfused and a.log2_samples >= 26:
+    if a.full and rank == 0 and not a.no_other_configs and not a.exact and not a.unfused and a.log2_samples >= 26:
         del out
         torch.cuda.empty_cache()
         others = other_configs(R, lib, stream, x, n, a.moved_json)
@@ -743,7 +777,7 @@ def main():
                 others[key]["cpu_baseline"] = cb[ck]
 
     cpu_rec = None
-    if rank == 0:
+    if a.full and rank == 0:
         # rank 0 only, also at N > 1 (the other ranks have nothing left to do; they wait in destroy_process_group)
         cpu_rec = None if a.no_cpu_baseline else cpu_baseline(a.cpu_log2_samples)
         if others is not None and not a.no_graph_leg:

@@ -307,6 +307,13 @@ static int ring_logic()
     return 0;
 }
 
+// scratch files of the WAV checks: under $TMPDIR when it is set (tests/test_kpn_cpp.py points it at a per-test directory)
+static std::string tmp_file(const char *name)
+{
+    const char *d = std::getenv("TMPDIR");
+    return std::string(d && *d ? d : "/tmp") + "/" + name;
+}
+
 static int plumbing()
 {
     if (int rc = ring_logic()) return rc;
@@ -518,21 +525,21 @@ static int plumbing()
     { // WAV round trip (float32 mono + stereo-as-IQ, PCM16 read)
         std::vector<float> x(4096);
         for (size_t i = 0; i < x.size(); ++i) x[i] = std::sin(0.01f * (float)i);
-        wavio::write_wav_f32("/tmp/kpn_rt.wav", x, 48000, 1);
+        wavio::write_wav_f32(tmp_file("kpn_rt.wav"), x, 48000, 1);
         auto [a, ar] = channel<float>();
-        auto t = spawn([&, s = std::move(a)]() mutable { wavio::wav_source_f32(std::move(s), "/tmp/kpn_rt.wav", 48000); });
+        auto t = spawn([&, s = std::move(a)]() mutable { wavio::wav_source_f32(std::move(s), tmp_file("kpn_rt.wav"), 48000); });
         t.join();
         CHECK(drain(ar) == x);
         auto [b, br] = channel<float>();
-        auto t2 = spawn([&, s = std::move(b)]() mutable { wavio::wav_source_f32(std::move(s), "/tmp/kpn_rt.wav", 48000, true); });
+        auto t2 = spawn([&, s = std::move(b)]() mutable { wavio::wav_source_f32(std::move(s), tmp_file("kpn_rt.wav"), 48000, true); });
         t2.join();
         CHECK(drain(br).size() == 2048); // the reference's (frames/2)/1024 chunk count
         bool threw = false;
-        try { auto [c, cr] = channel<float>(); wavio::wav_source_f32(std::move(c), "/tmp/kpn_rt.wav", 44100); } catch (const std::runtime_error &) { threw = true; }
+        try { auto [c, cr] = channel<float>(); wavio::wav_source_f32(std::move(c), tmp_file("kpn_rt.wav"), 44100); } catch (const std::runtime_error &) { threw = true; }
         CHECK(threw); // assert_eq!(samplerate)
-        wavio::write_wav_f32("/tmp/kpn_iq.wav", x, 48000, 2);
+        wavio::write_wav_f32(tmp_file("kpn_iq.wav"), x, 48000, 2);
         auto [d, dr] = channel<std::complex<float>>();
-        auto t3 = spawn([&, s = std::move(d)]() mutable { wavio::wav_source_complex_f32(std::move(s), "/tmp/kpn_iq.wav", 48000); });
+        auto t3 = spawn([&, s = std::move(d)]() mutable { wavio::wav_source_complex_f32(std::move(s), tmp_file("kpn_iq.wav"), 48000); });
         t3.join();
         auto iq = drain(dr);
         CHECK(iq.size() == 2048 && iq[1] == std::complex<float>(x[2], x[3]));
@@ -553,9 +560,9 @@ static int plumbing()
             return b;
         };
         auto outcome = [&](const std::vector<uint8_t> &b, size_t *frames = nullptr) { // 0: read, 1: runtime_error
-            put("/tmp/kpn_bad.wav", b);
+            put(tmp_file("kpn_bad.wav"), b);
             wavio::WavInfo info;
-            try { auto v = wavio::read_wav("/tmp/kpn_bad.wav", info); if (frames) *frames = info.frames; CHECK(v.size() == info.frames * info.channels); return 0; }
+            try { auto v = wavio::read_wav(tmp_file("kpn_bad.wav"), info); if (frames) *frames = info.frames; CHECK(v.size() == info.frames * info.channels); return 0; }
             catch (const std::runtime_error &) { return 1; }
         };
         size_t fr = 0;

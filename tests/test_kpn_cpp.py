@@ -49,8 +49,8 @@ def read_wav_f32(path):
     return np.frombuffer(b[i + 8:i + 8 + n], dtype=np.float32)
 
 
-def test_plumbing_blocks_cpu(exe):
-    out = subprocess.run([exe, "plumbing"], capture_output=True, text=True, timeout=900)
+def test_plumbing_blocks_cpu(exe, tmp_path):
+    out = subprocess.run([exe, "plumbing"], capture_output=True, text=True, timeout=900, env=dict(os.environ, TMPDIR=str(tmp_path)))
     assert out.returncode == 0 and "plumbing ok" in out.stdout, out.stderr
 
 

@@ -11,17 +11,17 @@ if [ "$2" != "notests" ]; then
   timeout 2400 python3 -m pytest tests -m gpu -x -q > $O/${TAG}_pytest.txt 2>&1; echo "pytest rc=$?" >> $O/${TAG}_pytest.txt
   tail -3 $O/${TAG}_pytest.txt
 fi
-python3 bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_driver_flags.json 2> $O/${TAG}_bench_driver_flags.err
-python3 bench.py --no-cpu-baseline > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_driver_flags.json 2> $O/${TAG}_bench_driver_flags.err
+python3 bench.py --full --no-cpu-baseline > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
 python3 tools/bench_configs.py c3 c4 c5 fir fft firshapes srcgen ingest u8chain > $O/${TAG}_other_configs_bench_lines.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_p_stats -- python3 $R/bench.py --no-cpu-baseline > $O/${TAG}_bench_under_rocprof.json 2> $O/${TAG}_p_stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_p_stats -- python3 $R/bench.py --full --no-cpu-baseline > $O/${TAG}_bench_under_rocprof.json 2> $O/${TAG}_p_stats.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_p_other -- python3 $R/tools/bench_configs.py c3 c4 c5 fir fft > $O/${TAG}_other_under_rocprof.txt 2> $O/${TAG}_p_other.err
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${TAG}_p_fetch -- python3 $R/bench.py --steps 20 --warmup 5 --steady 0 --no-cpu-baseline > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${TAG}_p_write -- python3 $R/bench.py --steps 20 --warmup 5 --steady 0 --no-cpu-baseline > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS --output-format csv -d $O/${TAG}_p_sq1 -- python3 $R/bench.py --steps 20 --warmup 5 --steady 0 --no-cpu-baseline > /dev/null 2> $O/${TAG}_p_sq1.err
-rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d $O/${TAG}_p_sq2 -- python3 $R/bench.py --steps 20 --warmup 5 --steady 0 --no-cpu-baseline > /dev/null 2> $O/${TAG}_p_sq2.err
-rocprofv3 --kernel-trace --pmc SQ_WAIT_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_IFETCH SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL GRBM_GUI_ACTIVE --output-format csv -d $O/${TAG}_p_sq3 -- python3 $R/bench.py --steps 20 --warmup 5 --steady 0 --no-cpu-baseline > /dev/null 2> $O/${TAG}_p_sq3.err
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${TAG}_p_fetch -- python3 $R/bench.py --full --steps 20 --warmup 5 --steady 0 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${TAG}_p_write -- python3 $R/bench.py --full --steps 20 --warmup 5 --steady 0 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS --output-format csv -d $O/${TAG}_p_sq1 -- python3 $R/bench.py --full --steps 20 --warmup 5 --steady 0 --no-cpu-baseline > /dev/null 2> $O/${TAG}_p_sq1.err
+rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d $O/${TAG}_p_sq2 -- python3 $R/bench.py --full --steps 20 --warmup 5 --steady 0 --no-cpu-baseline > /dev/null 2> $O/${TAG}_p_sq2.err
+rocprofv3 --kernel-trace --pmc SQ_WAIT_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_IFETCH SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL GRBM_GUI_ACTIVE --output-format csv -d $O/${TAG}_p_sq3 -- python3 $R/bench.py --full --steps 20 --warmup 5 --steady 0 --no-cpu-baseline > /dev/null 2> $O/${TAG}_p_sq3.err
 cd $R
 {
   echo "# chain_v4_kernel (fmaf build), mean per launch (bench.py --steps 20 --warmup 5 --steady 0, rocprofv3 --pmc, one pass per line group)"

@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; cd $R
 timeout 900 python3 -m pytest tests/test_kpn_cpp.py tests/test_gpu_runs.py -m gpu -q -x > $O/r06_kpn_pytest.txt 2>&1; echo "pytest rc=$?" >> $O/r06_kpn_pytest.txt
 tail -3 $O/r06_kpn_pytest.txt
-( time python3 bench.py --steps 20 --warmup 5 > $O/r06a_bench_driver_flags.json 2> $O/r06a_bench_driver_flags.err ) 2> $O/r06a_bench_time.txt
+( time python3 bench.py --full --steps 20 --warmup 5 > $O/r06a_bench_driver_flags.json 2> $O/r06a_bench_driver_flags.err ) 2> $O/r06a_bench_time.txt
 tail -3 $O/r06a_bench_time.txt; tail -3 $O/r06a_bench_driver_flags.err
 python3 - <<'PY'
 import json

@@ -3,7 +3,7 @@
 # chain_v4_kernel, the other configs' lines and kernel stats, the kpn graph sweep, the drop-in per-call table, the moved-bytes PMC passes.
 TAG=${1:-r06}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; cd $R
-python3 bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_driver_flags.json 2> $O/${TAG}_bench_driver_flags.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_driver_flags.json 2> $O/${TAG}_bench_driver_flags.err
 python3 tools/bench_configs.py c3 c3big c4 c5 fir fft firshapes c4gen u8chain u8c4 srcsmall > $O/${TAG}_other_configs_bench_lines.txt 2>&1
 python3 tools/dropin_latency.py > $O/${TAG}_dropin_calls.txt 2>&1
 timeout 900 tests/_build/kpn_tests bench_c2_sweep 0.3 3 13 28 > $O/${TAG}_kpn_sweep.txt 2>&1
@@ -11,9 +11,9 @@ for src in resident synth; do for snk in checksum drop; do for k in "24 2000" "2
   timeout 120 tests/_build/kpn_tests bench_c2 $k 4 $src $snk 0 0 >> $O/${TAG}_kpn_variants.txt 2>&1
 done; done; done
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_p_stats -- python3 $R/bench.py --no-cpu-baseline --no-graph-leg > $O/${TAG}_bench_under_rocprof.json 2> $O/${TAG}_p_stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_p_stats -- python3 $R/bench.py --full --no-cpu-baseline --no-graph-leg > $O/${TAG}_bench_under_rocprof.json 2> $O/${TAG}_p_stats.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_p_other -- python3 $R/tools/bench_configs.py c3 c3big c4 c5 fir fft c4gen u8c4 > $O/${TAG}_other_under_rocprof.txt 2> $O/${TAG}_p_other.err
-B="python3 $R/bench.py --steps 20 --warmup 5 --steady 0 --no-cpu-baseline --no-other-configs"
+B="python3 $R/bench.py --full --steps 20 --warmup 5 --steady 0 --no-cpu-baseline --no-other-configs"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${TAG}_p_fetch -- $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${TAG}_p_write -- $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS --output-format csv -d $O/${TAG}_p_sq1 -- $B > /dev/null 2> $O/${TAG}_p_sq1.err
