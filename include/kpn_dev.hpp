@@ -103,6 +103,24 @@ inline std::atomic<size_t> &default_ring_bytes_ref()
     return b;
 }
 inline void set_default_ring_bytes(size_t b) { default_ring_bytes_ref().store(b); }
+// Coalescing in dev::fir_fft_chain and dev::fft: after a block receives a message it also takes, without waiting, up to limit - 1 more
+// that are already queued in its channel, and runs them as ONE list launch (redio_*_enqueue_list) into one ring buffer; the outputs go
+// out as views of that buffer, in order, with their boundaries and bits unchanged.  A launch has a floor of about 10 us however little
+// it does (profiles/r06_kpn_graph.txt: one chain launch per message costs 9.6-10.5 us from 2^13 to 2^20 input samples), which is
+// all a small message costs.  1 (the default) is one launch per message.
+inline std::atomic<size_t> &coalesce_limit_ref()
+{
+    static std::atomic<size_t> n{1};
+    return n;
+}
+inline void set_coalesce_limit(size_t n) { coalesce_limit_ref().store(n ? n : 1); }
+// ... and a batch stops growing once its messages hold this many input samples together: about one launch that fills the chip
+// (2^20 samples of the 127 / 5 chain are 204 blocks, one wave each on 256 CUs).  Measured with 32 messages per list
+// (profiles/r07_list_launch.txt): the graph runs 19x / 14x / 3.7x faster with coalescing at 2^13 / 2^16 / 2^18-sample messages and
+// within 3 % at 2^20 and above, where a batch holds one message.  The bare list launches still gain there (2^20: 2.2 against 10.5 us
+// per message, 2^24: 32 against 42 us), so this bound is a starting point: raising it is measured together with the default.
+constexpr size_t COALESCE_MAX_IN = (size_t)1 << 20;
+
 // The byte budget is a preference about ORDER, never a reason to stop: a consumer that keeps a message while it waits for the next one
 // (a block with memory of its own) would otherwise wait for ever on a producer held back by its budget.  A budget wait that lasts this
 // long ends with the message going out anyway (a consumer that sat in a long host synchronisation with a message in hand: once); after
@@ -561,6 +579,50 @@ void run_block(Receiver<View<In>> &u, Sender<View<Out>> &v, NOut nout, Enqueue e
         v.send_unwrap(std::move(o));
     }
 }
+
+// run_block with coalescing (coalesce_limit_ref): recv, then whatever try_recv() finds queued, up to `limit` messages and about
+// COALESCE_MAX_IN input elements; one ring buffer for the batch's outputs (each at a 256-byte aligned offset); one Reading scope per
+// input around the ONE enqueue_list(inputs, buffer, offsets, stream) call; publish; the outputs sent in order as views of the buffer.
+// A hang-up while a batch is open ends the block only after that batch has gone out (try_recv never throws; the next recv() does).
+template <typename In, typename Out, typename NOut, typename EnqueueList>
+void run_block_list(Receiver<View<In>> &u, Sender<View<Out>> &v, NOut nout, EnqueueList enqueue_list, size_t limit = coalesce_limit_ref().load())
+{
+    static_assert(256 % sizeof(Out) == 0, "outputs at 256-byte offsets");
+    constexpr size_t ALIGN = 256 / sizeof(Out);
+    BlockStream st;
+    Ring ring;
+    std::vector<View<In>> ins;
+    std::vector<size_t> offs, lens;
+    size_t high = 0; // the largest batch buffer so far: every buffer of the ring settles at it, so batches of varying sizes stop regrowing them
+    for (;;) {
+        ins.clear();
+        ins.push_back(u.recv());
+        size_t in_elems = ins[0].len;
+        while (ins.size() < limit && in_elems < COALESCE_MAX_IN) {
+            auto d = u.try_recv();
+            if (!d) break;
+            in_elems += d->len;
+            ins.push_back(std::move(*d));
+        }
+        offs.resize(ins.size());
+        lens.resize(ins.size());
+        size_t total = 0;
+        for (size_t i = 0; i < ins.size(); ++i) {
+            offs[i] = (total + ALIGN - 1) / ALIGN * ALIGN;
+            lens[i] = nout(ins[i]);
+            total = offs[i] + lens[i];
+        }
+        high = std::max(high, total);
+        auto o = ring.acquire<Out>(high, st);
+        {
+            std::vector<std::unique_ptr<Reading<In>>> rd;
+            for (auto &d : ins) rd.emplace_back(new Reading<In>(d, st));
+            check(enqueue_list(ins, o, offs, (void *)st));
+        }
+        publish(o, st);
+        for (size_t i = 0; i < ins.size(); ++i) v.send_unwrap(o.sub(offs[i], lens[i]));
+    }
+}
 } // namespace detail
 
 // dsputils::convolve semantics on device streams (complex samples x real taps, optional decimation)
@@ -581,11 +643,19 @@ inline void fft(Receiver<View<std::complex<float>>> pin, Sender<View<std::comple
     redio_fft *h = nullptr;
     check(redio_fft_create(&h, (int)block_size, (int)inv));
     struct G { redio_fft *h; ~G() { redio_fft_destroy(h); } } g{h};
-    detail::run_block<cf, cf>(pin, cout,
-                              [&](const View<cf> &d) {
-                                  if (d.len % block_size) throw std::runtime_error("assert!(din.len() == block_size) (kissfft.rs:24)");
-                                  return d.len;
-                              },
+    const auto nout = [&](const View<cf> &d) {
+        if (d.len % block_size) throw std::runtime_error("assert!(din.len() == block_size) (kissfft.rs:24)");
+        return d.len;
+    };
+    if (coalesce_limit_ref().load() > 1) { // several queued messages in one launch (coalesce_limit_ref)
+        detail::run_block_list<cf, cf>(pin, cout, nout, [&](const std::vector<View<cf>> &ds, const View<cf> &o, const std::vector<size_t> &offs, void *st) {
+            std::vector<redio_msg> m(ds.size());
+            for (size_t i = 0; i < ds.size(); ++i) m[i] = redio_msg{ds[i].data(), ds[i].len / block_size, o.data() + offs[i]};
+            return redio_fft_enqueue_list(h, m.data(), m.size(), st);
+        });
+        return;
+    }
+    detail::run_block<cf, cf>(pin, cout, nout,
                               [&](const View<cf> &d, const View<cf> &o, void *st) { return redio_fft_enqueue(h, d.data(), o.data(), d.len / block_size, st); });
 }
 
@@ -597,7 +667,16 @@ inline void fir_fft_chain(Receiver<View<std::complex<float>>> u, Sender<View<std
     redio_chain *h = nullptr;
     check(redio_chain_create(&h, taps.data(), taps.size(), decim, nfft, fused ? REDIO_FIR_FUSED : 0));
     struct G { redio_chain *h; ~G() { redio_chain_destroy(h); } } g{h};
-    detail::run_block<cf, cf>(u, v, [&](const View<cf> &d) { return redio_chain_nblocks(h, d.len) * (size_t)nfft; },
+    const auto nout = [&](const View<cf> &d) { return redio_chain_nblocks(h, d.len) * (size_t)nfft; };
+    if (coalesce_limit_ref().load() > 1) { // several queued messages in one launch (coalesce_limit_ref)
+        detail::run_block_list<cf, cf>(u, v, nout, [&](const std::vector<View<cf>> &ds, const View<cf> &o, const std::vector<size_t> &offs, void *st) {
+            std::vector<redio_msg> m(ds.size());
+            for (size_t i = 0; i < ds.size(); ++i) m[i] = redio_msg{ds[i].data(), ds[i].len, o.data() + offs[i]};
+            return redio_chain_enqueue_list(h, m.data(), m.size(), st);
+        });
+        return;
+    }
+    detail::run_block<cf, cf>(u, v, nout,
                               [&](const View<cf> &d, const View<cf> &o, void *st) { return redio_chain_enqueue(h, d.data(), d.len, o.data(), st); });
 }
 

@@ -121,6 +121,21 @@ size_t redio_fir_nout(const redio_fir *h, size_t n_in);
 /* valid-mode over one device buffer; d_out must hold redio_fir_nout() samples; in != out */
 int redio_fir_enqueue(redio_fir *h, const void *d_in, size_t n_in, void *d_out, void *stream);
 
+/* ---- lists of independent messages for one launch (redio_fft_enqueue_list, redio_chain_enqueue_list) ----
+ * The reference runs one kissfft::fft per message of block_size samples (src/kissfft/src/kissfft.rs:20-27 asserts din.len() ==
+ * block_size) and one chain per message from a block thread (src/ratpak.rs:60-185); a launch per small message costs a fixed floor
+ * (about 10 us).  A list call takes up to REDIO_LIST_MAX such messages -- each with its own input, length and output -- and gives,
+ * bit for bit, what `count` single calls in list order give.  `n` is what the single call takes (input samples for the chain,
+ * transforms for the FFT); an entry that yields no output is skipped; count > REDIO_LIST_MAX runs as several launches.
+ * Preconditions: in != out for every entry (REDIO_ERR_ARG otherwise), and no output overlaps another output or any input of the
+ * list (the entries run concurrently).  Every entry is checked before anything is launched. */
+#define REDIO_LIST_MAX 32
+typedef struct {
+    const void *in;
+    size_t n; /* what the single call takes */
+    void *out;
+} redio_msg;
+
 /* ---- A5: kissfft::fft block, src/kissfft/src/kissfft.rs:18-31 (device-resident, batched) ----
  * nbatch consecutive messages of exactly nfft cf32 samples; unnormalised; inverse!=0 flips the sign
  * of the exponent.  Arithmetic order of the published kissfft butterflies (bit-exact with
@@ -133,6 +148,10 @@ int redio_fft_enqueue(redio_fft *h, const void *d_in, void *d_out, size_t nbatch
 int redio_fft_reserve(redio_fft *h, size_t nbatch);
 /* messages that start every in_stride samples (overlapping blocks when in_stride < nfft); no aliasing */
 int redio_fft_enqueue_strided(redio_fft *h, const void *d_in, void *d_out, size_t nbatch, long in_stride, void *stream);
+/* kissfft::fft (kissfft.rs:18-31) over a list: entry i is msgs[i].n consecutive transforms from msgs[i].in to msgs[i].out (list
+ * preconditions above).  nfft = 1024 is ONE launch per REDIO_LIST_MAX entries that neither allocates nor synchronises (capturable);
+ * every other size runs redio_fft_enqueue per entry -- the same bits, one launch per entry. */
+int redio_fft_enqueue_list(redio_fft *h, const redio_msg *msgs, size_t count, void *stream);
 
 /* ---- C2 chain: FIR (ntaps, decimate decim) -> nfft-point forward FFT of consecutive blocks ----
  * Fused single kernel for nfft = 1024 with (ntaps, decim) in {(127, 5), (127, 3), (127, 1), (63, 5), (63, 1)} on a
@@ -149,6 +168,11 @@ int redio_chain_set_unfused(redio_chain *h, int unfused);
 /* sizes the two-kernel path's intermediate for inputs of up to n_in samples, so that enqueue never allocates */
 int redio_chain_reserve(redio_chain *h, size_t n_in);
 int redio_chain_enqueue(redio_chain *h, const void *d_in, size_t n_in, void *d_out, void *stream);
+/* the chain (dsputils.rs:30-32 -> kissfft.rs:18-31) over a list: entry i is one redio_chain_enqueue of msgs[i].n input samples from
+ * msgs[i].in to msgs[i].out (list preconditions above).  A fused plan runs its entries with a 16-byte aligned input as ONE kernel per
+ * REDIO_LIST_MAX of them (no allocation, no synchronisation: capturable); the other entries go through redio_chain_enqueue behind it
+ * on the same stream.  A two-kernel plan (redio_chain_set_unfused, other shapes) runs redio_chain_enqueue per entry. */
+int redio_chain_enqueue_list(redio_chain *h, const redio_msg *msgs, size_t count, void *stream);
 /* The receiver's own format in: interleaved u8 I/Q bytes (rtlsdr::data_to_samples, src/rtlsdr/src/rtlsdr.rs:159-162: i as f32 / 127.0 - 1.0)
  * straight into the chain -- nbytes / 2 samples, the spectra redio_data_to_samples + redio_chain_enqueue would give, bit for bit.
  * The shapes with a fused cf32 kernel (above) on 4-byte aligned bytes are ONE kernel ((127, 5): 3.6 bytes per sample through HBM instead

@@ -43,6 +43,14 @@ _kiss = None
 _src = None
 
 
+REDIO_LIST_MAX = 32  # include/redio.h: entries one list launch takes (longer lists run as several launches)
+
+
+class redio_msg(C.Structure):
+    """include/redio.h redio_msg: one entry of redio_{chain,fft}_enqueue_list (n: what the single call takes)."""
+    _fields_ = [("in_", C.c_void_p), ("n", C.c_size_t), ("out", C.c_void_p)]
+
+
 def _sig(f, res, *args):
     f.restype = res
     f.argtypes = list(args)
@@ -94,6 +102,8 @@ def lib():
     _sig(L.redio_fft_create, i, C.POINTER(vp), i, i)
     _sig(L.redio_fft_destroy, i, vp)
     _sig(L.redio_fft_enqueue, i, vp, vp, vp, sz, vp)
+    _sig(L.redio_fft_enqueue_list, i, vp, C.POINTER(redio_msg), sz, vp)
+    _sig(L.redio_chain_enqueue_list, i, vp, C.POINTER(redio_msg), sz, vp)
     _sig(L.redio_chain_create, i, C.POINTER(vp), pf, sz, sz, i, u)
     _sig(L.redio_chain_destroy, i, vp)
     _sig(L.redio_chain_nblocks, sz, vp, sz)

@@ -11,6 +11,7 @@
 #include "fir_core.h"
 #include "fft_wave.h"
 #include "redio_internal.h"
+#include "../../include/redio.h"
 #include <type_traits>
 
 namespace redio {
@@ -209,6 +210,107 @@ __global__ __launch_bounds__(64, WPS) void chain_v4_kernel(const float2 *__restr
     }
 }
 
+// A list of independent cf32 messages in ONE launch (redio_chain_enqueue_list): message i owns the waves [wave0[i], wave0[i + 1]).
+// The list travels by value in the kernel arguments: no descriptor buffer, nothing to upload or recycle, and a captured launch carries
+// its own copy.
+struct ChainList {
+    const float2 *x[REDIO_LIST_MAX];
+    float2 *out[REDIO_LIST_MAX];
+    long nblocks[REDIO_LIST_MAX];
+    unsigned wave0[REDIO_LIST_MAX + 1]; // wave-start prefix: wave0[count] = the launch's waves
+    int count;
+};
+
+// A wave runs exactly what chain_v4_kernel<K, D, FUSED, 2, 8, false, true> runs for (x_i, out_i, nblocks_i, blocks_per_wave): the same
+// head fetch, FIR and transform, so the bits are those of one launch per message; a wave never spans two messages.  A copy of that
+// kernel's cf32 path, not a shared body: moving the body into an inlined function changed the instruction schedule of every existing
+// instantiation, and the headline kernel stays as it was measured.
+template <int K, int D, bool FUSED>
+__global__ __launch_bounds__(64, 2) void chain_v4_list_kernel(const ChainList list, const float *__restrict__ taps,
+                                                              const float2 *__restrict__ tw, long blocks_per_wave)
+{
+    constexpr int R = 4, CH = 8;
+    using G = FirGeomV<K, D, R>;
+    constexpr int SUB_OUT = 64 * R;                   // 256 outputs per sub-tile
+    constexpr int SUB_NEW = SUB_OUT * D;              // new input samples per sub-tile
+    constexpr int HALO = G::tile_in(SUB_OUT) - SUB_NEW; // samples shared with the previous sub-tile
+    static_assert(HALO % 2 == 0 && SUB_NEW % 128 == 0 && 4 * SUB_OUT == 1024, "geometry");
+    constexpr int HALO_V = HALO / 2;
+    constexpr int NLD = SUB_NEW / 2 / 64;
+    static_assert(HALO_V <= 64, "the halo moves with one instruction per lane");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    v4f_t *xs4 = reinterpret_cast<v4f_t *>(smem);
+    float2 *ex = reinterpret_cast<float2 *>(smem);
+
+    // which message: a scan of the wave-start prefix in scalar registers (the workgroup index and the list are wave-uniform)
+    const unsigned w = blockIdx.x;
+    int m = 0;
+    for (int i = 1; i < list.count; ++i) m = w >= list.wave0[i] ? i : m;
+    m = __builtin_amdgcn_readfirstlane(m);
+    const float2 *x = list.x[m];
+    float2 *out = list.out[m];
+    const long nblocks = list.nblocks[m];
+
+    const int lane = threadIdx.x;
+    const long b0 = (long)(w - list.wave0[m]) * blocks_per_wave; // < nblocks: the host gives message i ceil(nblocks_i / bpw) waves
+    const long b1 = (b0 + blocks_per_wave < nblocks) ? b0 + blocks_per_wave : nblocks;
+    const long nsub = 4 * (b1 - b0);
+    const v4f_t *src0 = reinterpret_cast<const v4f_t *>(x + b0 * 1024 * (long)D) + lane;
+    v4f_t pre[NLD];
+    auto fetch = [&](long j) { // new samples of sub-tile j: [HALO + j*SUB_NEW, HALO + (j+1)*SUB_NEW)
+        const v4f_t *src = src0 + HALO_V + j * (SUB_NEW / 2);
+#if REDIO_EXP_CHAIN_NT & 1
+        static_for4<NLD>([&](auto I) { pre[I.value] = __builtin_nontemporal_load(src + 64 * I.value); });
+#else
+        static_for4<NLD>([&](auto I) { pre[I.value] = src[64 * I.value]; });
+#endif
+    };
+    auto park = [&] { static_for4<NLD>([&](auto I) { xs4[G::lds_index(HALO + 2 * (lane + 64 * I.value)) / 2] = pre[I.value]; }); };
+
+    if (lane < HALO_V) xs4[G::lds_index(2 * lane) / 2] = src0[0]; // the run's own head
+    fetch(0);
+    park();
+    wave_lds_fence();
+
+    float2 a[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) a[i] = make_float2(0.f, 0.f);
+    Fft1knTw34 t34;
+    fft1kn_load_tw34(t34, lane, tw);
+#pragma unroll 1
+    for (long j = 0; j < nsub; ++j) {
+        const bool more = j + 1 < nsub;
+        if (more) fetch(j + 1);
+        float2 acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = make_float2(0.f, 0.f);
+        int lf = lane;
+        asm volatile("" : "+v"(lf));
+        fir_lane_v<K, D, R, FUSED, CH>(xs4, lf, taps, acc);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) a[i] = a[i + 4];
+#pragma unroll
+        for (int r = 0; r < R; ++r) a[12 + r] = acc[r];
+        wave_lds_fence();
+        v4f_t halo = v4f_t{0.f, 0.f, 0.f, 0.f};
+        if (more && lf < HALO_V) halo = xs4[G::lds_index(SUB_NEW + 2 * lf) / 2];
+        if ((j & 3) == 3) {
+            wave_lds_fence();
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            Fft1knTw12 t12;
+            fft1kn_load_tw12(t12, ln, tw);
+            fft1kn_wave_tw<false>(a, ex, tw, t12, t34, out + (b0 + (j >> 2)) * 1024, ln);
+            wave_lds_fence();
+        }
+        if (more) {
+            if (lf < HALO_V) xs4[G::lds_index(2 * lf) / 2] = halo;
+            park();
+        }
+        wave_lds_fence();
+    }
+}
+
 // blocks per wavefront of a launch over nblocks blocks at WPS wavefronts per SIMD (the chain: 2; the FIR alone: 3)
 long chain_v4_blocks_per_wave(long nblocks, int WPS)
 {
@@ -228,9 +330,9 @@ long chain_v4_blocks_per_wave(long nblocks, int WPS)
     return bpw;
 }
 
-template <int K, int D, int WPS, int CH, bool FIR_ONLY = false, bool TWP = false, bool IN_U8 = false, bool PF2 = false>
-static hipError_t launch_v4_t(const float2 *x, const float *taps, const float2 *tw, float2 *out, long nblocks, bool fused,
-                              hipStream_t s, unsigned long long *dbg, long dbg_cap = 0)
+// dynamic LDS of one wavefront of the kernels above
+template <int K, int D, int WPS, bool PF2 = false>
+static constexpr size_t chain_v4_lds()
 {
     static_assert(WPS == 2 || WPS == 3, "two wavefronts per SIMD (the chain: its transform needs 197 registers) or three (the FIR alone: 94-145)");
     using G = FirGeomV<K, D, 4>;
@@ -243,6 +345,14 @@ static hipError_t launch_v4_t(const float2 *x, const float *taps, const float2 *
     // half empty, and the launch ends when the most crowded CU does (measured: wave lifetimes 320-570 us).
     constexpr size_t LDS = (160 * 1024 / (4 * WPS)) - 480 > LDS_NEED ? (160 * 1024 / (4 * WPS)) - 480 : LDS_NEED;
     static_assert((4 * WPS + 1) * LDS > 160 * 1024, "one more wave must not fit");
+    return LDS;
+}
+
+template <int K, int D, int WPS, int CH, bool FIR_ONLY = false, bool TWP = false, bool IN_U8 = false, bool PF2 = false>
+static hipError_t launch_v4_t(const float2 *x, const float *taps, const float2 *tw, float2 *out, long nblocks, bool fused,
+                              hipStream_t s, unsigned long long *dbg, long dbg_cap = 0)
+{
+    constexpr size_t LDS = chain_v4_lds<K, D, WPS, PF2>();
     const long bpw = chain_v4_blocks_per_wave(nblocks, WPS);
     const long grid = (nblocks + bpw - 1) / bpw;
     if (fused) hipLaunchKernelGGL((chain_v4_kernel<K, D, true, WPS, CH, FIR_ONLY, TWP, IN_U8, PF2>), dim3((unsigned)grid), dim3(64), LDS, s, x, taps, tw, out, nblocks, bpw, dbg, dbg_cap);
@@ -288,6 +398,46 @@ hipError_t launch_chain_v4_shape(int K, int D, const float2 *x, const float *tap
     if (K == 127 && D == 1) return launch_v4_t<127, 1, 2, 8, false, true>(x, taps, tw, out, nblocks, fused, s, nullptr);
     if (K == 63 && D == 1) return launch_v4_t<63, 1, 2, 8, false, true>(x, taps, tw, out, nblocks, fused, s, nullptr);
     if (K == 127 && D == 3) return launch_v4_t<127, 3, 2, 8, false, true>(x, taps, tw, out, nblocks, fused, s, nullptr);
+    return hipErrorNotSupported;
+}
+
+template <int K, int D>
+static hipError_t launch_v4_list_t(const float2 *const *x, float2 *const *out, const long *nblocks, int count, const float *taps,
+                                   const float2 *tw, bool fused, hipStream_t s)
+{
+    ChainList list;
+    long total = 0;
+    for (int i = 0; i < count; ++i) total += nblocks[i];
+    // one rule for the whole launch, from its total: the runs of a list of small messages are as short as those of one message of that size
+    const long bpw = chain_v4_blocks_per_wave(total, 2);
+    unsigned w = 0;
+    for (int i = 0; i < count; ++i) {
+        list.x[i] = x[i];
+        list.out[i] = out[i];
+        list.nblocks[i] = nblocks[i];
+        list.wave0[i] = w;
+        w += (unsigned)((nblocks[i] + bpw - 1) / bpw);
+    }
+    list.wave0[count] = w;
+    list.count = count;
+    constexpr size_t LDS = chain_v4_lds<K, D, 2>(); // the single launch's request: the dispatcher packs no extra wave onto a CU
+    if (fused) hipLaunchKernelGGL((chain_v4_list_kernel<K, D, true>), dim3(w), dim3(64), LDS, s, list, taps, tw, bpw);
+    else hipLaunchKernelGGL((chain_v4_list_kernel<K, D, false>), dim3(w), dim3(64), LDS, s, list, taps, tw, bpw);
+    return hipGetLastError();
+}
+
+// count (1 ... REDIO_LIST_MAX) messages of the fused cf32 shapes in one launch: 16-byte aligned inputs, nblocks[i] >= 1 each
+hipError_t launch_chain_list(int K, long D, const float2 *const *x, float2 *const *out, const long *nblocks, int count, const float *taps,
+                             const float2 *tw, bool fused, hipStream_t s)
+{
+    if (count < 1 || count > REDIO_LIST_MAX) return hipErrorInvalidValue;
+    for (int i = 0; i < count; ++i)
+        if (nblocks[i] < 1 || (reinterpret_cast<uintptr_t>(x[i]) & 15) != 0) return hipErrorInvalidValue;
+    if (K == 127 && D == 5) return launch_v4_list_t<127, 5>(x, out, nblocks, count, taps, tw, fused, s);
+    if (K == 127 && D == 3) return launch_v4_list_t<127, 3>(x, out, nblocks, count, taps, tw, fused, s);
+    if (K == 127 && D == 1) return launch_v4_list_t<127, 1>(x, out, nblocks, count, taps, tw, fused, s);
+    if (K == 63 && D == 5) return launch_v4_list_t<63, 5>(x, out, nblocks, count, taps, tw, fused, s);
+    if (K == 63 && D == 1) return launch_v4_list_t<63, 1>(x, out, nblocks, count, taps, tw, fused, s);
     return hipErrorNotSupported;
 }
 

@@ -8,6 +8,7 @@
 //   fft_lds_kernel      any N that fits LDS: one workgroup per transform, in-place stages in LDS.
 //   fft_global_*        larger N: digit-reversal copy + one launch per stage in global memory.
 #include "redio_internal.h"
+#include "../../include/redio.h"
 #include "fft_wave.h"
 #include "fft_big_core.h"
 
@@ -74,6 +75,73 @@ __global__ __launch_bounds__(256) void fft1k_wave_kernel(const float2 *in, float
 #pragma unroll
         for (int i = 0; i < 16; ++i) v[i] = nx[i];
     }
+}
+
+// fft1k_wave_kernel over a list of independent messages in ONE launch (redio_fft_enqueue_list): message i holds nbatch[i] consecutive
+// transforms and owns the waves [wave0[i], wave0[i + 1]), each a run of FFT1K_RUN transforms inside that message; the list travels by
+// value in the kernel arguments.  Per wave the program of fft1k_wave_kernel, so the bits are those of one launch per message.
+struct Fft1kList {
+    const float2 *in[REDIO_LIST_MAX];
+    float2 *out[REDIO_LIST_MAX];
+    long nbatch[REDIO_LIST_MAX];
+    unsigned wave0[REDIO_LIST_MAX + 1]; // wave-start prefix: wave0[count] = the launch's waves
+    int count;
+};
+template <bool INV>
+__global__ __launch_bounds__(256) void fft1k_wave_list_kernel(const Fft1kList list, const float2 *__restrict__ tw)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float2 *ex = reinterpret_cast<float2 *>(smem) + wave * FFT1K_LDS;
+    const unsigned gw = blockIdx.x * 4u + (unsigned)wave;
+    if (gw >= list.wave0[list.count]) return; // wave-uniform: the last workgroup's spare waves
+    int m = 0; // which message: a scan of the wave-start prefix in scalar registers
+    for (int i = 1; i < list.count; ++i) m = gw >= list.wave0[i] ? i : m;
+    m = __builtin_amdgcn_readfirstlane(m);
+    const float2 *in = list.in[m];
+    float2 *out = list.out[m];
+    const long nbatch = list.nbatch[m];
+    const long b0 = (long)(gw - list.wave0[m]) * FFT1K_RUN;
+    const long b1 = (b0 + FFT1K_RUN < nbatch) ? b0 + FFT1K_RUN : nbatch;
+    Fft1kTw t;
+    fft1k_load_tw(t, lane, tw);
+    float2 v[16], nx[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = fft_ld_once(in + b0 * 1024 + lane + 64 * i);
+    for (long b = b0; b < b1; ++b) {
+        const long bn = (b + 1 < b1) ? b + 1 : b;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) nx[i] = fft_ld_once(in + bn * 1024 + lane + 64 * i);
+        fft1k_wave_regs<INV>(v, FftOnceOut{out + b * 1024}, ex, tw, t, lane);
+        wave_lds_fence();
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = nx[i];
+    }
+}
+
+// count (1 ... REDIO_LIST_MAX) messages of nbatch[i] >= 1 consecutive 1024-point transforms each, in one launch
+hipError_t launch_fft1k_list(const FftPlanDev &p, const float2 *const *in, float2 *const *out, const long *nbatch, int count, hipStream_t s)
+{
+    if (p.nfft != 1024) return hipErrorNotSupported;
+    if (count < 1 || count > REDIO_LIST_MAX) return hipErrorInvalidValue;
+    Fft1kList list;
+    unsigned w = 0;
+    for (int i = 0; i < count; ++i) {
+        if (nbatch[i] < 1) return hipErrorInvalidValue;
+        list.in[i] = in[i];
+        list.out[i] = out[i];
+        list.nbatch[i] = nbatch[i];
+        list.wave0[i] = w;
+        w += (unsigned)((nbatch[i] + FFT1K_RUN - 1) / FFT1K_RUN);
+    }
+    list.wave0[count] = w;
+    list.count = count;
+    const size_t lds = 4 * FFT1K_LDS * sizeof(float2);
+    const unsigned grid = (w + 3) / 4;
+    if (p.inverse) hipLaunchKernelGGL(fft1k_wave_list_kernel<true>, dim3(grid), dim3(256), lds, s, list, p.tw);
+    else hipLaunchKernelGGL(fft1k_wave_list_kernel<false>, dim3(grid), dim3(256), lds, s, list, p.tw);
+    return hipGetLastError();
 }
 
 // ---- overlap-save with 1024-point blocks: one wavefront per block, nothing but registers in between -------

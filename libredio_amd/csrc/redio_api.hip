@@ -492,6 +492,41 @@ extern "C" int redio_fft_enqueue_strided(redio_fft *h, const void *d_in, void *d
     return hip_rc(e);
 }
 
+// the list preconditions of include/redio.h that can be checked: a pointer for every entry that yields output, in != out
+static bool list_args_ok(const redio_msg *msgs, size_t count, size_t (*nout)(const void *, size_t), const void *h)
+{
+    if (count && !msgs) return false;
+    for (size_t i = 0; i < count; ++i)
+        if (nout(h, msgs[i].n) && (!msgs[i].in || !msgs[i].out || msgs[i].in == msgs[i].out)) return false;
+    return true;
+}
+static size_t fft_list_nout(const void *, size_t n) { return n; }
+
+extern "C" int redio_fft_enqueue_list(redio_fft *h, const redio_msg *msgs, size_t count, void *stream)
+{
+    if (!h || !list_args_ok(msgs, count, fft_list_nout, h)) return REDIO_ERR_ARG;
+    RD_TRY(hipSetDevice(h->device));
+    if (h->dev.nfft != 1024) { // one launch per entry (the other sizes' kernels take one contiguous batch)
+        for (size_t i = 0; i < count; ++i)
+            if (int rc = redio_fft_enqueue(h, msgs[i].in, msgs[i].out, msgs[i].n, stream)) return rc;
+        return REDIO_OK;
+    }
+    const float2 *in[REDIO_LIST_MAX];
+    float2 *out[REDIO_LIST_MAX];
+    long nb[REDIO_LIST_MAX];
+    int k = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if (msgs[i].n == 0) continue;
+        in[k] = (const float2 *)msgs[i].in; out[k] = (float2 *)msgs[i].out; nb[k] = (long)msgs[i].n;
+        if (++k == REDIO_LIST_MAX) {
+            RD_TRY(launch_fft1k_list(h->dev, in, out, nb, k, (hipStream_t)stream));
+            k = 0;
+        }
+    }
+    if (k) RD_TRY(launch_fft1k_list(h->dev, in, out, nb, k, (hipStream_t)stream));
+    return REDIO_OK;
+}
+
 const FftPlanDev *redio_fft_plan_dev(const redio_fft *h) { return h ? &h->dev : nullptr; }
 const float2 *redio_fft_twiddles_dev(const redio_fft *h) { return h ? h->dev.tw : nullptr; }
 const float2 *redio_fft_twiddles_pass_dev(const redio_fft *h) { return h ? h->dev.tw_pass : nullptr; }
@@ -619,6 +654,44 @@ extern "C" int redio_chain_enqueue(redio_chain *h, const void *d_in, size_t n_in
     RD_TRY(launch_fir(d_in, (long)need_in, h->fir->d_taps, (int)h->fir->ntaps, (long)h->fir->decim, h->d_mid, (long)ny,
                       true, fused_math, (hipStream_t)stream));
     return redio_fft_enqueue(h->fft, h->d_mid, d_out, nblk, stream);
+}
+
+static size_t chain_list_nout(const void *h, size_t n) { return redio_chain_nblocks((const redio_chain *)h, n); }
+
+extern "C" int redio_chain_enqueue_list(redio_chain *h, const redio_msg *msgs, size_t count, void *stream)
+{
+    if (!h || !list_args_ok(msgs, count, chain_list_nout, h)) return REDIO_ERR_ARG;
+    if (!redio_chain_is_fused(h)) { // the two-kernel path: one call per entry
+        for (size_t i = 0; i < count; ++i)
+            if (int rc = redio_chain_enqueue(h, msgs[i].in, msgs[i].n, msgs[i].out, stream)) return rc;
+        return REDIO_OK;
+    }
+    RD_TRY(hipSetDevice(h->fir->device));
+    const bool fused_math = (h->fir->flags & REDIO_FIR_FUSED) != 0;
+    const int K = (int)h->fir->ntaps;
+    const long D = (long)h->fir->decim;
+    // the entries the fused kernel takes (a 16-byte aligned input), REDIO_LIST_MAX per launch
+    const float2 *x[REDIO_LIST_MAX];
+    float2 *out[REDIO_LIST_MAX];
+    long nb[REDIO_LIST_MAX];
+    int k = 0;
+    bool rest = false;
+    for (size_t i = 0; i < count; ++i) {
+        const size_t nblk = redio_chain_nblocks(h, msgs[i].n);
+        if (nblk == 0) continue;
+        if ((reinterpret_cast<uintptr_t>(msgs[i].in) & 15) != 0) { rest = true; continue; }
+        x[k] = (const float2 *)msgs[i].in; out[k] = (float2 *)msgs[i].out; nb[k] = (long)nblk;
+        if (++k == REDIO_LIST_MAX) {
+            RD_TRY(launch_chain_list(K, D, x, out, nb, k, h->fir->d_taps, h->fft->dev.tw, fused_math, (hipStream_t)stream));
+            k = 0;
+        }
+    }
+    if (k) RD_TRY(launch_chain_list(K, D, x, out, nb, k, h->fir->d_taps, h->fft->dev.tw, fused_math, (hipStream_t)stream));
+    if (rest) // the others through the single call behind them on the same stream (its two-kernel path: the same bits)
+        for (size_t i = 0; i < count; ++i)
+            if (redio_chain_nblocks(h, msgs[i].n) && (reinterpret_cast<uintptr_t>(msgs[i].in) & 15) != 0)
+                if (int rc = redio_chain_enqueue(h, msgs[i].in, msgs[i].n, msgs[i].out, stream)) return rc;
+    return REDIO_OK;
 }
 
 // sizes what redio_chain_enqueue_u8 needs beyond the one-kernel form for messages of up to nbytes bytes: the converted samples,

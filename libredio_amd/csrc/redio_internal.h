@@ -41,6 +41,8 @@ size_t fftbig_tables_elems(int nfft);
 hipError_t fftbig_tables_build(const float2 *tw, float2 *tables, int nfft, hipStream_t s);
 hipError_t launch_fft(const FftPlanDev &p, const float2 *in, float2 *out, long nbatch, hipStream_t s, long in_stride = 0,
                       float2 *work = nullptr);
+// one launch over a list of count (1 ... REDIO_LIST_MAX) messages of nbatch[i] >= 1 consecutive transforms each; nfft 1024 only
+hipError_t launch_fft1k_list(const FftPlanDev &p, const float2 *const *in, float2 *const *out, const long *nbatch, int count, hipStream_t s);
 
 // overlap-save at nfft 1024 (one wave per block) and 4096: one kernel, no work buffers; at 4096 / 16384 tw_f / tw_i (4096) and
 // Tf / Ti (16384) are the plans' stage-ordered twiddle copies (redio_fft_twiddles_pass_dev)
@@ -65,6 +67,10 @@ hipError_t launch_chain_u8(const FftPlanDev &p, const void *bytes, const float *
                            hipStream_t s);
 hipError_t launch_chain(const FftPlanDev &p, const float2 *x, long n_in, const float *taps, int K, long D,
                         float2 *out, long nblocks, bool fused, hipStream_t s, unsigned long long *dbg = nullptr, long dbg_cap = 0);
+// chain_v4.hip: one launch over a list of count (1 ... REDIO_LIST_MAX) messages of the fused cf32 shapes, 16-byte aligned inputs,
+// nblocks[i] >= 1 each (hipErrorNotSupported: no such shape)
+hipError_t launch_chain_list(int K, long D, const float2 *const *x, float2 *const *out, const long *nblocks, int count, const float *taps,
+                             const float2 *tw, bool fused, hipStream_t s);
 long chain_v4_blocks_per_wave(long nblocks, int WPS = 2); // chain_v4.hip: consecutive blocks one wavefront of the fused kernel owns (WPS wavefronts per SIMD: the chain 2, the FIR alone 3)
 // the fused kernel's name as rocprofv3 prints it (spaces removed), so that a counter file can be tied to the kernel a plan launches
 const char *chain_kernel_name(int K, long D, bool fused_math, char *buf, size_t cap);

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import REDIO_FIR_COMPLEX, REDIO_FIR_FUSED, check, lib
+from . import REDIO_FIR_COMPLEX, REDIO_FIR_FUSED, check, lib, redio_msg
 
 _pf = C.POINTER(C.c_float)
 
@@ -80,6 +80,19 @@ class Fft:
         check(lib().redio_fft_enqueue(self._h, _dev_ptr(x), _dev_ptr(out), x.numel() // self.nfft, current_stream()), "fft_enqueue")
         return out
 
+    def enqueue_list(self, xs, outs=None):
+        """redio_fft_enqueue_list: every tensor of `xs` is its own message of whole nfft-sample transforms, all in one launch
+        (nfft 1024; other sizes one launch per message); the same bits as one call per message.  Returns the outputs."""
+        import torch
+        for x in xs:
+            assert x.dtype == torch.complex64 and x.numel() % self.nfft == 0, "messages of whole nfft-sample transforms"
+        if outs is None:
+            outs = [torch.empty_like(x) for x in xs]
+        assert len(outs) == len(xs) and all(o.numel() >= x.numel() for x, o in zip(xs, outs))
+        msgs = (redio_msg * max(len(xs), 1))(*[redio_msg(_dev_ptr(x), x.numel() // self.nfft, _dev_ptr(o)) for x, o in zip(xs, outs)])
+        check(lib().redio_fft_enqueue_list(self._h, msgs, len(xs), current_stream()), "fft_enqueue_list")
+        return outs
+
     def strided(self, x, nbatch, in_stride, out=None):
         """redio_fft_enqueue_strided: block b is x[b*in_stride : b*in_stride + nfft] (overlapping when in_stride < nfft,
         the overlap-save framing); the outputs are packed."""
@@ -151,6 +164,21 @@ class Chain:
         assert out.numel() >= nb * self.nfft
         check(lib().redio_chain_enqueue(self._h, _dev_ptr(x), x.numel(), _dev_ptr(out), current_stream()), "chain_enqueue")
         return out
+
+    def enqueue_list(self, xs, outs=None):
+        """redio_chain_enqueue_list: every cf32 tensor of `xs` is its own message, all in one launch on a fused plan; the same bits as
+        one call per message.  Returns the outputs, (nblocks, nfft) each."""
+        import torch
+        nbs = []
+        for x in xs:
+            assert x.dtype == torch.complex64
+            nbs.append(self.nblocks(x.numel()))
+        if outs is None:
+            outs = [torch.empty((nb, self.nfft), dtype=torch.complex64, device=x.device) for x, nb in zip(xs, nbs)]
+        assert len(outs) == len(xs) and all(o.numel() >= nb * self.nfft for o, nb in zip(outs, nbs))
+        msgs = (redio_msg * max(len(xs), 1))(*[redio_msg(_dev_ptr(x), x.numel(), _dev_ptr(o)) for x, o in zip(xs, outs)])
+        check(lib().redio_chain_enqueue_list(self._h, msgs, len(xs), current_stream()), "chain_enqueue_list")
+        return outs
 
     def reserve_u8(self, nbytes):
         """Size what from_bytes needs beyond the one-kernel form (other shapes, unaligned bytes) for messages of up to nbytes bytes."""
