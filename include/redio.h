@@ -293,7 +293,11 @@ int redio_pfb_reserve_two_pass(redio_pfb *h, size_t n_in, int ngroups);
  * librccl.so is loaded on first use; REDIO_ERR_COMM (text: redio_comm_last_error) if it is missing or a call fails.
  * One rank per process: rank 0 calls redio_comm_unique_id, the launcher hands the 128 bytes to every rank, every rank
  * calls redio_comm_init_rank on its own device.  Several ranks in one process (the reference's thread-per-block host):
- * redio_comm_init_all(comms, ndev, devices) then redio_pfb_exchange_all, which wraps all ranks' transfers in one group. */
+ * redio_comm_init_all(comms, ndev, devices) then redio_pfb_exchange_all, which wraps all ranks' transfers in one group.
+ * Test seam: when the environment variable REDIO_RCCL_LIB is set, the library at that path is the transport (loaded with
+ * RTLD_LOCAL on first use, its nine nccl* entry points resolved from it) and nothing else is tried; if it cannot be loaded or
+ * lacks an entry point every redio_comm_* call returns REDIO_ERR_COMM and redio_comm_last_error names the path.  The tests use
+ * it to run the exchange with several ranks on one device (tests/stub/fake_rccl.cpp); it is never set by the library or the host layer. */
 #define REDIO_COMM_ID_BYTES 128
 typedef struct redio_comm redio_comm;
 int redio_comm_unique_id(void *id128);

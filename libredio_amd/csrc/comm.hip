@@ -16,6 +16,7 @@
 #include <mutex>
 #include <new>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <vector>
 
@@ -35,21 +36,29 @@ struct Rccl {
 };
 Rccl g_rccl;
 std::once_flag g_once;
-thread_local char g_last_error[256] = ""; // per calling thread: one block thread per GPU may fail independently
-char g_load_error[256] = "";              // why librccl.so could not be used: written once (under g_once), read by every thread after
+thread_local char g_last_error[512] = ""; // per calling thread: one block thread per GPU may fail independently
+char g_load_error[512] = "";              // why librccl.so could not be used: written once (under g_once), read by every thread after
 
 void load_rccl()
 {
-    // a library of this name that is already mapped (e.g. the one PyTorch ships) is reused by the loader
-    const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-    for (const char *n : names) {
-        g_rccl.so = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-        if (g_rccl.so) break;
+    // REDIO_RCCL_LIB (a test seam, include/redio.h): the library at that path IS the transport and nothing else is tried.  RTLD_LOCAL
+    // keeps its nccl* names out of the global namespace of a process that also maps PyTorch's RCCL.
+    const char *lib = getenv("REDIO_RCCL_LIB");
+    const char *what = lib && *lib ? lib : "librccl.so"; // the name the error texts carry
+    if (lib && *lib) {
+        g_rccl.so = dlopen(lib, RTLD_NOW | RTLD_LOCAL);
+    } else {
+        // a library of this name that is already mapped (e.g. the one PyTorch ships) is reused by the loader
+        const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+        for (const char *n : names) {
+            g_rccl.so = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
+            if (g_rccl.so) break;
+        }
     }
-    if (!g_rccl.so) { snprintf(g_load_error, sizeof g_load_error, "librccl.so not loadable: %s", dlerror()); return; }
+    if (!g_rccl.so) { snprintf(g_load_error, sizeof g_load_error, "%s not loadable: %s", what, dlerror()); return; }
 #define RD_SYM(field, name) \
     g_rccl.field = reinterpret_cast<decltype(g_rccl.field)>(dlsym(g_rccl.so, name)); \
-    if (!g_rccl.field) { snprintf(g_load_error, sizeof g_load_error, "librccl.so lacks %s", name); return; }
+    if (!g_rccl.field) { snprintf(g_load_error, sizeof g_load_error, "%s lacks %s", what, name); return; }
     RD_SYM(GetUniqueId, "ncclGetUniqueId")
     RD_SYM(CommInitRank, "ncclCommInitRank")
     RD_SYM(CommInitAll, "ncclCommInitAll")
@@ -272,7 +281,7 @@ extern "C" int redio_pfb_exchange_all(redio_comm *const *comms, int ndev, const 
     const Rccl *r = rccl();
     if (!r) return REDIO_ERR_COMM;
     std::vector<size_t> off;
-    row_offsets(rows_per_rank, ndev, off);
+    const size_t total = row_offsets(rows_per_rank, ndev, off);
     const size_t fl = 2 * chans_per_rank;
     std::vector<std::vector<PeerXfer>> xs((size_t)ndev, std::vector<PeerXfer>((size_t)ndev));
     size_t np = 0;
@@ -280,6 +289,7 @@ extern "C" int redio_pfb_exchange_all(redio_comm *const *comms, int ndev, const 
         redio_comm *c = comms[g];
         if (!c || c->nranks != ndev) return REDIO_ERR_ARG;
         const size_t mine = rows_per_rank[g];
+        if ((mine && !d_grouped[g]) || (total && !d_out[g])) return REDIO_ERR_ARG; // the rule of redio_pfb_exchange, per rank
         for (int q = 0; q < ndev; ++q)
             xs[(size_t)g][(size_t)q] = {(const float *)d_grouped[g] + (size_t)q * mine * fl, mine * fl, (float *)d_out[g] + off[(size_t)q] * fl, rows_per_rank[q] * fl};
         const size_t p = xfer_pieces(xs[(size_t)g].data(), ndev);

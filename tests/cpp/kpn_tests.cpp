@@ -828,11 +828,16 @@ static int dev_c4_sharded(const char *in, const char *out, int want_dev)
     int ndev = 0;
     dev::check(redio_device_count(&ndev));
     if (want_dev > 0 && want_dev < ndev) ndev = want_dev;
+    const int have_dev = ndev;
+    if (const char *e = std::getenv("KPN_C4_RANKS")) ndev = std::atoi(e); // more ranks than devices (rank g on device g % have_dev): only a test transport allows that
+    if (have_dev < 1 || ndev < 1) return 5;
     while (M % ndev) --ndev;
+    std::vector<int> devices((size_t)ndev);
+    for (int g = 0; g < ndev; ++g) devices[(size_t)g] = g % have_dev;
     const size_t total_rows = x.size() / M, nout = total_rows - P + 1, cpg = (size_t)M / ndev;
     const std::vector<float> proto = dsputils::lpf_corrected((size_t)M * P, 0.45f / M);
     std::vector<redio_comm *> comms((size_t)ndev, nullptr);
-    dev::check(redio_comm_init_all(comms.data(), ndev, nullptr));
+    dev::check(redio_comm_init_all(comms.data(), ndev, devices.data()));
     std::vector<size_t> first((size_t)ndev), rows((size_t)ndev);
     for (int g = 0; g < ndev; ++g) { // contiguous output rows, the remainder to the lowest ranks (sharding.channelizer_time_shard)
         const size_t base = nout / ndev, extra = nout % ndev;
@@ -845,7 +850,7 @@ static int dev_c4_sharded(const char *in, const char *out, int want_dev)
     for (int g = 0; g < ndev; ++g)
         th.push_back(spawn([&, g]() { // the channelizer block of GPU g
             try {
-                dev::check(redio_set_device(g));
+                dev::check(redio_set_device(devices[(size_t)g]));
                 redio_pfb *h = nullptr;
                 dev::check(redio_pfb_create(&h, proto.data(), M, P, REDIO_FIR_FUSED));
                 const size_t nin = (rows[(size_t)g] + P - 1) * M;
@@ -866,7 +871,7 @@ static int dev_c4_sharded(const char *in, const char *out, int want_dev)
     dev::check(redio_pfb_exchange_all(comms.data(), ndev, d_grouped.data(), d_out.data(), rows.data(), cpg, streams.data()));
     std::vector<cf> all;
     for (int g = 0; g < ndev; ++g) {
-        dev::check(redio_set_device(g));
+        dev::check(redio_set_device(devices[(size_t)g]));
         dev::check(redio_stream_sync(streams[(size_t)g]));
         std::vector<cf> mine(nout * cpg);
         dev::check(redio_download(mine.data(), d_out[(size_t)g], mine.size() * sizeof(cf), nullptr));
