@@ -14,7 +14,7 @@
 //     a consumer receives a message only after its producer has enqueued the work that fills it, so its own work lands behind it in the
 //     same queue -- no event, no wait, no packet beyond the kernels themselves.  The kernels here fill the chip and are bound by HBM, so
 //     two of them side by side would only share the bandwidth; the host threads still overlap their launch work.  Blocks that move data
-//     over PCIe or synchronise with the host (to_device, to_host, resample) own a private stream so that a copy never sits in front of
+//     over PCIe or synchronise with the host (to_device, to_host, the mono resample) own a private stream so that a copy never sits in front of
 //     a kernel; set_stream_policy(PER_BLOCK) gives every block its own (graphs whose branches are many small kernels).
 //     Between DIFFERENT streams the order is made on demand, by the side that needs it: a buffer remembers the stream that wrote it
 //     and the streams that read it; a consumer on another stream records an event on the WRITER's stream at that moment (everything
@@ -747,6 +747,75 @@ inline void resample(Receiver<View<float>> din, Sender<View<float>> dout, double
         o.mem->buf->end_write(nullptr); // finished (synchronised above)
         dout.send_unwrap(o.sub(0, (size_t)gen));
     }
+}
+
+// nch mono streams through ONE batched converter in stream order (redio_src_enqueue): a message is [nch][frames] flattened, every
+// row one stream with samplerate::resample's semantics (output capacity floor(ratio*frames + 1) per row, samplerate.rs:59-87); the
+// message sent is [nch][gen] packed.  A compute block on the graph stream: after the first message at a constant ratio with integer
+// 1/ratio nothing synchronises (redio_src_enqueue_counts), the input is released by stream order like every other block's.  When
+// `counts` is given the handle's (queued, synchronised) call counts are written there at hang-up (tests, tools).
+inline void resample_channels(Receiver<View<float>> din, Sender<View<float>> dout, int nch, double ratio, int converter = 1,
+                              int mode = REDIO_SRC_EXACT, long *counts = nullptr)
+{
+    if (nch < 1) throw std::runtime_error("resample_channels: nch < 1");
+    BlockStream st;
+    Ring ring;
+    redio_src *h = nullptr;
+    check(redio_src_create(&h, converter, nch));
+    struct G {
+        redio_src *h; long *counts;
+        ~G()
+        {
+            if (counts) redio_src_enqueue_counts(h, counts, counts + 1);
+            redio_src_destroy(h);
+        }
+    } g{h, counts};
+    check(redio_src_set_mode(h, mode));
+    for (;;) {
+        auto d = din.recv();
+        if (d.len % (size_t)nch) throw std::runtime_error("resample_channels: message length is not a multiple of the channel count");
+        const long frames = (long)(d.len / (size_t)nch);
+        const long lout = (long)(ratio * (double)frames + 1.0);
+        auto o = ring.acquire<float>((size_t)lout * (size_t)nch, st);
+        long used = 0, gen = 0;
+        {
+            Reading<float> in(d, st);
+            check(redio_src_enqueue(h, d.data(), frames, frames, o.data(), lout, 0 /* packed */, ratio, &used, &gen, st));
+        }
+        publish(o, st);
+        dout.send_unwrap(o.sub(0, (size_t)gen * (size_t)nch));
+    }
+}
+
+// the channelizer's rows [nrows][nchan] cf32 -> [2*nchan][nrows] f32, plane 2c = Re and 2c + 1 = Im of channel c: resample_channels'
+// message for 2*nchan streams; and back
+inline void channel_planes(Receiver<View<std::complex<float>>> u, Sender<View<float>> v, int nchan)
+{
+    using cf = std::complex<float>;
+    if (nchan < 1) throw std::runtime_error("channel_planes: nchan < 1");
+    detail::run_block<cf, float>(u, v,
+                                 [&](const View<cf> &d) {
+                                     if (d.len % (size_t)nchan) throw std::runtime_error("channel_planes: message is not whole rows");
+                                     return 2 * d.len;
+                                 },
+                                 [&](const View<cf> &d, const View<float> &o, void *st) {
+                                     const size_t nrows = d.len / (size_t)nchan;
+                                     return redio_rows_to_planes_c32(d.data(), nrows, nchan, o.data(), nrows, st);
+                                 });
+}
+inline void plane_rows(Receiver<View<float>> u, Sender<View<std::complex<float>>> v, int nchan)
+{
+    using cf = std::complex<float>;
+    if (nchan < 1) throw std::runtime_error("plane_rows: nchan < 1");
+    detail::run_block<float, cf>(u, v,
+                                 [&](const View<float> &d) {
+                                     if (d.len % (2 * (size_t)nchan)) throw std::runtime_error("plane_rows: message is not whole planes");
+                                     return d.len / 2;
+                                 },
+                                 [&](const View<float> &d, const View<cf> &o, void *st) {
+                                     const size_t nrows = d.len / (2 * (size_t)nchan);
+                                     return redio_planes_to_rows_c32(d.data(), nrows, nrows, nchan, o.data(), st);
+                                 });
 }
 
 // the 64-channel polyphase filterbank (BASELINE configs[3]) as a block: rows of 64 channel samples out

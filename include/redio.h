@@ -69,7 +69,9 @@ int redio_stream_signal(void *stream, void *d_word, uint32_t value);
  * recorded once between redio_graph_begin/end on a stream created by redio_stream_create and replayed
  * with one submission.  Pointers and sizes are baked in: replay on the same buffers.  Run the sequence
  * once un-captured first: plans size their internal scratch on first use.
- * (redio_src_process synchronises and is not capturable; redio_*_create / *_destroy never are.) */
+ * (redio_src_process synchronises and is not capturable; redio_src_enqueue does not synchronise on its queued path but advances the
+ * converter's state with every call, so it is not capturable either and returns REDIO_ERR_UNSUPPORTED on a capturing stream;
+ * redio_*_create / *_destroy never are.) */
 typedef struct redio_graph redio_graph;
 int redio_graph_begin(void *stream);
 int redio_graph_end(void *stream, redio_graph **g);
@@ -403,6 +405,20 @@ int redio_src_set_mode(redio_src *h, int mode);
 int redio_src_process(redio_src *h, const void *d_in, long input_frames, long in_stride, void *d_out, long output_frames,
                       long out_stride, double src_ratio, int end_of_input, long *input_frames_used,
                       long *output_frames_gen, void *stream);
+/* redio_src_process(..., end_of_input = 0, ...) in stream order: the same outputs, counts, error codes and carried state for every
+ * converter, ratio and mode, and the two entries (with reset / set_ratio / set_mode) may be mixed freely on one handle.
+ *   QUEUED: a call the single-launch uniform path serves (constant ratio, 1/ratio an integer <= 256, sinc converters, EXACT or FAST)
+ *   whose tables for that increment already exist only launches kernels on `stream`: no synchronisation, no copy, no allocation; the
+ *   counts are final when the call returns.  d_in must stay valid until the stream has passed the call.
+ *   SYNCHRONISED: every other call (the first at a new increment, a varying or non-integer 1/ratio, a ratio that fell below the
+ *   history kept, converters 3 / 4, a shape without a single-launch kernel) runs redio_src_process's path including its wait.
+ * out_stride == 0: packed rows, d_out[nchan][*output_frames_gen]; nothing behind nchan * gen floats is written (d_out holds
+ * nchan * output_frames floats at most).  One handle belongs to one stream at a time; the caller orders its use on different streams.
+ * Not capturable (see redio_graph_begin): REDIO_ERR_UNSUPPORTED on a capturing stream, state untouched. */
+int redio_src_enqueue(redio_src *h, const void *d_in, long input_frames, long in_stride, void *d_out, long output_frames,
+                      long out_stride, double src_ratio, long *input_frames_used, long *output_frames_gen, void *stream);
+/* calls of redio_src_enqueue on this handle that were queued / that synchronised */
+int redio_src_enqueue_counts(const redio_src *h, long *queued, long *synchronised);
 /* host buffers, interleaved frames of the handle's nchan channels (mono: plain samples), synchronous: the body of the
  * src_process drop-in (include/samplerate.h); every channel is converted exactly as a mono stream */
 int redio_src_process_host(redio_src *h, const float *data_in, long input_frames, float *data_out, long output_frames,
@@ -420,6 +436,14 @@ int redio_mul_f32(const void *d_a, const void *d_b, void *d_out, size_t n, void 
 int redio_add_f32(const void *d_a, const void *d_b, void *d_out, size_t n, void *stream);
 int redio_mul_c32(const void *d_a, const void *d_b, void *d_out, size_t n, void *stream);
 int redio_add_c32(const void *d_a, const void *d_b, void *d_out, size_t n, void *stream);
+
+/* ---- layout: the channelizer's rows <-> one contiguous mono stream per channel component ----
+ * d_rows cf32 [nrows][nchan] (redio_pfb_enqueue's output); d_planes f32 [2*nchan][plane_stride]: plane 2c = Re of channel c, plane
+ * 2c + 1 = Im, each plane uses its first nrows entries (the rest is not touched) -- redio_src_enqueue's rows for 2*nchan channels.
+ * Pure data movement: every 32-bit word arrives unchanged.  nrows == 0: REDIO_OK, no launch; nchan < 1, plane_stride < nrows, or a
+ * NULL / not 4-byte aligned pointer with work to do: REDIO_ERR_ARG.  Launch only (capturable). */
+int redio_rows_to_planes_c32(const void *d_rows, size_t nrows, int nchan, void *d_planes, size_t plane_stride, void *stream);
+int redio_planes_to_rows_c32(const void *d_planes, size_t plane_stride, size_t nrows, int nchan, void *d_rows, void *stream);
 
 /* order-free 64-bit sum of the n 32-bit words at d_words, ADDED to the u64 at d_sum_u64 (device memory the caller zeroed; one atomic
  * per workgroup): the checking sink of a device-resident graph -- reads every word a block produced, exact whatever the order */

@@ -141,6 +141,10 @@ def lib():
     _sig(L.redio_src_set_ratio, i, vp, C.c_double)
     _sig(L.redio_src_set_mode, i, vp, i)
     _sig(L.redio_src_process, i, vp, vp, C.c_long, C.c_long, vp, C.c_long, C.c_long, C.c_double, i, pl, pl, vp)
+    _sig(L.redio_src_enqueue, i, vp, vp, C.c_long, C.c_long, vp, C.c_long, C.c_long, C.c_double, pl, pl, vp)
+    _sig(L.redio_src_enqueue_counts, i, vp, pl, pl)
+    _sig(L.redio_rows_to_planes_c32, i, vp, sz, i, vp, sz, vp)
+    _sig(L.redio_planes_to_rows_c32, i, vp, sz, sz, i, vp, vp)
     _sig(L.redio_src_process_host, i, vp, pf, C.c_long, pf, C.c_long, C.c_double, i, pl, pl)
     _sig(L.redio_src_table, i, i, pf, C.POINTER(i), C.POINTER(i))
     _sig(L.redio_src_path_counts, i, vp, pl, pl)
@@ -239,4 +243,4 @@ def check(code, what="redio"):
 
 
 from . import bitfount, dsputils, kissfft, kpn_dev, plans, samplerate  # noqa: E402,F401
-from .plans import Chain, Channelizer, Comm, Fft, Fir, Graph, OverlapSave, Src, Stream, channelizer_all_to_all, current_stream, synth_f32, synth_iq  # noqa: E402,F401
+from .plans import Chain, Channelizer, Comm, Fft, Fir, Graph, OverlapSave, Src, Stream, channelizer_all_to_all, current_stream, planes_to_rows, rows_to_planes, synth_f32, synth_iq  # noqa: E402,F401

@@ -120,6 +120,10 @@ struct redio_src {
                                              // the state's channels for an interleaved message, 1 for the batched rows (independent mono streams)
     size_t stage_in_cap, stage_out_cap;
     hipStream_t host_stream; // the host-buffer entry point's own stream: states on different threads do not serialise
+    // redio_src_enqueue: calls that only launched (nothing waited for them) / calls that ran the synchronising path; in_flight: a queued
+    // call's kernels may still be reading or writing the buffer images (reset waits for them before it clears the images)
+    long enq_queued, enq_synchronised;
+    int in_flight;
 };
 
 static inline double fmod_one(double x) { return src_fmod_one(x); }
@@ -129,6 +133,10 @@ extern "C" int redio_src_reset(redio_src *s)
 {
     if (!s) return REDIO_SRC_ERR_BAD_STATE;
     SRC_TRY(hipSetDevice(s->device));
+    if (s->in_flight) { // queued calls (redio_src_enqueue) may still be running on a non-blocking stream: the memsets below must not pass them
+        SRC_TRY(hipDeviceSynchronize());
+        s->in_flight = 0;
+    }
     s->last_ratio = 0.0;
     s->last_position = 0.0;
     if (s->converter >= 3) { // zoh_reset / linear_reset
@@ -171,6 +179,7 @@ extern "C" int redio_src_create(redio_src **h, int converter, int nchan)
     s->periodic_launches = s->general_launches = s->tile_launches = 0;
     s->d_T2 = nullptr; s->nm = 0; s->fast_scale = 0.0; s->d_Hp = nullptr; s->fastp_nc = 0; s->mode = REDIO_SRC_EXACT; s->window_ok = 1; s->zl_channels = 1;
     s->h_coeffs = coeffs;
+    s->enq_queued = s->enq_synchronised = 0; s->in_flight = 0;
     if (zl) {
         s->b_len = 0; s->buf_stride = 0;
         hipError_t ez = hipMalloc((void **)&s->d_last, (size_t)nchan * sizeof(float));
@@ -578,7 +587,7 @@ static int flush_epoch(redio_src *f, long first, long count, float *d_out, long 
 // part of the buffer image that later calls can read.  Returns 1 when it handled the call, 0 when the
 // call is not eligible (the epoch path then runs), < 0 / error code on failure.
 static int try_uniform_window(redio_src *f, const SrcInput &in, long in_count, float *d_out, long out_stride, long out_count,
-                              double src_ratio_arg, int end_of_input, long *in_used_out, long *out_gen_out, hipStream_t st)
+                              double src_ratio_arg, int end_of_input, long *in_used_out, long *out_gen_out, hipStream_t st, int *launch_only)
 {
     if (end_of_input || f->b_real_end >= 0 || !in.dev) return 0;
     if (fabs(f->last_ratio - src_ratio_arg) > 1e-10) return 0;
@@ -640,10 +649,14 @@ static int try_uniform_window(redio_src *f, const SrcInput &in, long in_count, f
         b_current = (int)(((long)b_current + run * S) % f->b_len);
     }
     if (a_in0 < 0) a_in0 = A0 + b_end; // no input consumed: every index is served by the old image
+    const bool fast = f->mode == REDIO_SRC_FAST;
+    // tables of this increment already on the device?  Then nothing below allocates, copies or waits: the call is launches only
+    // (redio_src_enqueue reports it as queued); the two prepare_* calls return at their first line
+    const bool cached = f->fast_inc == inc && f->d_cl && (!fast || (f->d_T2 && f->fast_scale == scale && f->nm == ((f->ncl + f->ncr + S + 127) & ~127)));
     int rc = prepare_uniform(f, inc);
     if (rc) return rc;
-    const bool fast = f->mode == REDIO_SRC_FAST;
     if (fast) { rc = prepare_fast_taps(f, S, scale); if (rc) return rc; }
+    if (out_stride == 0) out_stride = out_gen > 0 ? out_gen : 1; // packed rows (redio_src_enqueue): the count is known before the launch
     // the final image.  A call without a move (A0 == 0: the library only appended) appends the new samples to the LIVE image in place, like
     // prepare_data above -- the launch reads the image below a_in0 only and the append writes from a_in0 on, so the image keeps everything
     // since its last move and a small message costs its own samples, not the widest filter's reach (round 5; advisor, round 4).
@@ -666,6 +679,7 @@ static int try_uniform_window(redio_src *f, const SrcInput &in, long in_count, f
     f->last_ratio = src_ratio;
     if (in_used_out) *in_used_out = in_used;
     if (out_gen_out) *out_gen_out = out_gen;
+    if (launch_only) *launch_only = cached ? 1 : 0;
     return 1;
 }
 
@@ -886,16 +900,46 @@ static int try_general_window(redio_src *f, const SrcInput &in, long in_count, f
 }
 
 // src_process + sinc_mono_vari_process; outputs land in d_out[nchan][out_stride]
+// packed (redio_src_enqueue only): out_stride == 0 asks for rows [nchan][output_frames_gen].  The single-launch uniform path knows the
+// count before it launches and writes packed rows itself; every other path converts into the handle's row scratch at stride
+// output_frames and the rows are copied out packed at the end (nothing behind nchan * gen floats of d_out is written).
+// *launch_only (may be NULL) is set when the call only launched kernels: no allocation, no copy, nothing the host must keep alive.
 static int src_process_impl(redio_src *f, const SrcInput &in, long input_frames, float *d_out, long out_stride, long output_frames,
-                            double src_ratio_arg, int end_of_input, long *in_used_out, long *out_gen_out, hipStream_t st)
+                            double src_ratio_arg, int end_of_input, long *in_used_out, long *out_gen_out, hipStream_t st,
+                            bool packed = false, int *launch_only = nullptr)
 {
+    if (launch_only) *launch_only = 0;
     if (is_bad_src_ratio(src_ratio_arg)) return REDIO_SRC_ERR_BAD_SRC_RATIO;
     if (input_frames < 0) input_frames = 0;
     if (output_frames < 0) output_frames = 0;
     if (f->last_ratio < (1.0 / SRC_MAX_RATIO)) f->last_ratio = src_ratio_arg;
+    long gen_local = 0;
+    if (!out_gen_out) out_gen_out = &gen_local;
+    packed = packed && out_stride == 0;
+    if (packed && f->nchan == 1) { packed = false; out_stride = output_frames > 0 ? output_frames : 1; } // one row is packed at any stride
+    float *d_packed = nullptr;
+    auto rows_to_scratch = [&]() -> int {
+        const size_t need = (size_t)f->nchan * (size_t)(output_frames > 0 ? output_frames : 1);
+        if (need > f->rows_out_cap) {
+            hipFree(f->d_rows_out);
+            f->d_rows_out = nullptr; f->rows_out_cap = 0;
+            SRC_TRY(hipMalloc((void **)&f->d_rows_out, (need + 1024) * sizeof(float)));
+            f->rows_out_cap = need + 1024;
+        }
+        d_packed = d_out;
+        d_out = f->d_rows_out;
+        out_stride = output_frames > 0 ? output_frames : 1;
+        return REDIO_OK;
+    };
+    auto pack_rows = [&](int code) -> int {
+        if (code != REDIO_OK || !d_packed || *out_gen_out <= 0) return code;
+        SRC_TRY(launch_src_copy_rows(f->d_rows_out, out_stride, 0, d_packed, *out_gen_out, 0, *out_gen_out, f->nchan, st));
+        return REDIO_OK;
+    };
     if (f->converter >= 3) {
         if (!in.dev && input_frames > 0) return REDIO_SRC_ERR_BAD_DATA_PTR;
-        return zoh_linear_impl(f, in.dev, in.in_stride, input_frames, d_out, out_stride, output_frames, src_ratio_arg, in_used_out, out_gen_out, st);
+        if (packed) { const int prc = rows_to_scratch(); if (prc) return prc; }
+        return pack_rows(zoh_linear_impl(f, in.dev, in.in_stride, input_frames, d_out, out_stride, output_frames, src_ratio_arg, in_used_out, out_gen_out, st));
     }
 
     const long in_count = input_frames, out_count = output_frames;
@@ -913,11 +957,14 @@ static int src_process_impl(redio_src *f, const SrcInput &in, long input_frames,
     }
     if (f->window_ok && !f->front_short) {
         const int handled = try_uniform_window(f, in, in_count, d_out, out_stride, out_count, src_ratio_arg, end_of_input, in_used_out,
-                                               out_gen_out, st);
+                                               out_gen_out, st, launch_only);
         if (handled == 1) return REDIO_OK;
         if (handled != 0) return handled;
+    }
+    if (packed) { const int prc = rows_to_scratch(); if (prc) return prc; }
+    if (f->window_ok && !f->front_short) {
         const int general = try_general_window(f, in, in_count, d_out, out_stride, out_count, src_ratio_arg, end_of_input, in_used_out, out_gen_out, st);
-        if (general == 1) return REDIO_OK;
+        if (general == 1) return pack_rows(REDIO_OK);
         if (general != 0) return general;
     }
     int rc = ensure_scratch(f, (size_t)out_count);
@@ -989,7 +1036,53 @@ static int src_process_impl(redio_src *f, const SrcInput &in, long input_frames,
     f->last_position = input_index;
     f->last_ratio = src_ratio;
     if (in_used_out) *in_used_out = in_used;
-    if (out_gen_out) *out_gen_out = out_gen;
+    *out_gen_out = out_gen;
+    return pack_rows(REDIO_OK);
+}
+
+static bool src_stream_is_capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+// redio_src_process without end_of_input and without the wait, where nothing needs one.  A call the single-launch uniform path serves
+// from tables that are already on the device passes everything to its kernels by value: the counts and the next buffer state come
+// from host counters, so the call returns with the work queued.  Every other call keeps host arrays (per-output parameters, periodic
+// tables) alive until its uploads have run, or builds tables: it waits for the stream as redio_src_process does.
+extern "C" int redio_src_enqueue(redio_src *s, const void *d_in, long input_frames, long in_stride, void *d_out, long output_frames,
+                                 long out_stride, double src_ratio, long *input_frames_used, long *output_frames_gen, void *stream)
+{
+    if (input_frames_used) *input_frames_used = 0;
+    if (output_frames_gen) *output_frames_gen = 0;
+    if (!s) return REDIO_SRC_ERR_BAD_STATE;
+    if ((!d_in && input_frames > 0) || (!d_out && output_frames > 0)) return REDIO_SRC_ERR_BAD_DATA_PTR;
+    if (in_stride < 0 || out_stride < 0) return REDIO_ERR_ARG;
+    SRC_TRY(hipSetDevice(s->device));
+    // the state advances with every call: a replayed capture would repeat this call's offsets on a later call's data
+    if (src_stream_is_capturing((hipStream_t)stream)) return REDIO_ERR_UNSUPPORTED;
+    SrcInput in = {nullptr, (const float *)d_in, in_stride};
+    s->zl_channels = 1; // rows are independent mono streams
+    int launch_only = 0;
+    int rc = src_process_impl(s, in, input_frames, (float *)d_out, out_stride, output_frames, src_ratio, 0, input_frames_used,
+                              output_frames_gen, (hipStream_t)stream, true, &launch_only);
+    if (launch_only) {
+        ++s->enq_queued;
+        s->in_flight = 1;
+        return rc;
+    }
+    ++s->enq_synchronised;
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (e == hipSuccess) s->in_flight = 0; // one handle, one stream at a time: everything queued before has finished too
+    if (rc) return rc;
+    return hip_rc(e);
+}
+
+extern "C" int redio_src_enqueue_counts(const redio_src *s, long *queued, long *synchronised)
+{
+    if (!s) return REDIO_SRC_ERR_BAD_STATE;
+    if (queued) *queued = s->enq_queued;
+    if (synchronised) *synchronised = s->enq_synchronised;
     return REDIO_OK;
 }
 
@@ -1009,6 +1102,7 @@ extern "C" int redio_src_process(redio_src *s, const void *d_in, long input_fram
     int rc = src_process_impl(s, in, input_frames, (float *)d_out, out_stride, output_frames, src_ratio, end_of_input,
                               input_frames_used, output_frames_gen, (hipStream_t)stream);
     hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (e == hipSuccess) s->in_flight = 0;
     if (rc) return rc;
     return hip_rc(e);
 }

@@ -288,6 +288,37 @@ class Src:
         check(rc, "src_process")
         return out[:, : gen.value], used.value
 
+    def enqueue(self, x, ratio, out=None, output_frames=None, packed=False):
+        """redio_src_enqueue: process() without end_of_input in stream order -- a uniform-phase call (constant ratio, integer 1/ratio)
+        after the first at its ratio only launches, nothing synchronises.  x: float32 CUDA tensor [nchan, frames], rows contiguous
+        (any row stride).  out: float32 CUDA tensor of at least nchan * capacity elements (allocated when None).  Returns
+        (out[nchan, gen], input_frames_used, gen); with packed=True the rows are written back to back and the result is a
+        contiguous [nchan, gen] view of the start of `out`."""
+        import torch
+        assert x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] == self.nchan and x.is_cuda and (x.shape[1] <= 1 or x.stride(1) == 1)
+        frames = x.shape[1]
+        cap = int(ratio * frames + 1.0) if output_frames is None else int(output_frames)
+        if out is None:
+            out = torch.empty((self.nchan, max(cap, 1)), dtype=torch.float32, device=x.device)
+        assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.numel() >= self.nchan * cap
+        stride = 0 if packed else (out.stride(0) if out.dim() == 2 else max(cap, 1))
+        used, gen = C.c_long(0), C.c_long(0)
+        rc = lib().redio_src_enqueue(self._h, C.c_void_p(x.data_ptr()), frames, x.stride(0), C.c_void_p(out.data_ptr()), cap, stride,
+                                     float(ratio), C.byref(used), C.byref(gen), current_stream())
+        check(rc, "src_enqueue")
+        g = gen.value
+        if packed:
+            return out.reshape(-1)[: self.nchan * g].view(self.nchan, g), used.value, g
+        if out.dim() == 2:
+            return out[:, :g], used.value, g
+        return out.reshape(-1)[: self.nchan * stride].view(self.nchan, stride)[:, :g], used.value, g
+
+    def enqueue_counts(self):
+        """(calls of enqueue() that only launched, calls that ran the synchronising path)."""
+        a, b = C.c_long(0), C.c_long(0)
+        check(lib().redio_src_enqueue_counts(self._h, C.byref(a), C.byref(b)), "src_enqueue_counts")
+        return a.value, b.value
+
     def reset(self):
         check(lib().redio_src_reset(self._h), "src_reset")
 
@@ -359,6 +390,33 @@ def synth_f32(seed, first, n, device="cuda"):
     import torch
     out = torch.empty(n, dtype=torch.float32, device=device)
     check(lib().redio_synth_f32(_dev_ptr(out), seed, first, n, current_stream()), "synth_f32")
+    return out
+
+
+def rows_to_planes(rows, out=None, plane_stride=None):
+    """redio_rows_to_planes_c32: complex64 [nrows, nchan] (the channelizer's rows) -> float32 [2*nchan, plane_stride], plane 2c = Re and
+    plane 2c + 1 = Im of channel c in its first nrows entries -- Src.enqueue's rows for 2*nchan mono streams."""
+    import torch
+    assert rows.dtype == torch.complex64 and rows.dim() == 2
+    nrows, nchan = rows.shape
+    stride = nrows if plane_stride is None else int(plane_stride)
+    if out is None:
+        out = torch.empty((2 * nchan, stride), dtype=torch.float32, device=rows.device)
+    assert out.dtype == torch.float32 and out.numel() >= 2 * nchan * stride
+    check(lib().redio_rows_to_planes_c32(_dev_ptr(rows), nrows, nchan, _dev_ptr(out), stride, current_stream()), "rows_to_planes")
+    return out
+
+
+def planes_to_rows(planes, nrows=None, out=None):
+    """redio_planes_to_rows_c32, the inverse: float32 [2*nchan, plane_stride] -> complex64 [nrows, nchan] (nrows: plane_stride when None)."""
+    import torch
+    assert planes.dtype == torch.float32 and planes.dim() == 2 and planes.shape[0] % 2 == 0
+    nchan, stride = planes.shape[0] // 2, planes.shape[1]
+    nrows = stride if nrows is None else int(nrows)
+    if out is None:
+        out = torch.empty((nrows, nchan), dtype=torch.complex64, device=planes.device)
+    assert out.dtype == torch.complex64 and out.numel() >= nrows * nchan
+    check(lib().redio_planes_to_rows_c32(_dev_ptr(planes), stride, nrows, nchan, _dev_ptr(out), current_stream()), "planes_to_rows")
     return out
 
 
