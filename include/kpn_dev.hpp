@@ -659,6 +659,39 @@ inline void fft(Receiver<View<std::complex<float>>> pin, Sender<View<std::comple
                               [&](const View<cf> &d, const View<cf> &o, void *st) { return redio_fft_enqueue(h, d.data(), o.data(), d.len / block_size, st); });
 }
 
+// kiss_fftr as a block (redio_fftr_*): every message is a whole number of block_size real samples; each block of block_size
+// samples becomes block_size / 2 + 1 bins.  Output through the ring, no host wait.
+inline void fftr(Receiver<View<float>> pin, Sender<View<std::complex<float>>> cout, uint32_t block_size)
+{
+    using cf = std::complex<float>;
+    redio_fftr *h = nullptr;
+    check(redio_fftr_create(&h, (int)block_size, 0));
+    struct G { redio_fftr *h; ~G() { redio_fftr_destroy(h); } } g{h};
+    const size_t nbins = block_size / 2 + 1;
+    detail::run_block<float, cf>(pin, cout,
+                                 [&](const View<float> &d) {
+                                     if (d.len % block_size) throw std::runtime_error("assert!(din.len() == block_size) (kissfft.rs:24)");
+                                     return d.len / block_size * nbins;
+                                 },
+                                 [&](const View<float> &d, const View<cf> &o, void *st) { return redio_fftr_enqueue(h, d.data(), o.data(), d.len / block_size, st); });
+}
+
+// kiss_fftri as a block: every message is a whole number of block_size / 2 + 1 bins; each becomes block_size real samples (unnormalised)
+inline void fftri(Receiver<View<std::complex<float>>> pin, Sender<View<float>> cout, uint32_t block_size)
+{
+    using cf = std::complex<float>;
+    redio_fftr *h = nullptr;
+    check(redio_fftr_create(&h, (int)block_size, 1));
+    struct G { redio_fftr *h; ~G() { redio_fftr_destroy(h); } } g{h};
+    const size_t nbins = block_size / 2 + 1;
+    detail::run_block<cf, float>(pin, cout,
+                                 [&](const View<cf> &d) {
+                                     if (d.len % nbins) throw std::runtime_error("assert!(din.len() == block_size) (kissfft.rs:24)");
+                                     return d.len / nbins * (size_t)block_size;
+                                 },
+                                 [&](const View<cf> &d, const View<float> &o, void *st) { return redio_fftr_enqueue(h, d.data(), o.data(), d.len / nbins, st); });
+}
+
 // the fused north-star chain as one block
 inline void fir_fft_chain(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<float> taps,
                           size_t decim, int nfft, bool fused)

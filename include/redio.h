@@ -155,6 +155,33 @@ int redio_fft_enqueue_strided(redio_fft *h, const void *d_in, void *d_out, size_
  * every other size runs redio_fft_enqueue per entry -- the same bits, one launch per entry. */
 int redio_fft_enqueue_list(redio_fft *h, const redio_msg *msgs, size_t count, void *stream);
 
+/* ---- the real-input transform: kiss_fftr / kiss_fftri of the kissfft library (tools/kiss_fftr.c), device-resident, batched ----
+ * The other half of the library kiss_fft.h stands in for; the reference's real streams (dsputils::convolve, samplerate::resample,
+ * the magnitudes of rtlsdr / bitfount) get their spectra without widening to cf32.  nfft = N real points, N even; M = N / 2.
+ * A forward plan (kiss_fftr) takes nbatch rows of N f32 and writes nbatch rows of M + 1 cf32 (bins 0 ... M; the imaginary parts of
+ * bins 0 and M are +0); an inverse plan (kiss_fftri) takes rows of M + 1 cf32 (the imaginary parts of bins 0 and M are ignored) and
+ * writes rows of N f32, unnormalised: inverse(forward(x)) = N x.  Arithmetic: the complex transform of size M (redio_fft_*, the same
+ * bits) and the published split loop with every multiply and add rounded on its own ("real-input transform").
+ * N = 2048 is ONE kernel that moves 8 bytes per real sample and needs no scratch (redio_fftr_is_fused() == 1); every other size runs
+ * the complex plan and a split pass through plan-owned scratch (16 bytes per real sample).
+ * create: odd nfft or nfft < 2 -> REDIO_ERR_ARG; nfft > 2^25 -> REDIO_ERR_UNSUPPORTED. */
+typedef struct redio_fftr redio_fftr;
+int redio_fftr_create(redio_fftr **h, int nfft /* real points */, int inverse);
+int redio_fftr_destroy(redio_fftr *h);
+/* scratch of the generic path for up to nbatch rows per call: afterwards an enqueue of up to nbatch rows neither allocates nor
+ * synchronises.  Un-reserved, the scratch grows on first use (REDIO_ERR_NOT_RESERVED while the stream is being captured). */
+int redio_fftr_reserve(redio_fftr *h, size_t nbatch);
+int redio_fftr_is_fused(const redio_fftr *h);
+/* kiss_fftr (forward plan) / kiss_fftri (inverse plan) over nbatch packed rows.  d_in != d_out, both 8-byte aligned;
+ * NULL or aliasing pointers -> REDIO_ERR_ARG; nbatch == 0 -> REDIO_OK, no launch. */
+int redio_fftr_enqueue(redio_fftr *h, const void *d_in, void *d_out, size_t nbatch, void *stream);
+/* the same with row b at d_in + b * in_stride and d_out + b * out_stride, counted in elements of their own side (f32 on the real
+ * side, cf32 on the spectrum side).  out_stride >= the output row length; the real-side stride is even (rows stay 8-byte aligned);
+ * a forward in_stride < nfft gives overlapping frames (the sliding spectrogram, as redio_fft_enqueue_strided does for complex
+ * blocks); in_stride <= 0 or any other stride -> REDIO_ERR_ARG.  An inverse generic-path call with out_stride != nfft is one
+ * complex launch per row. */
+int redio_fftr_enqueue_strided(redio_fftr *h, const void *d_in, void *d_out, size_t nbatch, long in_stride, long out_stride, void *stream);
+
 /* ---- C2 chain: FIR (ntaps, decimate decim) -> nfft-point forward FFT of consecutive blocks ----
  * Fused single kernel for nfft = 1024 with (ntaps, decim) in {(127, 5), (127, 3), (127, 1), (63, 5), (63, 1)} on a
  * 16-byte aligned stream; other shapes run the FIR and FFT kernels back to back through a plan-owned

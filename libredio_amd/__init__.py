@@ -103,6 +103,12 @@ def lib():
     _sig(L.redio_fft_destroy, i, vp)
     _sig(L.redio_fft_enqueue, i, vp, vp, vp, sz, vp)
     _sig(L.redio_fft_enqueue_list, i, vp, C.POINTER(redio_msg), sz, vp)
+    _sig(L.redio_fftr_create, i, C.POINTER(vp), i, i)
+    _sig(L.redio_fftr_destroy, i, vp)
+    _sig(L.redio_fftr_reserve, i, vp, sz)
+    _sig(L.redio_fftr_is_fused, i, vp)
+    _sig(L.redio_fftr_enqueue, i, vp, vp, vp, sz, vp)
+    _sig(L.redio_fftr_enqueue_strided, i, vp, vp, vp, sz, C.c_long, C.c_long, vp)
     _sig(L.redio_chain_enqueue_list, i, vp, C.POINTER(redio_msg), sz, vp)
     _sig(L.redio_chain_create, i, C.POINTER(vp), pf, sz, sz, i, u)
     _sig(L.redio_chain_destroy, i, vp)
@@ -193,7 +199,7 @@ def lib():
 
 
 def kisslib():
-    """The loaded libkissfft.so drop-in (kiss_fft_alloc / kiss_fft / kiss_fft_cleanup)."""
+    """The loaded libkissfft.so drop-in (kiss_fft_alloc / kiss_fft / kiss_fft_cleanup, and the real-input kiss_fftr*)."""
     global _kiss
     if _kiss is not None:
         return _kiss
@@ -208,6 +214,10 @@ def kisslib():
     _sig(K.kiss_fft_next_fast_size, C.c_int, C.c_int)
     _sig(K.kiss_fft_free, None, C.c_void_p)
     _sig(K.redio_kiss_fft_set_spin_ns, None, C.c_long)
+    _sig(K.kiss_fftr_alloc, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_size_t))
+    _sig(K.kiss_fftr, None, C.c_void_p, C.c_void_p, C.c_void_p)
+    _sig(K.kiss_fftri, None, C.c_void_p, C.c_void_p, C.c_void_p)
+    _sig(K.kiss_fftr_free, None, C.c_void_p)
     _kiss = K
     return K
 
@@ -243,4 +253,4 @@ def check(code, what="redio"):
 
 
 from . import bitfount, dsputils, kissfft, kpn_dev, plans, samplerate  # noqa: E402,F401
-from .plans import Chain, Channelizer, Comm, Fft, Fir, Graph, OverlapSave, Src, Stream, channelizer_all_to_all, current_stream, planes_to_rows, rows_to_planes, synth_f32, synth_iq  # noqa: E402,F401
+from .plans import Chain, Channelizer, Comm, Fft, Fftr, Fir, Graph, OverlapSave, Src, Stream, channelizer_all_to_all, current_stream, planes_to_rows, rows_to_planes, synth_f32, synth_iq  # noqa: E402,F401

@@ -1,6 +1,8 @@
 // kissfft_shim.cpp -- libkissfft.so: the C symbols of src/kissfft/src/kissfft.rs:11-16 on top of
-// the redio FFT plan.  See include/kiss_fft.h for the contract.
+// the redio FFT plan, and the library's real-input half (kiss_fftr*) on top of redio_fftr_*.  See include/kiss_fft.h and
+// include/kiss_fftr.h for the contract.
 #include "../../include/kiss_fft.h"
+#include "../../include/kiss_fftr.h"
 #include "../../include/redio.h"
 #include <math.h>
 #include <stdio.h>
@@ -153,5 +155,96 @@ extern "C" void kiss_fft_free(kiss_fft_cfg st)
     redio_host_free(st->flag);
     redio_stream_destroy(st->stream);
     free(st->gather);
+    if (st->on_heap) free(st);
+}
+
+// ---------------------------------------------------------------- kiss_fftr / kiss_fftri (include/kiss_fftr.h)
+struct kiss_fftr_state {
+    int nfft; // real points
+    int inverse;
+    int on_heap;
+    redio_fftr *plan;
+    void *d_time; // nfft f32 on the device
+    void *d_freq; // nfft / 2 + 1 cf32
+    void *stream;
+};
+
+extern "C" kiss_fftr_cfg kiss_fftr_alloc(int nfft, int inverse_fft, void *mem, size_t *lenmem)
+{
+    if (nfft & 1) {
+        fprintf(stderr, "Real FFT optimization must be even.\n");
+        return NULL;
+    }
+    const size_t need = sizeof(kiss_fftr_state) + alignof(kiss_fftr_state) - 1; // placement as kiss_fft_alloc
+    kiss_fftr_state *st = NULL;
+    if (lenmem == NULL) {
+        st = (kiss_fftr_state *)malloc(sizeof(kiss_fftr_state));
+        if (st) st->on_heap = 1;
+    } else {
+        if (mem != NULL && *lenmem >= need) {
+            const uintptr_t a = ((uintptr_t)mem + alignof(kiss_fftr_state) - 1) & ~(uintptr_t)(alignof(kiss_fftr_state) - 1);
+            st = (kiss_fftr_state *)a;
+            st->on_heap = 0;
+        }
+        *lenmem = need;
+    }
+    if (!st) return NULL;
+    st->nfft = nfft; st->inverse = inverse_fft ? 1 : 0; st->plan = NULL; st->d_time = st->d_freq = NULL; st->stream = NULL;
+    if (nfft < 2) { if (st->on_heap) free(st); return NULL; }
+    int rc = redio_fftr_create(&st->plan, nfft, st->inverse);
+    if (rc == REDIO_OK) rc = redio_fftr_reserve(st->plan, 1);
+    if (rc == REDIO_OK) rc = redio_malloc(&st->d_time, (size_t)nfft * sizeof(kiss_fft_scalar));
+    if (rc == REDIO_OK) rc = redio_malloc(&st->d_freq, ((size_t)nfft / 2 + 1) * sizeof(kiss_fft_cpx));
+    if (rc == REDIO_OK) rc = redio_stream_create(&st->stream);
+    if (rc != REDIO_OK) {
+        fprintf(stderr, "kiss_fftr_alloc(%d): %s\n", nfft, redio_strerror(rc));
+        redio_fftr_destroy(st->plan);
+        redio_free(st->d_time);
+        redio_free(st->d_freq);
+        if (st->on_heap) free(st);
+        return NULL;
+    }
+    return st;
+}
+
+// one transform through the device buffers; on any failure the output is poisoned (no error return in this interface)
+static void kiss_fftr_run(kiss_fftr_state *st, int inverse, const char *name, const void *in, void *out)
+{
+    const size_t tbytes = (size_t)st->nfft * sizeof(kiss_fft_scalar), fbytes = ((size_t)st->nfft / 2 + 1) * sizeof(kiss_fft_cpx);
+    const size_t ibytes = inverse ? fbytes : tbytes, obytes = inverse ? tbytes : fbytes;
+    void *d_in = inverse ? st->d_freq : st->d_time, *d_out = inverse ? st->d_time : st->d_freq;
+    if (st->inverse != inverse) {
+        fprintf(stderr, "kiss fft usage error: improper alloc\n");
+    } else {
+        int rc = redio_upload(d_in, in, ibytes, st->stream);
+        if (rc == REDIO_OK) rc = redio_fftr_enqueue(st->plan, d_in, d_out, 1, st->stream);
+        if (rc == REDIO_OK) rc = redio_download(out, d_out, obytes, st->stream);
+        if (rc == REDIO_OK) rc = redio_stream_sync(st->stream);
+        if (rc == REDIO_OK) return;
+        fprintf(stderr, "%s: %s\n", name, redio_strerror(rc));
+    }
+    float *o = (float *)out;
+    for (size_t i = 0; i < obytes / sizeof(float); ++i) o[i] = NAN;
+}
+
+extern "C" void kiss_fftr(kiss_fftr_cfg st, const kiss_fft_scalar *timedata, kiss_fft_cpx *freqdata)
+{
+    if (!st || !timedata || !freqdata) return;
+    kiss_fftr_run(st, 0, "kiss_fftr", timedata, freqdata);
+}
+
+extern "C" void kiss_fftri(kiss_fftr_cfg st, const kiss_fft_cpx *freqdata, kiss_fft_scalar *timedata)
+{
+    if (!st || !freqdata || !timedata) return;
+    kiss_fftr_run(st, 1, "kiss_fftri", freqdata, timedata);
+}
+
+extern "C" void kiss_fftr_free(kiss_fftr_cfg st)
+{
+    if (!st) return;
+    redio_fftr_destroy(st->plan);
+    redio_free(st->d_time);
+    redio_free(st->d_freq);
+    redio_stream_destroy(st->stream);
     if (st->on_heap) free(st);
 }

@@ -44,6 +44,14 @@ hipError_t launch_fft(const FftPlanDev &p, const float2 *in, float2 *out, long n
 // one launch over a list of count (1 ... REDIO_LIST_MAX) messages of nbatch[i] >= 1 consecutive transforms each; nfft 1024 only
 hipError_t launch_fft1k_list(const FftPlanDev &p, const float2 *const *in, float2 *const *out, const long *nbatch, int count, hipStream_t s);
 
+// fftr_kernels.hip: the real-input transform.  launch_fftr1k: 2048 real points per row fused into the one-wave 1024-point transform
+// (tw: the complex plan's table, stw: the M / 2 super twiddles; strides in elements of their own side).  launch_fftr_split: the
+// split pass of every other size, Z -> freq (forward) or freq -> T (inverse), strides in cf32
+hipError_t launch_fftr1k(bool inverse, const void *in, void *out, const float2 *tw, const float2 *stw, long nbatch, long in_stride,
+                         long out_stride, hipStream_t s);
+hipError_t launch_fftr_split(bool inverse, const float2 *src, long src_stride, float2 *dst, long dst_stride, const float2 *stw, int M, long nbatch,
+                             hipStream_t s);
+
 // overlap-save at nfft 1024 (one wave per block) and 4096: one kernel, no work buffers; at 4096 / 16384 tw_f / tw_i (4096) and
 // Tf / Ti (16384) are the plans' stage-ordered twiddle copies (redio_fft_twiddles_pass_dev)
 hipError_t launch_ovsave1k(const float2 *x, long hop, const float2 *tw_f, const float2 *tw_i, const float2 *Hc, float2 *out, long nblk,

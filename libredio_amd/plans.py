@@ -109,6 +109,61 @@ class Fft:
             self._h = None
 
 
+class Fftr:
+    """redio_fftr_*: batched kiss_fftr (rows of nfft float32 -> rows of nfft/2 + 1 complex64) or, with inverse=True, kiss_fftri (the
+    reverse, unnormalised).  nfft counts real points and is even."""
+
+    def __init__(self, nfft, inverse=False):
+        self.nfft, self.inverse = int(nfft), bool(inverse)
+        self.nbins = self.nfft // 2 + 1
+        self._h = C.c_void_p()
+        check(lib().redio_fftr_create(C.byref(self._h), self.nfft, int(self.inverse)), "fftr_create")
+
+    @property
+    def is_fused(self):
+        return bool(lib().redio_fftr_is_fused(self._h))
+
+    def reserve(self, nbatch):
+        check(lib().redio_fftr_reserve(self._h, nbatch), "fftr_reserve")
+
+    def _sides(self):
+        import torch
+        if self.inverse:
+            return torch.complex64, self.nbins, torch.float32, self.nfft
+        return torch.float32, self.nfft, torch.complex64, self.nbins
+
+    def __call__(self, x, out=None):
+        import torch
+        din, nin, dout, nout = self._sides()
+        assert x.dtype == din and x.numel() % nin == 0, "whole rows of the plan's input side"
+        nbatch = x.numel() // nin
+        if out is None:
+            out = torch.empty(nbatch * nout, dtype=dout, device=x.device)
+        assert out.dtype == dout and out.numel() >= nbatch * nout
+        check(lib().redio_fftr_enqueue(self._h, _dev_ptr(x), _dev_ptr(out), nbatch, current_stream()), "fftr_enqueue")
+        return out
+
+    def strided(self, x, nbatch, in_stride, out_stride=None, out=None):
+        """redio_fftr_enqueue_strided: row b is x[b*in_stride : b*in_stride + row] (a forward in_stride < nfft gives overlapping
+        frames) and lands at out[b*out_stride : ...]; strides count elements of their own side, out_stride defaults to packed rows."""
+        import torch
+        din, nin, dout, nout = self._sides()
+        if out_stride is None:
+            out_stride = nout
+        assert x.dtype == din and in_stride > 0 and (nbatch == 0 or (nbatch - 1) * in_stride + nin <= x.numel())
+        if out is None:
+            out = torch.empty(max(nbatch - 1, 0) * out_stride + (nout if nbatch else 0), dtype=dout, device=x.device)
+        assert out.dtype == dout and (nbatch == 0 or (nbatch - 1) * out_stride + nout <= out.numel())
+        check(lib().redio_fftr_enqueue_strided(self._h, _dev_ptr(x), _dev_ptr(out), nbatch, in_stride, out_stride, current_stream()),
+              "fftr_enqueue_strided")
+        return out
+
+    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
+        if getattr(self, "_h", None):
+            _safe_destroy("redio_fftr_destroy", self._h)
+            self._h = None
+
+
 class Chain:
     """redio_chain_*: FIR(ntaps, decimate) -> nfft-point forward FFT over consecutive blocks."""
 

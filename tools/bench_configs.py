@@ -1,5 +1,5 @@
 """Throughput of the non-headline configs of BASELINE.json on one MI355X (own measurements; bench.py
-stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft]..."""
+stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr]..."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, libredio_amd as R
@@ -51,6 +51,30 @@ if "fft" in which:
         out = torch.empty_like(x)
         ms = timeit(lambda: plan(x, out=out), n=20 if nfft < 16384 else 5, warm=3)
         print(f"FFT {nfft}: {ms:.3f} ms  {x.numel()/ms/1e6:.1f} GS/s  {16*x.numel()/ms/1e6:.0f} GB/s algorithmic ({16*x.numel()/ms/1e6/8000:.1%})")
+if "fftr" in which:
+    # the real-input transform of 2^28 real samples against what such a stream costs today: the complex transform of the same size on
+    # 2^28 cf32 samples (the widening pass f32 -> cf32 that route also needs is NOT counted: a head start for the old route).  The two
+    # are timed alternately, twice each, in this one process; the smaller time of each is printed.
+    xr_all = R.synth_f32(3, 0, n)
+    xc_all = R.synth_iq(2, 0, n)
+    for nfft in (2048, 512, 128, 4096, 1000, 131072):
+        rows = n // nfft
+        xr, xc = xr_all[: rows * nfft], xc_all[: rows * nfft]
+        real, cplx = R.Fftr(nfft), R.Fft(nfft)
+        real.reserve(rows)
+        outr = torch.empty(rows * (nfft // 2 + 1), dtype=torch.complex64, device="cuda")
+        outc = torch.empty_like(xc)
+        reps = 20 if nfft < 16384 else 5
+        ms_r = ms_c = 1e30
+        for _ in range(2):
+            ms_r = min(ms_r, timeit(lambda: real(xr, out=outr), n=reps, warm=3))
+            ms_c = min(ms_c, timeit(lambda: cplx(xc, out=outc), n=reps, warm=3))
+        b = 4 + 8 * (nfft // 2 + 1) / nfft  # algorithmic bytes per real sample: the row read once, the M + 1 bins written once
+        ns = rows * nfft
+        print(f"FFTR {nfft} ({'fused' if real.is_fused else 'generic'}): {ms_r:.3f} ms  {ns/ms_r/1e6:.1f} real GS/s  {b*ns/ms_r/1e6:.0f} GB/s algorithmic "
+              f"({b*ns/ms_r/1e6/8000:.1%} of 8 TB/s) | complex FFT {nfft} on as many cf32 samples: {ms_c:.3f} ms  {ns/ms_c/1e6:.1f} GS/s | "
+              f"time per sample real / complex = {ms_r/ms_c:.3f}")
+        del real, cplx, outr, outc
 if "fftall" in which:
     for nfft in (6, 9, 10, 12, 15, 20, 24, 25, 27, 30, 40, 45, 48, 60, 75, 80, 81, 90, 96, 100, 120, 125, 150, 160, 180, 192, 200, 225, 240, 243, 250, 300, 320, 360, 384, 400, 450, 480, 500, 600, 625, 640, 720, 729, 768, 800, 900, 960, 1000, 1200, 1280, 1440, 1536, 1600, 1800, 1920, 2000, 2187, 2400, 2560, 3072, 3125, 3200, 3600, 3840, 4000, 4800, 5120, 6144, 6400, 6561, 7680, 8000):
         x = R.synth_iq(2, 0, n)[: n // nfft * nfft]
