@@ -881,19 +881,18 @@ inline void overlap_save(Receiver<View<std::complex<float>>> u, Sender<View<std:
 // output unit sends nothing.  The seam is staged by work on the block's own stream, inside the input's Reading scope, so the
 // input buffer may be recycled as soon as that scope's `done` event has passed.
 namespace detail {
-template <typename NOut, typename Enqueue>
-void run_stream_block(Receiver<View<std::complex<float>>> &u, Sender<View<std::complex<float>>> &v, NOut nout, Enqueue enqueue)
+template <typename TI, typename TO, typename NOut, typename Enqueue>
+void run_stream_block_of(Receiver<View<TI>> &u, Sender<View<TO>> &v, NOut nout, Enqueue enqueue)
 {
-    using cf = std::complex<float>;
     BlockStream st;
     Ring ring;
     for (;;) {
         auto d = u.recv();
         const size_t n = nout(d.len);
-        auto o = n ? ring.acquire<cf>(n, st) : View<cf>();
+        auto o = n ? ring.acquire<TO>(n, st) : View<TO>();
         size_t got = 0;
         {
-            Reading<cf> in(d, st);
+            Reading<TI> in(d, st);
             check(enqueue(d, n ? o.data() : nullptr, &got, (void *)st));
         }
         if (n) {
@@ -901,6 +900,11 @@ void run_stream_block(Receiver<View<std::complex<float>>> &u, Sender<View<std::c
             v.send_unwrap(std::move(o));
         }
     }
+}
+template <typename NOut, typename Enqueue>
+void run_stream_block(Receiver<View<std::complex<float>>> &u, Sender<View<std::complex<float>>> &v, NOut nout, Enqueue enqueue)
+{
+    run_stream_block_of<std::complex<float>, std::complex<float>>(u, v, nout, enqueue);
 }
 } // namespace detail
 
@@ -956,6 +960,30 @@ inline void overlap_save_stream(Receiver<View<std::complex<float>>> u, Sender<Vi
     check(rc);
     detail::run_stream_block(u, v, [&](size_t len) { return redio_ovsave_stream_nout(s, len); },
                              [&](const View<cf> &d, cf *o, size_t *got, void *st) { return redio_ovsave_stream_enqueue(s, d.data(), d.len, o, got, st); });
+}
+
+// overlap-save on a REAL stream (redio_ovsave_real_*: kiss_fftr / kiss_fftri blocks of nfft samples; an even tap count counts as one
+// more), dsputils::convolve's valid-mode semantics per message
+inline void overlap_save_real(Receiver<View<float>> u, Sender<View<float>> v, std::vector<float> taps, int nfft)
+{
+    redio_ovsave_real *h = nullptr;
+    check(redio_ovsave_real_create(&h, taps.data(), taps.size(), nfft));
+    struct G { redio_ovsave_real *h; ~G() { redio_ovsave_real_destroy(h); } } g{h};
+    detail::run_block<float, float>(u, v, [&](const View<float> &d) { return redio_ovsave_real_nout(h, d.len); },
+                                    [&](const View<float> &d, const View<float> &o, void *st) { return redio_ovsave_real_enqueue(h, d.data(), d.len, o.data(), st); });
+}
+
+// the same as a STREAM: messages of any length, odd ones included, give the outputs of one call on the whole stream
+inline void overlap_save_real_stream(Receiver<View<float>> u, Sender<View<float>> v, std::vector<float> taps, int nfft)
+{
+    redio_ovsave_real *h = nullptr;
+    check(redio_ovsave_real_create(&h, taps.data(), taps.size(), nfft));
+    redio_ovsave_real_stream *s = nullptr;
+    const int rc = redio_ovsave_real_stream_create(&s, h);
+    struct G { redio_ovsave_real *h; redio_ovsave_real_stream *s; ~G() { redio_ovsave_real_stream_destroy(s); redio_ovsave_real_destroy(h); } } g{h, s};
+    check(rc);
+    detail::run_stream_block_of<float, float>(u, v, [&](size_t len) { return redio_ovsave_real_stream_nout(s, len); },
+                                              [&](const View<float> &d, float *o, size_t *got, void *st) { return redio_ovsave_real_stream_enqueue(s, d.data(), d.len, o, got, st); });
 }
 
 } // namespace dev

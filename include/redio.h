@@ -284,6 +284,29 @@ int redio_ovsave_destroy(redio_ovsave *h);
 size_t redio_ovsave_nout(const redio_ovsave *h, size_t n_in);
 int redio_ovsave_enqueue(redio_ovsave *h, const void *d_in, size_t n_in, void *d_out, void *stream);
 
+/* ---- overlap-save on REAL streams: the same valid-mode correlation (dsputils::convolve is real-only, dsputils.rs:30-32) on f32
+ * samples with real taps, through the real-input transforms above (kiss_fftr / kiss_fftri), N = nfft real points per block:
+ *     Ke = ntaps | 1 (an even tap count is treated as if one zero tap followed it), hop = N - Ke + 1 -- always even, so every block
+ *     starts on an 8-byte boundary;  Hc = conj(kiss_fftr(taps zero-padded to N));
+ *     out[b*hop + i] = kiss_fftri(kiss_fftr(x[b*hop .. b*hop + N)) .* Hc)[i] * (1.0f / N), i < hop
+ * (product: Y.r = X.r*Hc.r - X.i*Hc.i, Y.i = X.r*Hc.i + X.i*Hc.r, every operation rounded on its own).  Only whole blocks are produced:
+ * nout = ((n_in - N)/hop + 1) * hop, 0 when n_in < N.  It moves 4*N/hop + 4 bytes per output sample, half of what redio_ovsave_* moves
+ * for the same stream widened to cf32.  Within 2e-6 * sum|taps| * sqrt(log2 N) + 1e-7 of the direct fold.
+ * create: taps NULL, ntaps == 0, odd nfft, nfft < 2 or Ke > nfft -> REDIO_ERR_ARG (so ntaps == nfft is refused: nfft - 1
+ *   taps at most); nfft > 2^25 -> REDIO_ERR_UNSUPPORTED (redio_fftr_create's ceiling).
+ * N = 2048 is ONE kernel without scratch (redio_ovsave_real_is_fused() == 1).  Every other size runs the two transforms, a product
+ *   pass and a scaled copy through plan-owned scratch, in chunks of blocks: redio_ovsave_real_reserve(h, n_in) sizes it, after which an
+ *   enqueue of up to n_in samples neither allocates nor synchronises; un-reserved it grows on first use (REDIO_ERR_NOT_RESERVED while
+ *   the stream is being captured).
+ * enqueue: n_in < nfft -> REDIO_OK, no launch; NULL, overlapping or not 8-byte aligned d_in / d_out -> REDIO_ERR_ARG. */
+typedef struct redio_ovsave_real redio_ovsave_real;
+int redio_ovsave_real_create(redio_ovsave_real **h, const float *taps_host, size_t ntaps, int nfft);
+int redio_ovsave_real_destroy(redio_ovsave_real *h);
+size_t redio_ovsave_real_nout(const redio_ovsave_real *h, size_t n_in);
+int redio_ovsave_real_is_fused(const redio_ovsave_real *h);
+int redio_ovsave_real_reserve(redio_ovsave_real *h, size_t n_in);
+int redio_ovsave_real_enqueue(redio_ovsave_real *h, const void *d_in_f32, size_t n_in, void *d_out_f32, void *stream);
+
 /* ---- C4: M-channel polyphase channelizer (BASELINE.json configs[3]; a new composition) ----
  * Prototype of nchan*taps_per_branch taps; branch m filters rows x_t[m] = x[nchan*t + m] with
  * g_m[p] = proto[nchan*p + m] using the fold of dsputils::convolve (dsputils.rs:31), then every row
@@ -352,7 +375,8 @@ int redio_pfb_exchange_all(redio_comm *const *comms, int ndev, const void *const
  *     fir:    y[i] = fold_j x[decim*i + j]*taps[j] for every i whose window has arrived (decimation phase 0 at stream start)
  *     chain:  spectrum b from decimated samples [b*nfft, (b+1)*nfft) of that y
  *     pfb:    row t from input rows t .. t+taps_per_branch-1 (layout [row][nchan] only)
- *     ovsave: block b -> hop outputs, blocks every hop samples from the stream start
+ *     ovsave: block b -> hop outputs, blocks every hop samples from the stream start (ovsave_real: the same on f32 samples; d_new
+ *             needs 4-byte alignment only -- messages may have any length, odd ones included -- and d_out 8-byte alignment)
  * enqueue() writes *nout (= redio_*_stream_nout(h, n_new), known before the call) output samples to d_out; the new
  * samples are read in place (only a seam of fewer than one window is staged through a plan-owned buffer).  It only
  * launches kernels and small device copies -- with one exception: a plan shape that runs as two kernels (redio_chain_is_fused() == 0,
@@ -394,6 +418,13 @@ int redio_ovsave_stream_reset(redio_ovsave_stream *h);
 size_t redio_ovsave_stream_nout(const redio_ovsave_stream *h, size_t n_new);
 size_t redio_ovsave_stream_pending(const redio_ovsave_stream *h);
 int redio_ovsave_stream_enqueue(redio_ovsave_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
+typedef struct redio_ovsave_real_stream redio_ovsave_real_stream;
+int redio_ovsave_real_stream_create(redio_ovsave_real_stream **h, redio_ovsave_real *plan);
+int redio_ovsave_real_stream_destroy(redio_ovsave_real_stream *h);
+int redio_ovsave_real_stream_reset(redio_ovsave_real_stream *h);
+size_t redio_ovsave_real_stream_nout(const redio_ovsave_real_stream *h, size_t n_new);
+size_t redio_ovsave_real_stream_pending(const redio_ovsave_real_stream *h);
+int redio_ovsave_real_stream_enqueue(redio_ovsave_real_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
 
 /* ---- A6: samplerate::resample's native side, src/samplerate/src/samplerate.rs:59-87 ----
  * nchan independent mono streams that share ratio and block lengths (the reference creates one

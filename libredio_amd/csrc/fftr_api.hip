@@ -69,6 +69,9 @@ extern "C" int redio_fftr_destroy(redio_fftr *h)
     return REDIO_OK;
 }
 
+const float2 *redio_fftr_twiddles_dev(const redio_fftr *h) { return h->cplx ? redio_fft_twiddles_dev(h->cplx) : nullptr; }
+const float2 *redio_fftr_super_dev(const redio_fftr *h) { return h->d_stw; }
+
 extern "C" int redio_fftr_is_fused(const redio_fftr *h) { return h && h->fused ? 1 : 0; }
 
 extern "C" int redio_fftr_reserve(redio_fftr *h, size_t nbatch)

@@ -132,6 +132,30 @@ RD_HD void fftr1k_post_lane(const float2 (&v)[16], ExPtr ex, const Fftr1kTw &w, 
     }
 }
 
+// the same split with its results kept in registers, in the layout fftr1k_load_row() produces: a[t] = freq[k], b[t] = freq[1024 - k]
+// (k = lane + 64 t), mid = freq[512] (lane 0; the other lanes never use theirs).  For a consumer that goes on to the inverse split in
+// the same wave (ovsave_real_kernels.hip).
+template <typename ExPtr>
+RD_HD void fftr1k_post_lane_regs(const float2 (&v)[16], ExPtr ex, const Fftr1kTw &w, int lane, float2 (&a)[8], float2 (&b)[8], float2 &mid)
+{
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const float2 zk = v[fftr1k_reg(t)];
+        if (t == 0 && lane == 0) {
+            fftr_fwd_ends(zk, a[0], b[0]);
+        } else {
+            const float2 zm = ex[fftr1k_partner(lane, t)];
+            fftr_fwd_pair(zk, zm, w.s[t], a[t], b[t]);
+        }
+    }
+    mid = make_float2(0.f, 0.f);
+    if (lane == 0) {
+        float2 lo;
+        const float2 z = v[fftr1k_reg(8)];
+        fftr_fwd_pair(z, z, w.mid, lo, mid);
+    }
+}
+
 // the inverse's loads of one row by lane `lane`: a[t] = freq[k], b[t] = freq[1024 - k] (k = lane + 64 t), mid = freq[512]
 template <typename FPtr>
 RD_HD void fftr1k_load_row(FPtr f, int lane, float2 (&a)[8], float2 (&b)[8], float2 &mid)

@@ -52,6 +52,16 @@ hipError_t launch_fftr1k(bool inverse, const void *in, void *out, const float2 *
 hipError_t launch_fftr_split(bool inverse, const float2 *src, long src_stride, float2 *dst, long dst_stride, const float2 *stw, int M, long nbatch,
                              hipStream_t s);
 
+// ovsave_real_kernels.hip: overlap-save on real streams.  launch_ovsave_real2k: 2048-sample blocks, one kernel (tw_*: the 1024-point
+// complex tables, stw_*: the super twiddles of the forward / inverse real plans, Hc: 1025 bins; x 4-byte, out 8-byte aligned, hop even).
+// The others are the product, conjugate, scaled-copy and row-gather passes of the generic path (ovsave_real_api.hip).
+hipError_t launch_ovsave_real2k(const float *x, long hop, const float2 *tw_f, const float2 *tw_i, const float2 *stw_f, const float2 *stw_i,
+                                const float2 *Hc, float *out, long nblk, float scale, hipStream_t s);
+hipError_t launch_ovsave_real_mul(float2 *S, const float2 *Hc, long nblk, int nbins, hipStream_t s);
+hipError_t launch_ovsave_real_conj(float2 *H, int nbins, hipStream_t s);
+hipError_t launch_ovsave_real_scale_out(const float *y, float *out, long nblk, long nfft, long hop, float scale, hipStream_t s);
+hipError_t launch_ovsave_real_rows(const float *x, float *rows, long nblk, long nfft, long hop, hipStream_t s);
+
 // overlap-save at nfft 1024 (one wave per block) and 4096: one kernel, no work buffers; at 4096 / 16384 tw_f / tw_i (4096) and
 // Tf / Ti (16384) are the plans' stage-ordered twiddle copies (redio_fft_twiddles_pass_dev)
 hipError_t launch_ovsave1k(const float2 *x, long hop, const float2 *tw_f, const float2 *tw_i, const float2 *Hc, float2 *out, long nblk,
@@ -109,14 +119,22 @@ inline int num_cus()
 } // namespace redio
 
 // plan shapes for the carried-history layer (stream_carry.hip); defined next to each plan struct
-struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave;
+struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real;
 void redio_fir_shape(const redio_fir *h, size_t *ntaps, size_t *decim, unsigned *flags, int *device);
 void redio_chain_shape(const redio_chain *h, size_t *ntaps, size_t *decim, int *nfft, int *device);
 void redio_pfb_shape(const redio_pfb *h, int *nchan, int *taps_per_branch, int *device);
 void redio_ovsave_shape(const redio_ovsave *h, int *nfft, size_t *hop, int *device);
+void redio_ovsave_real_shape(const redio_ovsave_real *h, int *nfft, size_t *hop, int *device);
+// redio_ovsave_real_enqueue for the carried-history layer: d_in may be only 4-byte aligned (a message that started on an odd sample)
+int redio_ovsave_real_enqueue_any(redio_ovsave_real *h, const void *d_in, size_t n_in, void *d_out, void *stream);
 
 // redio_api.hip: the device twiddle table behind a public FFT handle (library-internal)
 struct redio_fft;
 const redio::FftPlanDev *redio_fft_plan_dev(const redio_fft *h);
 const float2 *redio_fft_twiddles_dev(const redio_fft *h);
 const float2 *redio_fft_twiddles_pass_dev(const redio_fft *h); // the pass-ordered copy (multi-pass sizes), else null
+
+// fftr_api.hip: the tables behind a real-input plan (library-internal): the complex plan's twiddles (size nfft / 2) and the super twiddles
+struct redio_fftr;
+const float2 *redio_fftr_twiddles_dev(const redio_fftr *h);
+const float2 *redio_fftr_super_dev(const redio_fftr *h);

@@ -7,7 +7,7 @@
 //     FIR          W = ntaps                       H = decim          unit = 1 output sample
 //     chain        W = (nfft-1)*decim + ntaps      H = nfft*decim     unit = 1 spectrum (nfft samples)
 //     channelizer  W = nchan*taps_per_branch       H = nchan          unit = 1 row (nchan samples)
-//     overlap-save W = nfft                        H = hop            unit = hop output samples
+//     overlap-save W = nfft                        H = hop            unit = hop output samples (cf32, or f32 for the real operator)
 // so one layer serves them all.  The handle keeps the stream's unconsumed tail (fewer than W samples) on the device.
 // A call with n new samples
 //   1. appends the first min(n, W-1) new samples to the tail in a plan-owned staging buffer (one small copy),
@@ -55,7 +55,7 @@ hipError_t seam_copy(void *dst, const void *src, size_t bytes, hipStream_t st)
     SEAM_GO(uint8_t)
 #undef SEAM_GO
 }
-enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8 }; // _U8: the samples are interleaved u8 I/Q byte pairs
+enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL }; // _U8: the samples are interleaved u8 I/Q byte pairs
 struct Carry {
     int device = 0;
     Kind kind = K_FIR;
@@ -91,6 +91,7 @@ int run(const Carry &c, const void *d_in, size_t n_in, void *d_out, void *stream
     case K_OVSAVE: return redio_ovsave_enqueue((redio_ovsave *)c.plan, d_in, n_in, d_out, stream);
     case K_CHAIN_U8: return redio_chain_enqueue_u8((redio_chain *)c.plan, d_in, 2 * n_in, d_out, stream);
     case K_PFB_U8: return redio_pfb_enqueue_u8((redio_pfb *)c.plan, d_in, 2 * n_in, d_out, 1, stream);
+    case K_OVSAVE_REAL: return redio_ovsave_real_enqueue_any((redio_ovsave_real *)c.plan, d_in, n_in, d_out, stream); // a unit may start on an odd sample
     }
     return REDIO_ERR_ARG;
 }
@@ -211,6 +212,7 @@ struct redio_fir_stream { Carry *c; };
 struct redio_chain_stream { Carry *c; };
 struct redio_pfb_stream { Carry *c; };
 struct redio_ovsave_stream { Carry *c; };
+struct redio_ovsave_real_stream { Carry *c; };
 
 #define RD_STREAM_API(NAME)                                                                                                     \
     extern "C" int redio_##NAME##_stream_destroy(redio_##NAME##_stream *h)                                                      \
@@ -236,6 +238,7 @@ RD_STREAM_API(fir)
 RD_STREAM_API(chain)
 RD_STREAM_API(pfb)
 RD_STREAM_API(ovsave)
+RD_STREAM_API(ovsave_real)
 
 template <typename Hd>
 static int make(Hd **h, Kind kind, void *plan, int dev, size_t W, size_t H, size_t in_elem, size_t unit_out, size_t out_elem)
@@ -315,4 +318,17 @@ extern "C" int redio_ovsave_stream_create(redio_ovsave_stream **h, redio_ovsave 
     int nfft, dev; size_t hop;
     redio_ovsave_shape(plan, &nfft, &hop, &dev);
     return make(h, K_OVSAVE, plan, dev, (size_t)nfft, hop, 8, hop, 8);
+}
+extern "C" int redio_ovsave_real_stream_create(redio_ovsave_real_stream **h, redio_ovsave_real *plan)
+{
+    if (!h) return REDIO_ERR_ARG;
+    *h = nullptr;
+    if (!plan) return REDIO_ERR_ARG;
+    int nfft, dev; size_t hop;
+    redio_ovsave_real_shape(plan, &nfft, &hop, &dev);
+    // the generic path's scratch, sized here for the seam windows (at most 2*W samples per head run); a longer body run grows it at
+    // enqueue time unless redio_ovsave_real_reserve(plan, largest message + nfft) came first
+    const int rr = redio_ovsave_real_reserve(plan, 2 * (size_t)nfft);
+    if (rr) return rr;
+    return make(h, K_OVSAVE_REAL, plan, dev, (size_t)nfft, hop, 4, hop, 4);
 }

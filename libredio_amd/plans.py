@@ -258,14 +258,14 @@ class Chain:
 
 
 class Stream:
-    """redio_{fir,chain,pfb,ovsave}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
+    """redio_{fir,chain,pfb,ovsave,ovsave_real}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
     segmentation of the input gives the bits of one stateless call on the whole stream (the stateless plans keep the
-    reference's per-message semantics, dsputils.rs:30-32).  `plan` is a Fir, Chain, Channelizer or OverlapSave."""
+    reference's per-message semantics, dsputils.rs:30-32).  `plan` is a Fir, Chain, Channelizer, OverlapSave or OverlapSaveReal."""
 
     def __init__(self, plan, u8=False):
         """u8=True (Chain and Channelizer): the stream arrives as the receiver's interleaved u8 I/Q bytes (uint8 tensors, two
         bytes per sample; redio_{chain,pfb}_stream_create_u8)."""
-        kind = {Fir: "fir", Chain: "chain"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave"}[type(plan).__name__]
+        kind = {Fir: "fir", Chain: "chain"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real"}[type(plan).__name__]
         assert not u8 or kind in ("chain", "pfb")
         self._kind, self._plan, self._u8 = kind, plan, bool(u8)          # the plan must outlive the stream handle
         self._h = C.c_void_p()
@@ -288,7 +288,7 @@ class Stream:
         """Feed the next piece of the stream; returns the output samples that became computable (flat tensor; the
         chain's are whole spectra of nfft samples, the channelizer's whole rows of nchan samples)."""
         import torch
-        real = self._kind == "fir" and not self._plan.complex_input
+        real = self._kind == "ovsave_real" or (self._kind == "fir" and not self._plan.complex_input)
         want = torch.float32 if real else torch.complex64
         if self._u8:
             assert x.dtype == torch.uint8 and x.numel() % 2 == 0, "expected an even number of uint8 bytes"
@@ -655,4 +655,42 @@ class OverlapSave:
     def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
         if getattr(self, "_h", None):
             _safe_destroy("redio_ovsave_destroy", self._h)
+            self._h = None
+
+
+class OverlapSaveReal:
+    """redio_ovsave_real_*: overlap-save FFT convolution of a REAL (float32) stream with real taps through kiss_fftr / kiss_fftri, the
+    semantics of dsputils::convolve (valid-mode correlation, dsputils.rs:30-32).  An even tap count counts as one more (a zero tap
+    behind it): hop = nfft - (ntaps | 1) + 1 is always even.  nfft = 2048 is one kernel (is_fused)."""
+
+    def __init__(self, taps, nfft=2048):
+        t, p = _taps(taps)
+        self.ntaps, self.nfft = len(t), int(nfft)
+        self.hop = self.nfft - (self.ntaps | 1) + 1
+        self._h = C.c_void_p()
+        check(lib().redio_ovsave_real_create(C.byref(self._h), p, len(t), self.nfft), "ovsave_real_create")
+
+    def nout(self, n_in):
+        return lib().redio_ovsave_real_nout(self._h, n_in)
+
+    @property
+    def is_fused(self):
+        return bool(lib().redio_ovsave_real_is_fused(self._h))
+
+    def reserve(self, n_in):
+        check(lib().redio_ovsave_real_reserve(self._h, n_in), "ovsave_real_reserve")
+
+    def __call__(self, x, out=None):
+        import torch
+        assert x.dtype == torch.float32
+        n = self.nout(x.numel())
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=x.device)
+        assert out.dtype == torch.float32 and out.numel() >= n
+        check(lib().redio_ovsave_real_enqueue(self._h, _dev_ptr(x), x.numel(), _dev_ptr(out), current_stream()), "ovsave_real_enqueue")
+        return out[:n]
+
+    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
+        if getattr(self, "_h", None):
+            _safe_destroy("redio_ovsave_real_destroy", self._h)
             self._h = None

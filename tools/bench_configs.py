@@ -1,5 +1,5 @@
 """Throughput of the non-headline configs of BASELINE.json on one MI355X (own measurements; bench.py
-stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr]..."""
+stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal]..."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, libredio_amd as R
@@ -75,6 +75,38 @@ if "fftr" in which:
               f"({b*ns/ms_r/1e6/8000:.1%} of 8 TB/s) | complex FFT {nfft} on as many cf32 samples: {ms_c:.3f} ms  {ns/ms_c/1e6:.1f} GS/s | "
               f"time per sample real / complex = {ms_r/ms_c:.3f}")
         del real, cplx, outr, outc
+if "ovsavereal" in which:
+    # overlap-save on 2^28 real samples against what such a stream costs today, timed alternately (twice each; the smaller time is
+    # printed) in this one process: (a) redio_ovsave on 2^28 cf32 samples -- a widened real stream, its widening pass NOT counted -- and
+    # (b) the direct f32 FIR with the same taps.  Then the generic path at two larger block sizes.
+    xr = R.synth_f32(3, 0, n)
+    xc = R.synth_iq(2, 0, n)
+    for nfft, k in ((2048, 127), (4096, 1025), (65536, 8193)):
+        taps = R.dsputils.lpf_corrected(k, 0.02)
+        real = R.OverlapSaveReal(taps, nfft)
+        real.reserve(n)
+        outr = torch.empty(real.nout(n), dtype=torch.float32, device="cuda")
+        reps = 10 if real.is_fused else 3
+        b = 4 * nfft / real.hop + 4  # algorithmic bytes per output sample
+        if not real.is_fused:
+            ms_r = min(timeit(lambda: real(xr, out=outr), n=reps, warm=2) for _ in range(2))
+            print(f"OVSAVE-REAL {nfft}/{k} (generic): {ms_r:.3f} ms  {n/ms_r/1e6:.1f} real GS/s  {b*outr.numel()/ms_r/1e6:.0f} GB/s algorithmic "
+                  f"({b*outr.numel()/ms_r/1e6/8000:.1%} of 8 TB/s)")
+            del real, outr
+            continue
+        cplx, fir = R.OverlapSave(taps, nfft), R.Fir(taps, 1, complex_input=False, fused=True)
+        outc = torch.empty(cplx.nout(n), dtype=torch.complex64, device="cuda")
+        outf = torch.empty(fir.nout(n), dtype=torch.float32, device="cuda")
+        ms_r = ms_c = ms_f = 1e30
+        for _ in range(2):
+            ms_r = min(ms_r, timeit(lambda: real(xr, out=outr), n=reps, warm=3))
+            ms_c = min(ms_c, timeit(lambda: cplx(xc, out=outc), n=reps, warm=3))
+            ms_f = min(ms_f, timeit(lambda: fir(xr, out=outf), n=reps, warm=3))
+        print(f"OVSAVE-REAL {nfft}/{k} (fused): {ms_r:.3f} ms  {n/ms_r/1e6:.1f} real GS/s  {b*outr.numel()/ms_r/1e6:.0f} GB/s algorithmic "
+              f"({b*outr.numel()/ms_r/1e6/8000:.1%} of 8 TB/s) | (a) complex overlap-save {nfft}/{k} on as many cf32 samples: {ms_c:.3f} ms  "
+              f"{n/ms_c/1e6:.1f} GS/s | (b) direct f32 FIR {k} taps /1: {ms_f:.3f} ms  {n/ms_f/1e6:.1f} GS/s | "
+              f"time per sample real / complex = {ms_r/ms_c:.3f}")
+        del real, cplx, fir, outr, outc, outf
 if "fftall" in which:
     for nfft in (6, 9, 10, 12, 15, 20, 24, 25, 27, 30, 40, 45, 48, 60, 75, 80, 81, 90, 96, 100, 120, 125, 150, 160, 180, 192, 200, 225, 240, 243, 250, 300, 320, 360, 384, 400, 450, 480, 500, 600, 625, 640, 720, 729, 768, 800, 900, 960, 1000, 1200, 1280, 1440, 1536, 1600, 1800, 1920, 2000, 2187, 2400, 2560, 3072, 3125, 3200, 3600, 3840, 4000, 4800, 5120, 6144, 6400, 6561, 7680, 8000):
         x = R.synth_iq(2, 0, n)[: n // nfft * nfft]
