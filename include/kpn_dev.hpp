@@ -986,5 +986,32 @@ inline void overlap_save_real_stream(Receiver<View<float>> u, Sender<View<float>
                                               [&](const View<float> &d, float *o, size_t *got, void *st) { return redio_ovsave_real_stream_enqueue(s, d.data(), d.len, o, got, st); });
 }
 
+// the integrated power spectrum (redio_pspec_*: |X|^2 of nfft-point kissfft::fft blocks that start every `step` samples, summed over
+// `integrate` transforms; window: empty or nfft values): cf32 messages in, rows of nfft f32 out, per-message semantics -- the rows
+// that fit in each message, a trailing partial row dropped
+inline void power_spectrum(Receiver<View<std::complex<float>>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {})
+{
+    using cf = std::complex<float>;
+    redio_pspec *h = nullptr;
+    check(redio_pspec_create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
+    struct G { redio_pspec *h; ~G() { redio_pspec_destroy(h); } } g{h};
+    detail::run_block<cf, float>(u, v, [&](const View<cf> &d) { return redio_pspec_nrows(h, d.len) * (size_t)nfft; },
+                                 [&](const View<cf> &d, const View<float> &o, void *st) { return redio_pspec_enqueue(h, d.data(), d.len, o.data(), st); });
+}
+
+// the same as a STREAM: messages of any length give the rows of one call on the whole stream; a message that completes no row sends nothing
+inline void power_spectrum_stream(Receiver<View<std::complex<float>>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {})
+{
+    using cf = std::complex<float>;
+    redio_pspec *h = nullptr;
+    check(redio_pspec_create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
+    redio_pspec_stream *s = nullptr;
+    const int rc = redio_pspec_stream_create(&s, h);
+    struct G { redio_pspec *h; redio_pspec_stream *s; ~G() { redio_pspec_stream_destroy(s); redio_pspec_destroy(h); } } g{h, s};
+    check(rc);
+    detail::run_stream_block_of<cf, float>(u, v, [&](size_t len) { return redio_pspec_stream_nout(s, len); },
+                                           [&](const View<cf> &d, float *o, size_t *got, void *st) { return redio_pspec_stream_enqueue(s, d.data(), d.len, o, got, st); });
+}
+
 } // namespace dev
 } // namespace kpn

@@ -182,6 +182,41 @@ int redio_fftr_enqueue(redio_fftr *h, const void *d_in, void *d_out, size_t nbat
  * complex launch per row. */
 int redio_fftr_enqueue_strided(redio_fftr *h, const void *d_in, void *d_out, size_t nbatch, long in_stride, long out_stride, void *stream);
 
+/* ---- the integrated power spectrum: |X[k]|^2 of the kissfft::fft block (src/kissfft/src/kissfft.rs:18-31) summed over K transforms ----
+ * The transform is the reference's (kissfft.rs:18-31, the bits of redio_fft_*); the integration is NEW -- the reference has no
+ * such block -- and is a stated design.  What a spectrum display, a waterfall, a detector or a radiometer reads:
+ * the periodogram, or with a window and step < nfft Welch's method.  N = nfft, K = integrate, forward transforms only:
+ *     transform t of row r reads x[(r K + t) step ... + N), times window[n] when there is a window (NULL: no multiply at all);
+ *     p_t[k] = X[k].re * X[k].re + X[k].im * X[k].im;
+ *     segment s of a row holds t in [16 s, min(16 s + 16, K)) (REDIO_PSPEC_SEG): seg_s = ((p_first + p_next) + ...), a left fold in
+ *     ascending t;  out[r][k] = ((seg_0 + seg_1) + ...), a left fold in ascending s.  For K <= 16 that is the plain sequential sum.
+ * All f32, every multiply and add rounded on its own; the order does not depend on launch geometry.  With W = (K - 1) step + N and
+ * H = K step a call of n_in samples gives nrows = (n_in - W) / H + 1 rows (0 when n_in < W; a trailing partial row is dropped) of N
+ * f32 in natural bin order, packed.  No fftshift, no dB, no division by sum(w^2): those are the caller's.
+ * create: NULL h, nfft < 1, integrate == 0, step == 0 -> REDIO_ERR_ARG; a size redio_fft_create refuses -> its error.
+ * N = 1024 is ONE kernel in which the spectra never leave the wave's registers (redio_pspec_is_fused() == 1): 8 N / step bytes read
+ *   and 4 / K written per sample.  Every other size gathers (and windows) the rows, runs the plan's own redio_fft and an accumulate
+ *   pass through plan-owned scratch in chunks of at most 64 MiB.
+ * reserve(h, n_in) sizes the scratch for calls of up to n_in samples (and for redio_pspec_enqueue_spectra calls of as many rows),
+ *   after which an enqueue neither allocates nor synchronises; un-reserved it grows on first use (REDIO_ERR_NOT_RESERVED while the
+ *   stream is being captured).
+ * enqueue: launches only, on the caller's stream.  Fewer than W samples -> REDIO_OK, no launch; NULL or overlapping buffers, d_in
+ *   not 8-byte or d_out not 4-byte aligned -> REDIO_ERR_ARG.
+ * enqueue_spectra: the same integration over nbatch packed, already transformed rows of N bins (window and step do not apply):
+ *   nbatch / K rows come out.  This is how redio_chain_enqueue's spectra are integrated.
+ * set_split: 0 auto, 1 one wavefront (or thread group) per whole row, 2 one per segment and a fold pass over the partials.  For tests
+ *   and measurement, like redio_chain_set_unfused: the bits are the same in every mode. */
+#define REDIO_PSPEC_SEG 16
+typedef struct redio_pspec redio_pspec;
+int redio_pspec_create(redio_pspec **h, int nfft, size_t integrate, size_t step, const float *window_host /* NULL or nfft */);
+int redio_pspec_destroy(redio_pspec *h);
+size_t redio_pspec_nrows(const redio_pspec *h, size_t n_in);
+int redio_pspec_is_fused(const redio_pspec *h);
+int redio_pspec_reserve(redio_pspec *h, size_t n_in);
+int redio_pspec_enqueue(redio_pspec *h, const void *d_in_c32, size_t n_in, void *d_out_f32, void *stream);
+int redio_pspec_enqueue_spectra(redio_pspec *h, const void *d_spectra_c32, size_t nbatch, void *d_out_f32, void *stream);
+int redio_pspec_set_split(redio_pspec *h, int mode);
+
 /* ---- C2 chain: FIR (ntaps, decimate decim) -> nfft-point forward FFT of consecutive blocks ----
  * Fused single kernel for nfft = 1024 with (ntaps, decim) in {(127, 5), (127, 3), (127, 1), (63, 5), (63, 1)} on a
  * 16-byte aligned stream; other shapes run the FIR and FFT kernels back to back through a plan-owned
@@ -377,6 +412,9 @@ int redio_pfb_exchange_all(redio_comm *const *comms, int ndev, const void *const
  *     pfb:    row t from input rows t .. t+taps_per_branch-1 (layout [row][nchan] only)
  *     ovsave: block b -> hop outputs, blocks every hop samples from the stream start (ovsave_real: the same on f32 samples; d_new
  *             needs 4-byte alignment only -- messages may have any length, odd ones included -- and d_out 8-byte alignment)
+ *     pspec:  row r from the W = (integrate - 1) step + nfft samples that start at r * integrate * step; *nout counts f32 words
+ *             (whole rows of nfft).  The staging buffers hold fewer than W samples each side of a seam -- 8 MiB of history at
+ *             nfft = integrate = 1024 -- so a long integration costs that much device memory per stream handle.
  * enqueue() writes *nout (= redio_*_stream_nout(h, n_new), known before the call) output samples to d_out; the new
  * samples are read in place (only a seam of fewer than one window is staged through a plan-owned buffer).  It only
  * launches kernels and small device copies -- with one exception: a plan shape that runs as two kernels (redio_chain_is_fused() == 0,
@@ -425,6 +463,13 @@ int redio_ovsave_real_stream_reset(redio_ovsave_real_stream *h);
 size_t redio_ovsave_real_stream_nout(const redio_ovsave_real_stream *h, size_t n_new);
 size_t redio_ovsave_real_stream_pending(const redio_ovsave_real_stream *h);
 int redio_ovsave_real_stream_enqueue(redio_ovsave_real_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
+typedef struct redio_pspec_stream redio_pspec_stream;
+int redio_pspec_stream_create(redio_pspec_stream **h, redio_pspec *plan);
+int redio_pspec_stream_destroy(redio_pspec_stream *h);
+int redio_pspec_stream_reset(redio_pspec_stream *h);
+size_t redio_pspec_stream_nout(const redio_pspec_stream *h, size_t n_new);
+size_t redio_pspec_stream_pending(const redio_pspec_stream *h);
+int redio_pspec_stream_enqueue(redio_pspec_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
 
 /* ---- A6: samplerate::resample's native side, src/samplerate/src/samplerate.rs:59-87 ----
  * nchan independent mono streams that share ratio and block lengths (the reference creates one

@@ -62,6 +62,15 @@ hipError_t launch_ovsave_real_conj(float2 *H, int nbins, hipStream_t s);
 hipError_t launch_ovsave_real_scale_out(const float *y, float *out, long nblk, long nfft, long hop, float scale, hipStream_t s);
 hipError_t launch_ovsave_real_rows(const float *x, float *rows, long nblk, long nfft, long hop, hipStream_t s);
 
+// pspec_kernels.hip: the integrated power spectrum.  launch_pspec1k: 1024-point transforms, one wavefront per unit (a row of K
+// transforms, or with `split` one segment of at most 16); dst: 1024 f32 per unit; win: 1024 values or null; tw: the plan's forward table.
+// The others are the generic path's row gather, the accumulate pass over segments [q0, q0 + nseg) of the call (spec: the spectrum of
+// transform g_base; dst: N f32 per segment of the call) and the fold of S partials per row (pspec_api.hip).
+hipError_t launch_pspec1k(const float2 *x, long step, long K, const float *win, const float2 *tw, float *dst, long nunits, bool split, hipStream_t s);
+hipError_t launch_pspec_rows(const float2 *x, const float *win, float2 *rows, long ntr, long N, long step, hipStream_t s);
+hipError_t launch_pspec_accum(const float2 *spec, float *dst, long q0, long nseg, long N, long K, long g_base, hipStream_t s);
+hipError_t launch_pspec_fold(const float *part, float *out, long nrows, long N, long S, hipStream_t s);
+
 // overlap-save at nfft 1024 (one wave per block) and 4096: one kernel, no work buffers; at 4096 / 16384 tw_f / tw_i (4096) and
 // Tf / Ti (16384) are the plans' stage-ordered twiddle copies (redio_fft_twiddles_pass_dev)
 hipError_t launch_ovsave1k(const float2 *x, long hop, const float2 *tw_f, const float2 *tw_i, const float2 *Hc, float2 *out, long nblk,
@@ -119,12 +128,13 @@ inline int num_cus()
 } // namespace redio
 
 // plan shapes for the carried-history layer (stream_carry.hip); defined next to each plan struct
-struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real;
+struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real; struct redio_pspec;
 void redio_fir_shape(const redio_fir *h, size_t *ntaps, size_t *decim, unsigned *flags, int *device);
 void redio_chain_shape(const redio_chain *h, size_t *ntaps, size_t *decim, int *nfft, int *device);
 void redio_pfb_shape(const redio_pfb *h, int *nchan, int *taps_per_branch, int *device);
 void redio_ovsave_shape(const redio_ovsave *h, int *nfft, size_t *hop, int *device);
 void redio_ovsave_real_shape(const redio_ovsave_real *h, int *nfft, size_t *hop, int *device);
+void redio_pspec_shape(const redio_pspec *h, int *nfft, size_t *integrate, size_t *step, int *device);
 // redio_ovsave_real_enqueue for the carried-history layer: d_in may be only 4-byte aligned (a message that started on an odd sample)
 int redio_ovsave_real_enqueue_any(redio_ovsave_real *h, const void *d_in, size_t n_in, void *d_out, void *stream);
 

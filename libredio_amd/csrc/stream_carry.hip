@@ -8,6 +8,7 @@
 //     chain        W = (nfft-1)*decim + ntaps      H = nfft*decim     unit = 1 spectrum (nfft samples)
 //     channelizer  W = nchan*taps_per_branch       H = nchan          unit = 1 row (nchan samples)
 //     overlap-save W = nfft                        H = hop            unit = hop output samples (cf32, or f32 for the real operator)
+//     power spectrum W = (integrate-1)*step + nfft H = integrate*step unit = 1 row (nfft f32 from cf32 samples)
 // so one layer serves them all.  The handle keeps the stream's unconsumed tail (fewer than W samples) on the device.
 // A call with n new samples
 //   1. appends the first min(n, W-1) new samples to the tail in a plan-owned staging buffer (one small copy),
@@ -55,7 +56,7 @@ hipError_t seam_copy(void *dst, const void *src, size_t bytes, hipStream_t st)
     SEAM_GO(uint8_t)
 #undef SEAM_GO
 }
-enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL }; // _U8: the samples are interleaved u8 I/Q byte pairs
+enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC }; // _U8: the samples are interleaved u8 I/Q byte pairs
 struct Carry {
     int device = 0;
     Kind kind = K_FIR;
@@ -91,6 +92,7 @@ int run(const Carry &c, const void *d_in, size_t n_in, void *d_out, void *stream
     case K_OVSAVE: return redio_ovsave_enqueue((redio_ovsave *)c.plan, d_in, n_in, d_out, stream);
     case K_CHAIN_U8: return redio_chain_enqueue_u8((redio_chain *)c.plan, d_in, 2 * n_in, d_out, stream);
     case K_PFB_U8: return redio_pfb_enqueue_u8((redio_pfb *)c.plan, d_in, 2 * n_in, d_out, 1, stream);
+    case K_PSPEC: return redio_pspec_enqueue((redio_pspec *)c.plan, d_in, n_in, d_out, stream);
     case K_OVSAVE_REAL: return redio_ovsave_real_enqueue_any((redio_ovsave_real *)c.plan, d_in, n_in, d_out, stream); // a unit may start on an odd sample
     }
     return REDIO_ERR_ARG;
@@ -213,6 +215,7 @@ struct redio_chain_stream { Carry *c; };
 struct redio_pfb_stream { Carry *c; };
 struct redio_ovsave_stream { Carry *c; };
 struct redio_ovsave_real_stream { Carry *c; };
+struct redio_pspec_stream { Carry *c; };
 
 #define RD_STREAM_API(NAME)                                                                                                     \
     extern "C" int redio_##NAME##_stream_destroy(redio_##NAME##_stream *h)                                                      \
@@ -239,6 +242,7 @@ RD_STREAM_API(chain)
 RD_STREAM_API(pfb)
 RD_STREAM_API(ovsave)
 RD_STREAM_API(ovsave_real)
+RD_STREAM_API(pspec)
 
 template <typename Hd>
 static int make(Hd **h, Kind kind, void *plan, int dev, size_t W, size_t H, size_t in_elem, size_t unit_out, size_t out_elem)
@@ -331,4 +335,18 @@ extern "C" int redio_ovsave_real_stream_create(redio_ovsave_real_stream **h, red
     const int rr = redio_ovsave_real_reserve(plan, 2 * (size_t)nfft);
     if (rr) return rr;
     return make(h, K_OVSAVE_REAL, plan, dev, (size_t)nfft, hop, 4, hop, 4);
+}
+extern "C" int redio_pspec_stream_create(redio_pspec_stream **h, redio_pspec *plan)
+{
+    if (!h) return REDIO_ERR_ARG;
+    *h = nullptr;
+    if (!plan) return REDIO_ERR_ARG;
+    int nfft, dev; size_t K, step;
+    redio_pspec_shape(plan, &nfft, &K, &step, &dev);
+    const size_t W = (K - 1) * step + (size_t)nfft;
+    // the plan's scratch, sized here for the seam windows (at most 2*W samples per head run); a longer body run grows it at enqueue
+    // time unless redio_pspec_reserve(plan, largest message + W) came first
+    const int rr = redio_pspec_reserve(plan, 2 * W);
+    if (rr) return rr;
+    return make(h, K_PSPEC, plan, dev, W, K * step, 8, (size_t)nfft, 4);
 }

@@ -258,14 +258,15 @@ class Chain:
 
 
 class Stream:
-    """redio_{fir,chain,pfb,ovsave,ovsave_real}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
+    """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
     segmentation of the input gives the bits of one stateless call on the whole stream (the stateless plans keep the
-    reference's per-message semantics, dsputils.rs:30-32).  `plan` is a Fir, Chain, Channelizer, OverlapSave or OverlapSaveReal."""
+    reference's per-message semantics, dsputils.rs:30-32).  `plan` is a Fir, Chain, Channelizer, OverlapSave, OverlapSaveReal or PowerSpectrum
+    (complex64 in, float32 rows out)."""
 
     def __init__(self, plan, u8=False):
         """u8=True (Chain and Channelizer): the stream arrives as the receiver's interleaved u8 I/Q bytes (uint8 tensors, two
         bytes per sample; redio_{chain,pfb}_stream_create_u8)."""
-        kind = {Fir: "fir", Chain: "chain"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real"}[type(plan).__name__]
+        kind = {Fir: "fir", Chain: "chain"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec"}[type(plan).__name__]
         assert not u8 or kind in ("chain", "pfb")
         self._kind, self._plan, self._u8 = kind, plan, bool(u8)          # the plan must outlive the stream handle
         self._h = C.c_void_p()
@@ -298,7 +299,7 @@ class Stream:
             nsamp = x.numel()
         n = self.nout(nsamp)
         if out is None:
-            out = torch.empty(max(n, 1), dtype=want, device=x.device)
+            out = torch.empty(max(n, 1), dtype=torch.float32 if self._kind == "pspec" else want, device=x.device)
         assert out.numel() >= n
         got = C.c_size_t(0)
         check(self._f("enqueue")(self._h, _dev_ptr(x) if x.numel() else None, nsamp, _dev_ptr(out), C.byref(got), current_stream()),
@@ -693,4 +694,58 @@ class OverlapSaveReal:
     def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
         if getattr(self, "_h", None):
             _safe_destroy("redio_ovsave_real_destroy", self._h)
+            self._h = None
+
+
+class PowerSpectrum:
+    """redio_pspec_*: |X[k]|^2 of kissfft::fft blocks (kissfft.rs:18-31) of nfft samples that start every `step` samples, optionally
+    windowed, summed over `integrate` consecutive transforms in the blocked order of DESIGN.md 5.3c: complex64 samples in, rows of
+    nfft float32 out.  nfft = 1024 is one kernel (is_fused)."""
+
+    AUTO, ROWS, SEGMENTS = 0, 1, 2
+
+    def __init__(self, nfft=1024, integrate=1, step=None, window=None):
+        self.nfft, self.integrate = int(nfft), int(integrate)
+        self.step = self.nfft if step is None else int(step)
+        p = None
+        if window is not None:
+            w, p = _taps(window)
+            assert len(w) == self.nfft, "a window of nfft values"
+        self._h = C.c_void_p()
+        check(lib().redio_pspec_create(C.byref(self._h), self.nfft, self.integrate, self.step, p), "pspec_create")
+
+    def nrows(self, n_in):
+        return lib().redio_pspec_nrows(self._h, n_in)
+
+    @property
+    def is_fused(self):
+        return bool(lib().redio_pspec_is_fused(self._h))
+
+    def reserve(self, n_in):
+        check(lib().redio_pspec_reserve(self._h, n_in), "pspec_reserve")
+
+    def set_split(self, mode):
+        """AUTO / ROWS (one wavefront per whole row) / SEGMENTS (one per segment of 16 transforms and a fold pass): the same bits."""
+        check(lib().redio_pspec_set_split(self._h, int(mode)), "pspec_set_split")
+
+    def _run(self, fn, x, count, rows, out):
+        import torch
+        assert x.dtype == torch.complex64
+        if out is None:
+            out = torch.empty(rows * self.nfft, dtype=torch.float32, device=x.device)
+        assert out.dtype == torch.float32 and out.numel() >= rows * self.nfft
+        check(fn(self._h, _dev_ptr(x), count, _dev_ptr(out), current_stream()), "pspec_enqueue")
+        return out[: rows * self.nfft].view(rows, self.nfft)
+
+    def __call__(self, x, out=None):
+        return self._run(lib().redio_pspec_enqueue, x, x.numel(), self.nrows(x.numel()), out)
+
+    def spectra(self, X, out=None):
+        """the same integration over packed, already transformed rows of nfft bins (a Chain's output): numel // nfft // integrate rows"""
+        nbatch = X.numel() // self.nfft
+        return self._run(lib().redio_pspec_enqueue_spectra, X, nbatch, nbatch // self.integrate, out)
+
+    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
+        if getattr(self, "_h", None):
+            _safe_destroy("redio_pspec_destroy", self._h)
             self._h = None

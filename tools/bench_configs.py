@@ -1,5 +1,5 @@
 """Throughput of the non-headline configs of BASELINE.json on one MI355X (own measurements; bench.py
-stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal]..."""
+stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec]..."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, libredio_amd as R
@@ -107,6 +107,34 @@ if "ovsavereal" in which:
               f"{n/ms_c/1e6:.1f} GS/s | (b) direct f32 FIR {k} taps /1: {ms_f:.3f} ms  {n/ms_f/1e6:.1f} GS/s | "
               f"time per sample real / complex = {ms_r/ms_c:.3f}")
         del real, cplx, fir, outr, outc, outf
+if "pspec" in which:
+    # the integrated power spectrum of 2^28 cf32 samples against the plain 1024-point transform of the same samples (which writes every
+    # spectrum back: 16 B per sample), timed alternately, twice each, in this one process; the smaller time of each is printed.  The bar
+    # for the fused size: time per sample below the transform's.  Then N = 4096 on the generic path (no bar: it pays the transform's 16 B
+    # and the accumulate pass).
+    x = R.synth_iq(2, 0, n)
+    fft = R.Fft(1024)
+    outc = torch.empty_like(x)
+    win = R.dsputils.lpf_corrected(1024, 0.1)
+    for nfft, k, step, w, mode, label in ((1024, 16, 1024, None, 0, "auto"), (1024, 1024, 1024, None, 1, "mode 1: a wave per row"),
+                                          (1024, 1024, 1024, None, 2, "mode 2: a wave per segment + fold"), (1024, 16, 512, win, 0, "auto, windowed, step 512"),
+                                          (4096, 16, 4096, None, 0, "generic")):
+        plan = R.PowerSpectrum(nfft, k, step, w)
+        plan.set_split(mode)
+        plan.reserve(n)
+        rows = plan.nrows(n)
+        out = torch.empty(rows * nfft, dtype=torch.float32, device="cuda")
+        reps = 10 if plan.is_fused else 3
+        b = 8 * nfft / step + 4 / k  # algorithmic bytes per input sample
+        ms_p = ms_f = 1e30
+        for _ in range(2):
+            ms_p = min(ms_p, timeit(lambda: plan(x, out=out), n=reps, warm=3))
+            ms_f = min(ms_f, timeit(lambda: fft(x, out=outc), n=reps, warm=3))
+        print(f"PSPEC {nfft} K={k} step={step} ({label}): {rows} rows  {ms_p:.3f} ms  {n/ms_p/1e6:.1f} GS/s  {b*n/ms_p/1e6:.0f} GB/s algorithmic "
+              f"({b*n/ms_p/1e6/8000:.1%} of 8 TB/s) | FFT 1024 on the same samples: {ms_f:.3f} ms  {n/ms_f/1e6:.1f} GS/s | "
+              f"time per sample pspec / fft = {ms_p/ms_f:.3f}")
+        del plan, out
+    del x, outc, fft
 if "fftall" in which:
     for nfft in (6, 9, 10, 12, 15, 20, 24, 25, 27, 30, 40, 45, 48, 60, 75, 80, 81, 90, 96, 100, 120, 125, 150, 160, 180, 192, 200, 225, 240, 243, 250, 300, 320, 360, 384, 400, 450, 480, 500, 600, 625, 640, 720, 729, 768, 800, 900, 960, 1000, 1200, 1280, 1440, 1536, 1600, 1800, 1920, 2000, 2187, 2400, 2560, 3072, 3125, 3200, 3600, 3840, 4000, 4800, 5120, 6144, 6400, 6561, 7680, 8000):
         x = R.synth_iq(2, 0, n)[: n // nfft * nfft]
