@@ -34,10 +34,15 @@ __device__ __forceinline__ void static_for4(F &&f)
 // 2 + 1.6 bytes per sample through HBM instead of 8 + 8 + 1.6 for the conversion kernel followed by this one.
 // PF2: TWO sub-tiles of loads in flight (round 6): a second register set of NLD pairs, the loop unrolled by two with the
 // roles of the sets swapped -- the request for sub-tile j + 2 is issued before the FIR of sub-tile j, the set holding j + 1 is parked behind it.
-template <int K, int D, bool FUSED, int WPS, int CH, bool FIR_ONLY = false, bool TWP = false, bool IN_U8 = false, bool PF2 = false>
-__global__ __launch_bounds__(64, WPS) void chain_v4_kernel(const float2 *__restrict__ x, const float *__restrict__ taps,
-                                                           const float2 *__restrict__ tw, float2 *__restrict__ out,
-                                                           long nblocks, long blocks_per_wave, unsigned long long *dbg, long dbg_cap)
+// RES: the FIR runs with the taps resident in scalar registers (fir_lane_v_res).  PRECONDITION of RES: the taps are bit-palindromic
+// (taps[i] and taps[K-1-i] the same 32-bit pattern); the host decides that once per plan (taps_bit_palindromic) and every launcher
+// below takes the answer.  !RES: any taps (fir_lane_v, staged per chunk through the scalar cache).
+// One body for the single-message kernels, the list kernel and their any-taps twins; `wave` is the wavefront's index within its
+// message (the workgroup index of a single-message launch).
+template <int K, int D, bool FUSED, int WPS, int CH, bool FIR_ONLY, bool TWP, bool IN_U8, bool PF2, bool RES>
+__device__ __forceinline__ void chain_v4_body(const float2 *__restrict__ x, const float *__restrict__ taps,
+                                              const float2 *__restrict__ tw, float2 *__restrict__ out,
+                                              long nblocks, long blocks_per_wave, long wave, unsigned long long *dbg, long dbg_cap)
 {
     // diagnostic only (dbg != nullptr): shader-clock and 100 MHz real-time stamps around the wave's life,
     // written to a buffer of their own; run times of such launches are never quoted
@@ -57,10 +62,13 @@ __global__ __launch_bounds__(64, WPS) void chain_v4_kernel(const float2 *__restr
     float2 *ex = reinterpret_cast<float2 *>(smem);
 
     const int lane = threadIdx.x;
-    const long b0 = (long)blockIdx.x * blocks_per_wave;
+    const long b0 = wave * blocks_per_wave;
     if (b0 >= nblocks) return;
     const long b1 = (b0 + blocks_per_wave < nblocks) ? b0 + blocks_per_wave : nblocks;
     const long nsub = 4 * (b1 - b0);                  // sub-tiles of this wave, consecutive in the stream
+    // the ceil(K/2) distinct taps, once per wave (the any-taps kernels carry no resident state)
+    typename std::conditional<RES, FirTapsResident<K>, FirNoResidentTaps>::type rtaps;
+    if constexpr (RES) fir_taps_resident_load(rtaps, taps);
     // index of the first NEW pair of samples of sub-tile j (the halo precedes it): a pair is one float4, or one u32 of I/Q bytes
     using pair_t = typename std::conditional<IN_U8, unsigned, v4f_t>::type;
     const pair_t *src0 = (IN_U8 ? reinterpret_cast<const pair_t *>(reinterpret_cast<const unsigned *>(x) + b0 * 512 * (long)D)
@@ -147,7 +155,8 @@ __global__ __launch_bounds__(64, WPS) void chain_v4_kernel(const float2 *__restr
         for (int r = 0; r < R; ++r) acc[r] = make_float2(0.f, 0.f);
         int lf = lane; // opaque per sub-tile: keeps LDS address arithmetic out of the loop's live set
         asm volatile("" : "+v"(lf));
-        fir_lane_v<K, D, R, FUSED, CH>(xs4, lf, taps, acc);
+        if constexpr (RES) fir_lane_v_res<K, D, R, FUSED, CH>(xs4, lf, rtaps, acc);
+        else fir_lane_v<K, D, R, FUSED, CH>(xs4, lf, taps, acc);
         if (FIR_ONLY) { // 32 contiguous bytes per lane, 2 KiB per wave
             v4f_t *y4 = reinterpret_cast<v4f_t *>(out + (b0 * 4 + j) * SUB_OUT) + 2 * lane;
             y4[0] = v4f_t{acc[0].x, acc[0].y, acc[1].x, acc[1].y};
@@ -210,6 +219,24 @@ __global__ __launch_bounds__(64, WPS) void chain_v4_kernel(const float2 *__restr
     }
 }
 
+// PRECONDITION: bit-palindromic taps (chain_v4_body, RES).  The template parameters, and so the name a profiler prints, are those of
+// the kernel before the resident-taps form.
+template <int K, int D, bool FUSED, int WPS, int CH, bool FIR_ONLY = false, bool TWP = false, bool IN_U8 = false, bool PF2 = false>
+__global__ __launch_bounds__(64, WPS) void chain_v4_kernel(const float2 *__restrict__ x, const float *__restrict__ taps,
+                                                           const float2 *__restrict__ tw, float2 *__restrict__ out,
+                                                           long nblocks, long blocks_per_wave, unsigned long long *dbg, long dbg_cap)
+{
+    chain_v4_body<K, D, FUSED, WPS, CH, FIR_ONLY, TWP, IN_U8, PF2, true>(x, taps, tw, out, nblocks, blocks_per_wave, (long)blockIdx.x, dbg, dbg_cap);
+}
+// any taps: the plans whose taps are not bit-palindromic
+template <int K, int D, bool FUSED, int WPS, int CH, bool FIR_ONLY = false, bool TWP = false, bool IN_U8 = false, bool PF2 = false>
+__global__ __launch_bounds__(64, WPS) void chain_v4_anytaps_kernel(const float2 *__restrict__ x, const float *__restrict__ taps,
+                                                                   const float2 *__restrict__ tw, float2 *__restrict__ out,
+                                                                   long nblocks, long blocks_per_wave, unsigned long long *dbg, long dbg_cap)
+{
+    chain_v4_body<K, D, FUSED, WPS, CH, FIR_ONLY, TWP, IN_U8, PF2, false>(x, taps, tw, out, nblocks, blocks_per_wave, (long)blockIdx.x, dbg, dbg_cap);
+}
+
 // A list of independent cf32 messages in ONE launch (redio_chain_enqueue_list): message i owns the waves [wave0[i], wave0[i + 1]).
 // The list travels by value in the kernel arguments: no descriptor buffer, nothing to upload or recycle, and a captured launch carries
 // its own copy.
@@ -222,93 +249,34 @@ struct ChainList {
 };
 
 // A wave runs exactly what chain_v4_kernel<K, D, FUSED, 2, 8, false, true> runs for (x_i, out_i, nblocks_i, blocks_per_wave): the same
-// head fetch, FIR and transform, so the bits are those of one launch per message; a wave never spans two messages.  A copy of that
-// kernel's cf32 path, not a shared body: moving the body into an inlined function changed the instruction schedule of every existing
-// instantiation, and the headline kernel stays as it was measured.
-template <int K, int D, bool FUSED>
-__global__ __launch_bounds__(64, 2) void chain_v4_list_kernel(const ChainList list, const float *__restrict__ taps,
-                                                              const float2 *__restrict__ tw, long blocks_per_wave)
+// body, so the bits are those of one launch per message; a wave never spans two messages.
+template <int K, int D, bool FUSED, bool RES>
+__device__ __forceinline__ void chain_v4_list_body(const ChainList &list, const float *__restrict__ taps, const float2 *__restrict__ tw,
+                                                   long blocks_per_wave)
 {
-    constexpr int R = 4, CH = 8;
-    using G = FirGeomV<K, D, R>;
-    constexpr int SUB_OUT = 64 * R;                   // 256 outputs per sub-tile
-    constexpr int SUB_NEW = SUB_OUT * D;              // new input samples per sub-tile
-    constexpr int HALO = G::tile_in(SUB_OUT) - SUB_NEW; // samples shared with the previous sub-tile
-    static_assert(HALO % 2 == 0 && SUB_NEW % 128 == 0 && 4 * SUB_OUT == 1024, "geometry");
-    constexpr int HALO_V = HALO / 2;
-    constexpr int NLD = SUB_NEW / 2 / 64;
-    static_assert(HALO_V <= 64, "the halo moves with one instruction per lane");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    v4f_t *xs4 = reinterpret_cast<v4f_t *>(smem);
-    float2 *ex = reinterpret_cast<float2 *>(smem);
-
     // which message: a scan of the wave-start prefix in scalar registers (the workgroup index and the list are wave-uniform)
     const unsigned w = blockIdx.x;
     int m = 0;
     for (int i = 1; i < list.count; ++i) m = w >= list.wave0[i] ? i : m;
     m = __builtin_amdgcn_readfirstlane(m);
-    const float2 *x = list.x[m];
-    float2 *out = list.out[m];
-    const long nblocks = list.nblocks[m];
+    // wave index within the message: b0 < nblocks, the host gives message i ceil(nblocks_i / bpw) waves
+    chain_v4_body<K, D, FUSED, 2, 8, false, true, false, false, RES>(list.x[m], taps, tw, list.out[m], list.nblocks[m], blocks_per_wave,
+                                                                     (long)(w - list.wave0[m]), nullptr, 0);
+}
 
-    const int lane = threadIdx.x;
-    const long b0 = (long)(w - list.wave0[m]) * blocks_per_wave; // < nblocks: the host gives message i ceil(nblocks_i / bpw) waves
-    const long b1 = (b0 + blocks_per_wave < nblocks) ? b0 + blocks_per_wave : nblocks;
-    const long nsub = 4 * (b1 - b0);
-    const v4f_t *src0 = reinterpret_cast<const v4f_t *>(x + b0 * 1024 * (long)D) + lane;
-    v4f_t pre[NLD];
-    auto fetch = [&](long j) { // new samples of sub-tile j: [HALO + j*SUB_NEW, HALO + (j+1)*SUB_NEW)
-        const v4f_t *src = src0 + HALO_V + j * (SUB_NEW / 2);
-#if REDIO_EXP_CHAIN_NT & 1
-        static_for4<NLD>([&](auto I) { pre[I.value] = __builtin_nontemporal_load(src + 64 * I.value); });
-#else
-        static_for4<NLD>([&](auto I) { pre[I.value] = src[64 * I.value]; });
-#endif
-    };
-    auto park = [&] { static_for4<NLD>([&](auto I) { xs4[G::lds_index(HALO + 2 * (lane + 64 * I.value)) / 2] = pre[I.value]; }); };
-
-    if (lane < HALO_V) xs4[G::lds_index(2 * lane) / 2] = src0[0]; // the run's own head
-    fetch(0);
-    park();
-    wave_lds_fence();
-
-    float2 a[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) a[i] = make_float2(0.f, 0.f);
-    Fft1knTw34 t34;
-    fft1kn_load_tw34(t34, lane, tw);
-#pragma unroll 1
-    for (long j = 0; j < nsub; ++j) {
-        const bool more = j + 1 < nsub;
-        if (more) fetch(j + 1);
-        float2 acc[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = make_float2(0.f, 0.f);
-        int lf = lane;
-        asm volatile("" : "+v"(lf));
-        fir_lane_v<K, D, R, FUSED, CH>(xs4, lf, taps, acc);
-#pragma unroll
-        for (int i = 0; i < 12; ++i) a[i] = a[i + 4];
-#pragma unroll
-        for (int r = 0; r < R; ++r) a[12 + r] = acc[r];
-        wave_lds_fence();
-        v4f_t halo = v4f_t{0.f, 0.f, 0.f, 0.f};
-        if (more && lf < HALO_V) halo = xs4[G::lds_index(SUB_NEW + 2 * lf) / 2];
-        if ((j & 3) == 3) {
-            wave_lds_fence();
-            int ln = lane;
-            asm volatile("" : "+v"(ln));
-            Fft1knTw12 t12;
-            fft1kn_load_tw12(t12, ln, tw);
-            fft1kn_wave_tw<false>(a, ex, tw, t12, t34, out + (b0 + (j >> 2)) * 1024, ln);
-            wave_lds_fence();
-        }
-        if (more) {
-            if (lf < HALO_V) xs4[G::lds_index(2 * lf) / 2] = halo;
-            park();
-        }
-        wave_lds_fence();
-    }
+// PRECONDITION: bit-palindromic taps (chain_v4_body, RES)
+template <int K, int D, bool FUSED>
+__global__ __launch_bounds__(64, 2) void chain_v4_list_kernel(const ChainList list, const float *__restrict__ taps,
+                                                              const float2 *__restrict__ tw, long blocks_per_wave)
+{
+    chain_v4_list_body<K, D, FUSED, true>(list, taps, tw, blocks_per_wave);
+}
+// any taps
+template <int K, int D, bool FUSED>
+__global__ __launch_bounds__(64, 2) void chain_v4_anytaps_list_kernel(const ChainList list, const float *__restrict__ taps,
+                                                                      const float2 *__restrict__ tw, long blocks_per_wave)
+{
+    chain_v4_list_body<K, D, FUSED, false>(list, taps, tw, blocks_per_wave);
 }
 
 // blocks per wavefront of a launch over nblocks blocks at WPS wavefronts per SIMD (the chain: 2; the FIR alone: 3)
@@ -348,62 +316,70 @@ static constexpr size_t chain_v4_lds()
     return LDS;
 }
 
+// pal: the plan's taps are bit-palindromic (decided once at plan creation): the resident-taps kernel, whose precondition that is; else its any-taps twin
 template <int K, int D, int WPS, int CH, bool FIR_ONLY = false, bool TWP = false, bool IN_U8 = false, bool PF2 = false>
-static hipError_t launch_v4_t(const float2 *x, const float *taps, const float2 *tw, float2 *out, long nblocks, bool fused,
+static hipError_t launch_v4_t(const float2 *x, const float *taps, bool pal, const float2 *tw, float2 *out, long nblocks, bool fused,
                               hipStream_t s, unsigned long long *dbg, long dbg_cap = 0)
 {
     constexpr size_t LDS = chain_v4_lds<K, D, WPS, PF2>();
     const long bpw = chain_v4_blocks_per_wave(nblocks, WPS);
     const long grid = (nblocks + bpw - 1) / bpw;
-    if (fused) hipLaunchKernelGGL((chain_v4_kernel<K, D, true, WPS, CH, FIR_ONLY, TWP, IN_U8, PF2>), dim3((unsigned)grid), dim3(64), LDS, s, x, taps, tw, out, nblocks, bpw, dbg, dbg_cap);
-    else hipLaunchKernelGGL((chain_v4_kernel<K, D, false, WPS, CH, FIR_ONLY, TWP, IN_U8, PF2>), dim3((unsigned)grid), dim3(64), LDS, s, x, taps, tw, out, nblocks, bpw, dbg, dbg_cap);
+    if (pal) {
+        if (fused) hipLaunchKernelGGL((chain_v4_kernel<K, D, true, WPS, CH, FIR_ONLY, TWP, IN_U8, PF2>), dim3((unsigned)grid), dim3(64), LDS, s, x, taps, tw, out, nblocks, bpw, dbg, dbg_cap);
+        else hipLaunchKernelGGL((chain_v4_kernel<K, D, false, WPS, CH, FIR_ONLY, TWP, IN_U8, PF2>), dim3((unsigned)grid), dim3(64), LDS, s, x, taps, tw, out, nblocks, bpw, dbg, dbg_cap);
+    } else {
+        if (fused) hipLaunchKernelGGL((chain_v4_anytaps_kernel<K, D, true, WPS, CH, FIR_ONLY, TWP, IN_U8, PF2>), dim3((unsigned)grid), dim3(64), LDS, s, x, taps, tw, out, nblocks, bpw, dbg, dbg_cap);
+        else hipLaunchKernelGGL((chain_v4_anytaps_kernel<K, D, false, WPS, CH, FIR_ONLY, TWP, IN_U8, PF2>), dim3((unsigned)grid), dim3(64), LDS, s, x, taps, tw, out, nblocks, bpw, dbg, dbg_cap);
+    }
     return hipGetLastError();
 }
 
-hipError_t launch_chain_v4(const float2 *x, const float *taps, const float2 *tw, float2 *out, long nblocks, bool fused,
+hipError_t launch_chain_v4(const float2 *x, const float *taps, bool pal, const float2 *tw, float2 *out, long nblocks, bool fused,
                            hipStream_t s, unsigned long long *dbg, long dbg_cap)
 {
     // (three wavefronts per SIMD were measured again in round 3 with the new access policy: the transform's registers spill at
     // 168 per lane, 0.56-0.60 against 0.517 ms)
 #ifdef REDIO_MEASURE // three wavefronts per SIMD without the resident last-stage twiddles (168 registers, 80 bytes of scratch): measured in round 4, see DESIGN.md 5.1
-    if (measure_env("REDIO_CHAIN_WPS3")) return launch_v4_t<127, 5, 3, 8, false, false>(x, taps, tw, out, nblocks, fused, s, dbg, dbg_cap);
+    if (measure_env("REDIO_CHAIN_WPS3")) return launch_v4_t<127, 5, 3, 8, false, false>(x, taps, pal, tw, out, nblocks, fused, s, dbg, dbg_cap);
     // two sub-tiles of loads in flight (round 6): A/B against the product form in one process, tools/chain_pf2_ab.py
-    if (measure_env("REDIO_CHAIN_PF2")) return launch_v4_t<127, 5, 2, 8, false, true, false, true>(x, taps, tw, out, nblocks, fused, s, dbg, dbg_cap);
+    if (measure_env("REDIO_CHAIN_PF2")) return launch_v4_t<127, 5, 2, 8, false, true, false, true>(x, taps, pal, tw, out, nblocks, fused, s, dbg, dbg_cap);
 #endif
-    return launch_v4_t<127, 5, 2, 8, false, true>(x, taps, tw, out, nblocks, fused, s, dbg, dbg_cap); // last-stage twiddles resident
+    return launch_v4_t<127, 5, 2, 8, false, true>(x, taps, pal, tw, out, nblocks, fused, s, dbg, dbg_cap); // last-stage twiddles resident
 }
 
 // u8 I/Q bytes in (4-byte aligned), spectra out: data_to_samples -> 127-tap FIR / 5 -> 1024-point FFT in one kernel
-hipError_t launch_chain_v4_u8(const void *bytes, const float *taps, const float2 *tw, float2 *out, long nblocks, bool fused, hipStream_t s)
+// pal, here and in every launcher of this file: the plan's taps are bit-palindromic (the precondition of chain_v4_kernel); false selects
+// chain_v4_anytaps_kernel
+hipError_t launch_chain_v4_u8(const void *bytes, const float *taps, bool pal, const float2 *tw, float2 *out, long nblocks, bool fused, hipStream_t s)
 {
-    return launch_v4_t<127, 5, 2, 8, false, true, true>((const float2 *)bytes, taps, tw, out, nblocks, fused, s, nullptr); // 3 waves per SIMD: 0.52 against 0.46 ms
+    return launch_v4_t<127, 5, 2, 8, false, true, true>((const float2 *)bytes, taps, pal, tw, out, nblocks, fused, s, nullptr); // 3 waves per SIMD: 0.52 against 0.46 ms
 }
 
-hipError_t launch_chain_v4_shape_u8(int K, int D, const void *bytes, const float *taps, const float2 *tw, float2 *out, long nblocks, bool fused,
+hipError_t launch_chain_v4_shape_u8(int K, int D, const void *bytes, const float *taps, bool pal, const float2 *tw, float2 *out, long nblocks, bool fused,
                                     hipStream_t s)
 {
     const float2 *x = (const float2 *)bytes;
-    if (K == 63 && D == 5) return launch_v4_t<63, 5, 2, 8, false, true, true>(x, taps, tw, out, nblocks, fused, s, nullptr);
-    if (K == 127 && D == 1) return launch_v4_t<127, 1, 2, 8, false, true, true>(x, taps, tw, out, nblocks, fused, s, nullptr);
-    if (K == 63 && D == 1) return launch_v4_t<63, 1, 2, 8, false, true, true>(x, taps, tw, out, nblocks, fused, s, nullptr);
-    if (K == 127 && D == 3) return launch_v4_t<127, 3, 2, 8, false, true, true>(x, taps, tw, out, nblocks, fused, s, nullptr);
+    if (K == 63 && D == 5) return launch_v4_t<63, 5, 2, 8, false, true, true>(x, taps, pal, tw, out, nblocks, fused, s, nullptr);
+    if (K == 127 && D == 1) return launch_v4_t<127, 1, 2, 8, false, true, true>(x, taps, pal, tw, out, nblocks, fused, s, nullptr);
+    if (K == 63 && D == 1) return launch_v4_t<63, 1, 2, 8, false, true, true>(x, taps, pal, tw, out, nblocks, fused, s, nullptr);
+    if (K == 127 && D == 3) return launch_v4_t<127, 3, 2, 8, false, true, true>(x, taps, pal, tw, out, nblocks, fused, s, nullptr);
     return hipErrorNotSupported;
 }
 
 // the same kernel for the other tap / decimation pairs with a fused build (K - D even, image within the per-wave LDS budget)
-hipError_t launch_chain_v4_shape(int K, int D, const float2 *x, const float *taps, const float2 *tw, float2 *out, long nblocks, bool fused,
+hipError_t launch_chain_v4_shape(int K, int D, const float2 *x, const float *taps, bool pal, const float2 *tw, float2 *out, long nblocks, bool fused,
                                  hipStream_t s)
 {
-    if (K == 63 && D == 5) return launch_v4_t<63, 5, 2, 8, false, true>(x, taps, tw, out, nblocks, fused, s, nullptr);
-    if (K == 127 && D == 1) return launch_v4_t<127, 1, 2, 8, false, true>(x, taps, tw, out, nblocks, fused, s, nullptr);
-    if (K == 63 && D == 1) return launch_v4_t<63, 1, 2, 8, false, true>(x, taps, tw, out, nblocks, fused, s, nullptr);
-    if (K == 127 && D == 3) return launch_v4_t<127, 3, 2, 8, false, true>(x, taps, tw, out, nblocks, fused, s, nullptr);
+    if (K == 63 && D == 5) return launch_v4_t<63, 5, 2, 8, false, true>(x, taps, pal, tw, out, nblocks, fused, s, nullptr);
+    if (K == 127 && D == 1) return launch_v4_t<127, 1, 2, 8, false, true>(x, taps, pal, tw, out, nblocks, fused, s, nullptr);
+    if (K == 63 && D == 1) return launch_v4_t<63, 1, 2, 8, false, true>(x, taps, pal, tw, out, nblocks, fused, s, nullptr);
+    if (K == 127 && D == 3) return launch_v4_t<127, 3, 2, 8, false, true>(x, taps, pal, tw, out, nblocks, fused, s, nullptr);
     return hipErrorNotSupported;
 }
 
 template <int K, int D>
 static hipError_t launch_v4_list_t(const float2 *const *x, float2 *const *out, const long *nblocks, int count, const float *taps,
-                                   const float2 *tw, bool fused, hipStream_t s)
+                                   bool pal, const float2 *tw, bool fused, hipStream_t s)
 {
     ChainList list;
     long total = 0;
@@ -421,45 +397,51 @@ static hipError_t launch_v4_list_t(const float2 *const *x, float2 *const *out, c
     list.wave0[count] = w;
     list.count = count;
     constexpr size_t LDS = chain_v4_lds<K, D, 2>(); // the single launch's request: the dispatcher packs no extra wave onto a CU
-    if (fused) hipLaunchKernelGGL((chain_v4_list_kernel<K, D, true>), dim3(w), dim3(64), LDS, s, list, taps, tw, bpw);
-    else hipLaunchKernelGGL((chain_v4_list_kernel<K, D, false>), dim3(w), dim3(64), LDS, s, list, taps, tw, bpw);
+    if (pal) { // the resident-taps kernel's precondition
+        if (fused) hipLaunchKernelGGL((chain_v4_list_kernel<K, D, true>), dim3(w), dim3(64), LDS, s, list, taps, tw, bpw);
+        else hipLaunchKernelGGL((chain_v4_list_kernel<K, D, false>), dim3(w), dim3(64), LDS, s, list, taps, tw, bpw);
+    } else {
+        if (fused) hipLaunchKernelGGL((chain_v4_anytaps_list_kernel<K, D, true>), dim3(w), dim3(64), LDS, s, list, taps, tw, bpw);
+        else hipLaunchKernelGGL((chain_v4_anytaps_list_kernel<K, D, false>), dim3(w), dim3(64), LDS, s, list, taps, tw, bpw);
+    }
     return hipGetLastError();
 }
 
 // count (1 ... REDIO_LIST_MAX) messages of the fused cf32 shapes in one launch: 16-byte aligned inputs, nblocks[i] >= 1 each
+// pal: the plan's taps are bit-palindromic (the resident-taps list kernel), else the any-taps twin runs
 hipError_t launch_chain_list(int K, long D, const float2 *const *x, float2 *const *out, const long *nblocks, int count, const float *taps,
-                             const float2 *tw, bool fused, hipStream_t s)
+                             bool pal, const float2 *tw, bool fused, hipStream_t s)
 {
     if (count < 1 || count > REDIO_LIST_MAX) return hipErrorInvalidValue;
     for (int i = 0; i < count; ++i)
         if (nblocks[i] < 1 || (reinterpret_cast<uintptr_t>(x[i]) & 15) != 0) return hipErrorInvalidValue;
-    if (K == 127 && D == 5) return launch_v4_list_t<127, 5>(x, out, nblocks, count, taps, tw, fused, s);
-    if (K == 127 && D == 3) return launch_v4_list_t<127, 3>(x, out, nblocks, count, taps, tw, fused, s);
-    if (K == 127 && D == 1) return launch_v4_list_t<127, 1>(x, out, nblocks, count, taps, tw, fused, s);
-    if (K == 63 && D == 5) return launch_v4_list_t<63, 5>(x, out, nblocks, count, taps, tw, fused, s);
-    if (K == 63 && D == 1) return launch_v4_list_t<63, 1>(x, out, nblocks, count, taps, tw, fused, s);
+    if (K == 127 && D == 5) return launch_v4_list_t<127, 5>(x, out, nblocks, count, taps, pal, tw, fused, s);
+    if (K == 127 && D == 3) return launch_v4_list_t<127, 3>(x, out, nblocks, count, taps, pal, tw, fused, s);
+    if (K == 127 && D == 1) return launch_v4_list_t<127, 1>(x, out, nblocks, count, taps, pal, tw, fused, s);
+    if (K == 63 && D == 5) return launch_v4_list_t<63, 5>(x, out, nblocks, count, taps, pal, tw, fused, s);
+    if (K == 63 && D == 1) return launch_v4_list_t<63, 1>(x, out, nblocks, count, taps, pal, tw, fused, s);
     return hipErrorNotSupported;
 }
 
 // stand-alone decimating FIR on whole 1024-output blocks (16-byte aligned cf32 in and out) for the shapes the chain kernel is
 // built for: the chain's data path (wave-private image, halo carried in LDS, register prefetch, taps in SGPRs), storing the
 // decimated samples instead of transforming them.  hipErrorNotSupported: no such instantiation (the tiled kernels run).
-hipError_t launch_fir_v4(int K, int D, const float2 *x, const float *taps, float2 *y, long nblocks, bool fused, hipStream_t s)
+hipError_t launch_fir_v4(int K, int D, const float2 *x, const float *taps, bool pal, float2 *y, long nblocks, bool fused, hipStream_t s)
 {
     // Three wavefronts per SIMD (round 5): without the transform these instantiations need 94-145 registers, and the third wavefront
     // hides more of the window reads' and the stream's latency -- 2^26 samples: 127 / 5 0.1189 -> 0.1109 ms (67.7 -> 72.6 % of 8 TB/s),
     // 63 / 5 0.1007 -> 0.0983, 63 / 1 0.2561 -> 0.2441; 2^28: 0.4901 -> 0.4818, 0.4655 -> 0.4664, 0.9973 -> 0.9688; the reference-rounding
     // builds 4-6 % (profiles/r05_fir_three_waves.txt; interleaved A/B in one process, bit-identical).  REDIO_FIR_WPS2: measurement builds.
     if (!measure_env("REDIO_FIR_WPS2")) {
-        if (K == 127 && D == 5) return launch_v4_t<127, 5, 3, 8, true>(x, taps, nullptr, y, nblocks, fused, s, nullptr);
-        if (K == 63 && D == 5) return launch_v4_t<63, 5, 3, 8, true>(x, taps, nullptr, y, nblocks, fused, s, nullptr);
-        if (K == 63 && D == 1) return launch_v4_t<63, 1, 3, 8, true>(x, taps, nullptr, y, nblocks, fused, s, nullptr);
-        if (K == 127 && D == 3) return launch_v4_t<127, 3, 3, 8, true>(x, taps, nullptr, y, nblocks, fused, s, nullptr);
+        if (K == 127 && D == 5) return launch_v4_t<127, 5, 3, 8, true>(x, taps, pal, nullptr, y, nblocks, fused, s, nullptr);
+        if (K == 63 && D == 5) return launch_v4_t<63, 5, 3, 8, true>(x, taps, pal, nullptr, y, nblocks, fused, s, nullptr);
+        if (K == 63 && D == 1) return launch_v4_t<63, 1, 3, 8, true>(x, taps, pal, nullptr, y, nblocks, fused, s, nullptr);
+        if (K == 127 && D == 3) return launch_v4_t<127, 3, 3, 8, true>(x, taps, pal, nullptr, y, nblocks, fused, s, nullptr);
     }
 #ifdef REDIO_MEASURE
-    if (K == 127 && D == 5) return launch_v4_t<127, 5, 2, 8, true>(x, taps, nullptr, y, nblocks, fused, s, nullptr);
-    if (K == 63 && D == 5) return launch_v4_t<63, 5, 2, 8, true>(x, taps, nullptr, y, nblocks, fused, s, nullptr);
-    if (K == 63 && D == 1) return launch_v4_t<63, 1, 2, 8, true>(x, taps, nullptr, y, nblocks, fused, s, nullptr);
+    if (K == 127 && D == 5) return launch_v4_t<127, 5, 2, 8, true>(x, taps, pal, nullptr, y, nblocks, fused, s, nullptr);
+    if (K == 63 && D == 5) return launch_v4_t<63, 5, 2, 8, true>(x, taps, pal, nullptr, y, nblocks, fused, s, nullptr);
+    if (K == 63 && D == 1) return launch_v4_t<63, 1, 2, 8, true>(x, taps, pal, nullptr, y, nblocks, fused, s, nullptr);
 #endif
     // (127 taps, no decimation: VALU-bound, and the 256-thread tiled kernel with 8 outputs per lane is faster -- 0.44 against 0.56 ms per 2^26 samples;
     //  127 taps / 3 runs here since round 5 with three wavefronts per SIMD: 0.1589 against the chunked tiled kernel's 0.1713 ms, profiles/r05_fir_mid_shapes.txt)

@@ -166,6 +166,239 @@ RD_HD void fir_lane_v(Lds4Ptr xs4, int lane_slot, TapPtr h, float2 (&acc)[R])
     fir_chunks_v<0, K, D, R, FUSED, CH>(xs4, base4, h, q, hb, acc);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The same lane program for PALINDROMIC taps (h[j] and h[K-1-j] the same 32-bit pattern, which every
+// lpf_corrected design is): the ceil(K/2) distinct values stay in scalar registers for the life of the
+// wave as aligned 64-bit pairs, loaded once before the sub-tile loop.  Tap j is element
+// e = min(j, K-1-j): pair e/2, low word for even e, high word for odd e, selected by op_sel on the packed
+// multiply-add itself -- no per-chunk staging copy, no scalar move, and no scalar load inside the loop,
+// so the window's ds_read_b128 are the only counted (in-order) requests and are waited on one by one.
+// Samples are taken in ascending order and the live outputs of a sample in turn (r ascending), so each
+// output still receives its products in ascending tap order with the same rounding steps: same bits.
+// ---------------------------------------------------------------------------------------------
+template <int K>
+struct FirTapsResident {
+    static constexpr int NE = (K + 1) / 2;  // distinct tap values
+    static constexpr int NP = (NE + 1) / 2; // aligned pairs (the odd one out pairs with its mirror: index NE <= K-1 for K >= 3)
+    static_assert(K >= 3, "a pair never reads past the taps");
+    RD_HD static constexpr int elem(int j) { return j < K - 1 - j ? j : K - 1 - j; }
+    unsigned long long p[NP]; // (h[2i], h[2i+1]) as stored: low word first
+};
+
+struct FirNoResidentTaps {}; // what an any-taps kernel carries in that place: nothing
+
+// h: 8-byte aligned, wave-uniform.  Device: each pair is made opaque in a scalar register pair, so it is neither
+// re-fetched nor rebuilt inside the loop.
+template <int K, typename TapPtr>
+RD_HD void fir_taps_resident_load(FirTapsResident<K> &t, TapPtr h)
+{
+    fir_static_for<FirTapsResident<K>::NP>([&](auto I) {
+        constexpr int i = I.value;
+#if defined(__HIP_DEVICE_COMPILE__)
+        typedef unsigned long long u64a __attribute__((may_alias));
+        t.p[i] = reinterpret_cast<const u64a *>(&h[0])[i];
+        asm volatile("" : "+s"(t.p[i]));
+#else
+        unsigned lo, hi;
+        const float a = h[2 * i], b = h[2 * i + 1];
+        __builtin_memcpy(&lo, &a, 4);
+        __builtin_memcpy(&hi, &b, 4);
+        t.p[i] = (unsigned long long)lo | ((unsigned long long)hi << 32);
+#endif
+    });
+}
+
+// live outputs of window sample m: r in [r_lo(m), r_hi(m)], tap j = m - r*D in [0, K)
+template <int K, int D, int R>
+struct FirLive {
+    RD_HD static constexpr int lo(int m) { return m - (K - 1) <= 0 ? 0 : (m - (K - 1) + D - 1) / D; }
+    RD_HD static constexpr int hi(int m) { return m / D < R - 1 ? m / D : R - 1; }
+};
+
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef redio_v2f fir_acc_t; // one output (re, im) as ONE aligned 64-bit register pair
+#else
+typedef float2 fir_acc_t;
+#endif
+
+// What one 16-byte window read (samples m0 and m0 + 1) feeds: slot k = 4 * i + r is sample m0 + i into output r.
+template <int m0, int K, int D, int R, bool TWO /* sample m0 + 1 is inside the window */>
+struct FirReadPlan {
+    using L = FirLive<K, D, R>;
+    using T = FirTapsResident<K>;
+#if REDIO_EXP_ABLATE == 2 // timing-only experiment (tools/ablate.sh): half the multiply-adds (two of the four accumulators), as in fir_chunks_v
+    RD_HD static constexpr bool live(int k) { return !(k & 1) && (k < 4 || TWO) && (k & 3) >= L::lo(m0 + k / 4) && (k & 3) <= L::hi(m0 + k / 4) && (k & 3) < R; }
+#else
+    RD_HD static constexpr bool live(int k) { return (k < 4 || TWO) && (k & 3) >= L::lo(m0 + k / 4) && (k & 3) <= L::hi(m0 + k / 4) && (k & 3) < R; }
+#endif
+    RD_HD static constexpr int elem(int k) { return live(k) ? T::elem(m0 + k / 4 - (k & 3) * D) : 0; }
+    RD_HD static constexpr int pair(int k) { return elem(k) / 2; }
+    RD_HD static constexpr unsigned en() { unsigned v = 0; for (int k = 0; k < 8; ++k) v |= (live(k) ? 1u : 0u) << k; return v; }
+    RD_HD static constexpr unsigned hi() { unsigned v = 0; for (int k = 0; k < 8; ++k) v |= (unsigned)(elem(k) & 1) << k; return v; }
+    // FUSED: slots whose accumulator was written by the packed operation just before them (the previous live slot, or the last
+    // one of the previous read; the very first sample counts too: it follows the compiler's own initialisation)
+    RD_HD static constexpr unsigned nop_fused()
+    {
+        unsigned v = 0;
+        int prev = m0 == 0 ? 0 : L::hi(m0 - 1);
+        for (int k = 0; k < 8; ++k)
+            if (live(k)) { if ((k & 3) == prev) v |= 1u << k; prev = k & 3; }
+        return v;
+    }
+    // exact: bit i = sample m0 + i has ONE live output, so its add would directly follow its multiply
+    RD_HD static constexpr unsigned nop_exact()
+    {
+        unsigned v = 0;
+        for (int i = 0; i < 2; ++i) {
+            int n = 0;
+            for (int r = 0; r < 4; ++r) n += live(4 * i + r) ? 1 : 0;
+            if (n == 1) v |= 1u << i;
+        }
+        return v;
+    }
+};
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// The packed operations of ONE 16-byte read as ONE inline-assembly statement: acc[r] <- acc[r] + x_i * tap for the live slots, samples
+// in ascending order, the outputs of a sample in turn.  The slots a read does not have are assembled away (.if on the masks, which are
+// compile-time constants); their operands name registers that are live anyway.  One statement per read, so the compiler's wait for
+// that read (by count) is what separates two statements.
+// Inline assembly hides the instructions from the compiler's hazard pass: on gfx950 a packed-f32 result needs one wait state before
+// a vector instruction reads it, so no two DEPENDENT packed operations may be adjacent.  How that is guaranteed:
+//   FUSED: consecutive multiply-adds of a sample write different accumulators; where a slot's accumulator is the one the packed
+//          operation right before it wrote (one live output at the window's ends, the hand-over from sample to sample when the
+//          live ranges touch in one output, and across two statements, where the compiler may put nothing in between) the statement
+//          itself has an `s_nop 0` in front of that slot (FirReadPlan::nop_fused).
+//   exact: per sample, all multiplies come first and then the adds, so with two or more live outputs a product's add is at least
+//          two instructions behind its multiply and behind the previous add of its accumulator; with ONE live output an `s_nop 0`
+//          sits between the multiply and the add (nop_exact).  A sample begins with multiplies, which read no accumulator.
+//   fir_lane_v_res names the four accumulators in a statement of their own, followed by a wait state, before the first read's
+//   statement (the compiler's initialisation of them is then complete), and ends with one more `s_nop 0` before compiler code reads them.
+#define RD_FMA_SLOT(k, r, i)                                                                                             \
+    ".if (%[nb] >> " #k ") & 1\ns_nop 0\n.endif\n"                                                                      \
+    ".if (%[en] >> " #k ") & 1\n.if (%[hi] >> " #k ") & 1\n"                                                            \
+    "v_pk_fma_f32 %[a" #r "], %[x" #i "], %[t" #k "], %[a" #r "] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n.else\n"               \
+    "v_pk_fma_f32 %[a" #r "], %[x" #i "], %[t" #k "], %[a" #r "] op_sel:[0,0,0] op_sel_hi:[1,0,1]\n.endif\n.endif\n"
+#define RD_MUL_SLOT(k, r, i)                                                                                             \
+    ".if (%[en] >> " #k ") & 1\n.if (%[hi] >> " #k ") & 1\n"                                                            \
+    "v_pk_mul_f32 %[d" #r "], %[x" #i "], %[t" #k "] op_sel:[0,1] op_sel_hi:[1,1]\n.else\n"                               \
+    "v_pk_mul_f32 %[d" #r "], %[x" #i "], %[t" #k "] op_sel:[0,0] op_sel_hi:[1,0]\n.endif\n.endif\n"
+#define RD_ADD_SLOT(k, r) ".if (%[en] >> " #k ") & 1\nv_pk_add_f32 %[a" #r "], %[a" #r "], %[d" #r "]\n.endif\n"
+#define RD_ONE_NOP(i) ".if (%[nb] >> " #i ") & 1\ns_nop 0\n.endif\n"
+template <int m0, int K, int D, int R, bool FUSED, bool TWO>
+RD_D void fir_read_res(redio_v2f x0, redio_v2f x1, const FirTapsResident<K> &t, redio_v2f (&a)[R])
+{
+    static_assert(R == 4, "four accumulators per lane");
+    using P = FirReadPlan<m0, K, D, R, TWO>;
+    if constexpr (FUSED)
+        asm volatile(RD_FMA_SLOT(0, 0, 0) RD_FMA_SLOT(1, 1, 0) RD_FMA_SLOT(2, 2, 0) RD_FMA_SLOT(3, 3, 0)
+                     RD_FMA_SLOT(4, 0, 1) RD_FMA_SLOT(5, 1, 1) RD_FMA_SLOT(6, 2, 1) RD_FMA_SLOT(7, 3, 1)
+                     : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3])
+                     : [x0] "v"(x0), [x1] "v"(x1), [t0] "s"(t.p[P::pair(0)]), [t1] "s"(t.p[P::pair(1)]), [t2] "s"(t.p[P::pair(2)]),
+                       [t3] "s"(t.p[P::pair(3)]), [t4] "s"(t.p[P::pair(4)]), [t5] "s"(t.p[P::pair(5)]), [t6] "s"(t.p[P::pair(6)]),
+                       [t7] "s"(t.p[P::pair(7)]), [en] "i"(P::en()), [hi] "i"(P::hi()), [nb] "i"(P::nop_fused()));
+    else {
+        redio_v2f d0, d1, d2, d3;
+        asm volatile(RD_MUL_SLOT(0, 0, 0) RD_MUL_SLOT(1, 1, 0) RD_MUL_SLOT(2, 2, 0) RD_MUL_SLOT(3, 3, 0) RD_ONE_NOP(0)
+                     RD_ADD_SLOT(0, 0) RD_ADD_SLOT(1, 1) RD_ADD_SLOT(2, 2) RD_ADD_SLOT(3, 3)
+                     RD_MUL_SLOT(4, 0, 1) RD_MUL_SLOT(5, 1, 1) RD_MUL_SLOT(6, 2, 1) RD_MUL_SLOT(7, 3, 1) RD_ONE_NOP(1)
+                     RD_ADD_SLOT(4, 0) RD_ADD_SLOT(5, 1) RD_ADD_SLOT(6, 2) RD_ADD_SLOT(7, 3)
+                     : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3]), [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2),
+                       [d3] "=&v"(d3)
+                     : [x0] "v"(x0), [x1] "v"(x1), [t0] "s"(t.p[P::pair(0)]), [t1] "s"(t.p[P::pair(1)]), [t2] "s"(t.p[P::pair(2)]),
+                       [t3] "s"(t.p[P::pair(3)]), [t4] "s"(t.p[P::pair(4)]), [t5] "s"(t.p[P::pair(5)]), [t6] "s"(t.p[P::pair(6)]),
+                       [t7] "s"(t.p[P::pair(7)]), [en] "i"(P::en()), [hi] "i"(P::hi()), [nb] "i"(P::nop_exact()));
+    }
+}
+#undef RD_FMA_SLOT
+#undef RD_MUL_SLOT
+#undef RD_ADD_SLOT
+#undef RD_ONE_NOP
+#else
+// the plain C++ form of the same order (host builds)
+template <int m0, int K, int D, int R, bool FUSED, bool TWO>
+RD_HD void fir_read_res(float2 x0, float2 x1, const FirTapsResident<K> &t, float2 (&a)[R])
+{
+    using P = FirReadPlan<m0, K, D, R, TWO>;
+    for (int k = 0; k < 8; ++k) {
+        if (!P::live(k)) continue;
+        const int el = P::elem(k);
+        const unsigned w = (unsigned)(t.p[el / 2] >> (32 * (el & 1)));
+        float h;
+        __builtin_memcpy(&h, &w, 4);
+        a[k & 3] = mac<FUSED>(k < 4 ? x0 : x1, h, a[k & 3]);
+    }
+}
+#endif
+
+template <int c, int K, int D, int R, bool FUSED, int CH, typename Q, typename Lds4Ptr>
+RD_HD void fir_chunks_res(Lds4Ptr xs4, int base4, const FirTapsResident<K> &t, Q (&q)[2][CH], fir_acc_t (&acc)[R])
+{
+    using G = FirGeomV<K, D, R>;
+    constexpr int NRD = (G::SPAN + 1) / 2; // 16-byte reads in a window
+    constexpr int NCH = (NRD + CH - 1) / CH;
+    if constexpr (c < NCH) {
+        // the next chunk's samples are requested before this chunk's arithmetic; naming this chunk's first sample in an ordered
+        // statement keeps the requests behind the wait for it (a wait by count: LDS reads return in order)
+        RD_PIN_V(q[c & 1][0]);
+        fir_static_for<CH>([&](auto I) {
+            constexpr int i = (c + 1) * CH + I.value;
+#if REDIO_EXP_ABLATE == 1 // timing-only experiment (tools/ablate.sh), never in the product build: half the window reads, as in fir_chunks_v
+            if constexpr (i < NRD && (I.value & 1)) q[(c + 1) & 1][I.value] = q[(c + 1) & 1][I.value - 1];
+            else
+#endif
+            if constexpr (i < NRD) q[(c + 1) & 1][I.value] = xs4[base4 + G::lds_index(2 * i) / 2];
+        });
+        fir_static_for<CH>([&](auto I) {
+            constexpr int m = 2 * (c * CH + I.value);
+            if constexpr (m < G::SPAN) {
+                const Q v = q[c & 1][I.value];
+#if defined(__HIP_DEVICE_COMPILE__)
+                const fir_acc_t x0 = __builtin_shufflevector(v, v, 0, 1), x1 = __builtin_shufflevector(v, v, 2, 3);
+#else
+                const fir_acc_t x0 = make_float2(v.x, v.y), x1 = make_float2(v.z, v.w);
+#endif
+                fir_read_res<m, K, D, R, FUSED, (m + 1 < G::SPAN)>(x0, x1, t, acc);
+            }
+        });
+        RD_SCHED_BARRIER();
+        fir_chunks_res<c + 1, K, D, R, FUSED, CH>(xs4, base4, t, q, acc);
+    }
+}
+
+// fir_lane_v with resident palindromic taps (PRECONDITION: the taps t was loaded from are bit-palindromic); xs4 on the device is a
+// view of 16-byte vectors of four floats
+template <int K, int D, int R, bool FUSED, int CH = 8, typename Lds4Ptr>
+RD_HD void fir_lane_v_res(Lds4Ptr xs4, int lane_slot, const FirTapsResident<K> &t, float2 (&acc)[R])
+{
+    using G = FirGeomV<K, D, R>;
+    using Q = typename std::remove_cv<typename std::remove_reference<decltype(xs4[0])>::type>::type;
+    constexpr int NRD = (G::SPAN + 1) / 2;
+    const int base4 = lane_slot * (G::LANE_STRIDE / 2);
+    Q q[2][CH];
+    fir_static_for<CH>([&](auto I) {
+        constexpr int i = I.value;
+        if constexpr (i < NRD) q[0][i] = xs4[base4 + G::lds_index(2 * i) / 2];
+    });
+    fir_acc_t a[R];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int r = 0; r < R; ++r) a[r] = fir_acc_t{acc[r].x, acc[r].y};
+    static_assert(R == 4, "four accumulators per lane");
+    asm volatile("s_nop 0" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3])); // initialised, and one wait state old, before the first read's statement
+#else
+    for (int r = 0; r < R; ++r) a[r] = acc[r];
+#endif
+    fir_chunks_res<0, K, D, R, FUSED, CH>(xs4, base4, t, q, a);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_nop 0"); // the last packed result, one wait state ahead of the compiler's first reader
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = make_float2(a[r].x, a[r].y);
+#else
+    for (int r = 0; r < R; ++r) acc[r] = a[r];
+#endif
+}
+
 } // namespace redio
 
 // ---------------------------------------------------------------------------------------------

@@ -423,17 +423,19 @@ static hipError_t launch_fir_t(const T *x, long n_in, const float *taps, int K, 
     return hipGetLastError();
 }
 
-hipError_t launch_fir_v4(int K, int D, const float2 *x, const float *taps, float2 *y, long nblocks, bool fused, hipStream_t s); // chain_v4.hip
+hipError_t launch_fir_v4(int K, int D, const float2 *x, const float *taps, bool pal, float2 *y, long nblocks, bool fused, hipStream_t s); // chain_v4.hip
 hipError_t launch_fir_run_real(int K, int D, const float *x, long n_in, const float *taps, float *y, long n_out, bool fused, hipStream_t s, long *done); // fir_run.hip
 
-hipError_t launch_fir(const void *x, long n_in, const float *taps, int K, long D, void *y, long n_out,
+// taps_pal: the plan's taps are bit-palindromic (taps_bit_palindromic, decided at plan creation): launch_fir_v4 then runs the
+// resident-taps kernel, whose precondition that is, else its any-taps twin; the tiled kernels take any taps
+hipError_t launch_fir(const void *x, long n_in, const float *taps, bool taps_pal, int K, long D, void *y, long n_out,
                       bool cplx, bool fused, hipStream_t s)
 {
     // the shapes the chain kernel is built for (127 / 63 taps / 5, 63 taps / 1) run on its data path (wave-private images,
     // halo carried in LDS, register prefetch): whole 1024-output blocks there, the remainder on the tiled kernel
     if (cplx && n_out >= 1024 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0 && !measure_env("REDIO_FIR_NO_V4")) {
         const long nblocks = n_out / 1024;
-        hipError_t e = launch_fir_v4(K, (int)(D <= 5 ? D : 0), (const float2 *)x, taps, (float2 *)y, nblocks, fused, s);
+        hipError_t e = launch_fir_v4(K, (int)(D <= 5 ? D : 0), (const float2 *)x, taps, taps_pal, (float2 *)y, nblocks, fused, s);
         if (e == hipSuccess) {
             const long done = nblocks * 1024;
             if (done == n_out) return hipSuccess;

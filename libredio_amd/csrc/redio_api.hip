@@ -193,6 +193,7 @@ struct redio_fir {
     size_t ntaps, decim;
     unsigned flags;
     float *d_taps;
+    bool taps_pal; // taps_bit_palindromic(taps), decided here once: which form of the chain-form kernels every launch of this plan takes
 };
 
 extern "C" int redio_fir_create(redio_fir **h, const float *taps, size_t ntaps, size_t decim, unsigned flags)
@@ -207,6 +208,7 @@ extern "C" int redio_fir_create(redio_fir **h, const float *taps, size_t ntaps, 
     redio_fir *p = new (std::nothrow) redio_fir();
     if (!p) return REDIO_ERR_NOMEM;
     p->device = dev; p->ntaps = ntaps; p->decim = decim; p->flags = flags; p->d_taps = nullptr;
+    p->taps_pal = taps_bit_palindromic(taps, ntaps);
     // pad the tap table to a multiple of 16 floats so wide scalar loads never run off the end
     size_t padded = (ntaps + 15) & ~(size_t)15;
     std::vector<float> tmp(padded, 0.0f);
@@ -236,7 +238,7 @@ extern "C" int redio_fir_enqueue(redio_fir *h, const void *d_in, size_t n_in, vo
     if (nout == 0) return REDIO_OK;
     if (!d_in || !d_out || d_in == d_out) return REDIO_ERR_ARG;
     RD_TRY(hipSetDevice(h->device));
-    return hip_rc(launch_fir(d_in, (long)n_in, h->d_taps, (int)h->ntaps, (long)h->decim, d_out, (long)nout,
+    return hip_rc(launch_fir(d_in, (long)n_in, h->d_taps, h->taps_pal, (int)h->ntaps, (long)h->decim, d_out, (long)nout,
                              (h->flags & REDIO_FIR_COMPLEX) != 0, (h->flags & REDIO_FIR_FUSED) != 0, (hipStream_t)stream));
 }
 
@@ -608,7 +610,7 @@ extern "C" size_t redio_chain_launch_waves(const redio_chain *h, size_t nblocks)
 extern "C" const char *redio_chain_kernel_name(redio_chain *h)
 {
     if (!redio_chain_is_fused(h)) return nullptr;
-    return chain_kernel_name((int)h->fir->ntaps, (long)h->fir->decim, (h->fir->flags & REDIO_FIR_FUSED) != 0, h->kernel_name, sizeof(h->kernel_name));
+    return chain_kernel_name((int)h->fir->ntaps, (long)h->fir->decim, (h->fir->flags & REDIO_FIR_FUSED) != 0, h->fir->taps_pal, h->kernel_name, sizeof(h->kernel_name));
 }
 // sizes the two-kernel path's intermediate for inputs of up to n_in samples (allocation; may free a smaller one)
 extern "C" int redio_chain_reserve(redio_chain *h, size_t n_in)
@@ -637,7 +639,7 @@ extern "C" int redio_chain_enqueue(redio_chain *h, const void *d_in, size_t n_in
     RD_TRY(hipSetDevice(h->fir->device));
     const bool fused_math = (h->fir->flags & REDIO_FIR_FUSED) != 0;
     if (redio_chain_is_fused(h)) {
-        hipError_t e = launch_chain(h->fft->dev, (const float2 *)d_in, (long)n_in, h->fir->d_taps, (int)h->fir->ntaps,
+        hipError_t e = launch_chain(h->fft->dev, (const float2 *)d_in, (long)n_in, h->fir->d_taps, h->fir->taps_pal, (int)h->fir->ntaps,
                                     (long)h->fir->decim, (float2 *)d_out, (long)nblk, fused_math, (hipStream_t)stream, h->d_stamps, (long)h->stamp_waves);
         if (e != hipErrorNotSupported) return hip_rc(e);
         // e.g. an input pointer the fused kernel cannot take: same results through the two kernels below
@@ -651,7 +653,7 @@ extern "C" int redio_chain_enqueue(redio_chain *h, const void *d_in, size_t n_in
         if (rc) return rc;
     }
     size_t need_in = (ny - 1) * h->fir->decim + h->fir->ntaps; // inputs feeding the kept blocks
-    RD_TRY(launch_fir(d_in, (long)need_in, h->fir->d_taps, (int)h->fir->ntaps, (long)h->fir->decim, h->d_mid, (long)ny,
+    RD_TRY(launch_fir(d_in, (long)need_in, h->fir->d_taps, h->fir->taps_pal, (int)h->fir->ntaps, (long)h->fir->decim, h->d_mid, (long)ny,
                       true, fused_math, (hipStream_t)stream));
     return redio_fft_enqueue(h->fft, h->d_mid, d_out, nblk, stream);
 }
@@ -682,11 +684,11 @@ extern "C" int redio_chain_enqueue_list(redio_chain *h, const redio_msg *msgs, s
         if ((reinterpret_cast<uintptr_t>(msgs[i].in) & 15) != 0) { rest = true; continue; }
         x[k] = (const float2 *)msgs[i].in; out[k] = (float2 *)msgs[i].out; nb[k] = (long)nblk;
         if (++k == REDIO_LIST_MAX) {
-            RD_TRY(launch_chain_list(K, D, x, out, nb, k, h->fir->d_taps, h->fft->dev.tw, fused_math, (hipStream_t)stream));
+            RD_TRY(launch_chain_list(K, D, x, out, nb, k, h->fir->d_taps, h->fir->taps_pal, h->fft->dev.tw, fused_math, (hipStream_t)stream));
             k = 0;
         }
     }
-    if (k) RD_TRY(launch_chain_list(K, D, x, out, nb, k, h->fir->d_taps, h->fft->dev.tw, fused_math, (hipStream_t)stream));
+    if (k) RD_TRY(launch_chain_list(K, D, x, out, nb, k, h->fir->d_taps, h->fir->taps_pal, h->fft->dev.tw, fused_math, (hipStream_t)stream));
     if (rest) // the others through the single call behind them on the same stream (its two-kernel path: the same bits)
         for (size_t i = 0; i < count; ++i)
             if (redio_chain_nblocks(h, msgs[i].n) && (reinterpret_cast<uintptr_t>(msgs[i].in) & 15) != 0)
@@ -720,7 +722,7 @@ extern "C" int redio_chain_enqueue_u8(redio_chain *h, const void *d_bytes, size_
     if (!d_bytes || !d_out || d_bytes == d_out) return REDIO_ERR_ARG;
     RD_TRY(hipSetDevice(h->fir->device));
     if (redio_chain_is_fused(h)) {
-        hipError_t e = launch_chain_u8(h->fft->dev, d_bytes, h->fir->d_taps, (int)h->fir->ntaps, (long)h->fir->decim, (float2 *)d_out, (long)nblk,
+        hipError_t e = launch_chain_u8(h->fft->dev, d_bytes, h->fir->d_taps, h->fir->taps_pal, (int)h->fir->ntaps, (long)h->fir->decim, (float2 *)d_out, (long)nblk,
                                        (h->fir->flags & REDIO_FIR_FUSED) != 0, (hipStream_t)stream);
         if (e != hipErrorNotSupported) return hip_rc(e);
     }

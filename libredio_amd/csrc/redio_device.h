@@ -35,10 +35,13 @@ static inline float4 make_float4(float x, float y, float z, float w) { float4 r 
 typedef float redio_v2f __attribute__((ext_vector_type(2)));
 // names a wave-uniform value and a vector value as inputs of an ordered, memory-clobbering statement
 #define RD_PIN_SV(s, v) asm volatile("" : : "s"(s), "v"(v) : "memory")
+// the same for a vector value alone
+#define RD_PIN_V(v) asm volatile("" : : "v"(v) : "memory")
 #else
 #define RD_SCHED_BARRIER() ((void)0)
 #define RD_PIN_F2(a) ((void)0)
 #define RD_PIN_SV(s, v) ((void)0)
+#define RD_PIN_V(v) ((void)0)
 #endif
 
 namespace redio {

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 #include "fft_core.h"
 
 namespace redio {
@@ -16,8 +17,18 @@ inline const char *measure_env(const char *name) { return getenv(name); }
 inline const char *measure_env(const char *) { return nullptr; }
 #endif
 
+// The FIR and chain plans decide ONCE, at creation, whether their taps are bit-palindromic: taps[i] and taps[K-1-i] the same 32-bit
+// pattern for every i (+0.0 against -0.0, or a NaN against anything else, is not).  The chain-form kernels (chain_v4.hip) keep such
+// taps resident in scalar registers; every launcher that can reach them takes the answer as `taps_pal`.
+inline bool taps_bit_palindromic(const float *taps, size_t K)
+{
+    for (size_t i = 0; i < K / 2; ++i)
+        if (memcmp(&taps[i], &taps[K - 1 - i], sizeof(float)) != 0) return false;
+    return true;
+}
+
 // fir_kernels.hip
-hipError_t launch_fir(const void *x, long n_in, const float *taps, int K, long D, void *y, long n_out,
+hipError_t launch_fir(const void *x, long n_in, const float *taps, bool taps_pal, int K, long D, void *y, long n_out,
                       bool cplx, bool fused, hipStream_t s);
 
 // fft_kernels.hip
@@ -90,17 +101,17 @@ hipError_t launch_ovsave64k(const float2 *x, long hop, float2 *a, float2 *b, con
 
 // chain_kernels.hip : FIR(K taps, decimate D) -> nfft-point forward transform, fused
 bool chain_supported(int K, long D, int nfft);
-hipError_t launch_chain_u8(const FftPlanDev &p, const void *bytes, const float *taps, int K, long D, float2 *out, long nblocks, bool fused,
+hipError_t launch_chain_u8(const FftPlanDev &p, const void *bytes, const float *taps, bool taps_pal, int K, long D, float2 *out, long nblocks, bool fused,
                            hipStream_t s);
-hipError_t launch_chain(const FftPlanDev &p, const float2 *x, long n_in, const float *taps, int K, long D,
+hipError_t launch_chain(const FftPlanDev &p, const float2 *x, long n_in, const float *taps, bool taps_pal, int K, long D,
                         float2 *out, long nblocks, bool fused, hipStream_t s, unsigned long long *dbg = nullptr, long dbg_cap = 0);
 // chain_v4.hip: one launch over a list of count (1 ... REDIO_LIST_MAX) messages of the fused cf32 shapes, 16-byte aligned inputs,
 // nblocks[i] >= 1 each (hipErrorNotSupported: no such shape)
 hipError_t launch_chain_list(int K, long D, const float2 *const *x, float2 *const *out, const long *nblocks, int count, const float *taps,
-                             const float2 *tw, bool fused, hipStream_t s);
+                             bool taps_pal, const float2 *tw, bool fused, hipStream_t s);
 long chain_v4_blocks_per_wave(long nblocks, int WPS = 2); // chain_v4.hip: consecutive blocks one wavefront of the fused kernel owns (WPS wavefronts per SIMD: the chain 2, the FIR alone 3)
 // the fused kernel's name as rocprofv3 prints it (spaces removed), so that a counter file can be tied to the kernel a plan launches
-const char *chain_kernel_name(int K, long D, bool fused_math, char *buf, size_t cap);
+const char *chain_kernel_name(int K, long D, bool fused_math, bool taps_pal, char *buf, size_t cap);
 
 // misc_kernels.hip
 hipError_t launch_synth_iq(float2 *out, uint32_t seed, uint64_t first, long n, hipStream_t s);
