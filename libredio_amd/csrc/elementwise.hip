@@ -68,7 +68,6 @@ __global__ __launch_bounds__(256) void zip_c32_kernel(const float4 *__restrict__
 } // namespace redio
 using namespace redio;
 
-static inline int hip_rc(hipError_t e) { return e == hipSuccess ? REDIO_OK : REDIO_ERR_HIP_BASE - (int)e; }
 
 // 16-byte groups go through the vector loop when all three pointers are 16-byte aligned; the rest
 // (a short tail, or everything when a pointer is not aligned) through the scalar loop of the same launch

@@ -11,6 +11,7 @@
 #include "../../include/redio.h"
 #include "fft_wave.h"
 #include "fft_big_core.h"
+#include "fft_p2.h"
 
 namespace redio {
 
@@ -288,137 +289,6 @@ __global__ __launch_bounds__(256) void fft64_kernel(const float2 *in, float2 *ou
     }
 }
 
-// the one-wave programs (2048 and 4096 points, also as the quarters of 8192 and 16384) read their twiddles from a
-// stage-ordered copy of the table: the stage with sub-length m = NS / (4 fs) starts at m - ML (ML = 1 for 4096 = 4^6,
-// 2 for 2048 = 2 * 4^5) and holds T[(n - 1) m + k] = tw[n k fs] (fftbig_tables_build), so that lanes with neighbouring k
-// read neighbouring entries (in table order the 64 twiddles of a wave's stage-4 load are spread over 16 to 64 cache lines)
-template <int NS, int ML>
-struct TwProgram { const float2 *T; };
-template <int NS, int ML>
-__device__ __forceinline__ float2 tw_get(TwProgram<NS, ML> p, unsigned k, unsigned fs, unsigned n)
-{
-    const unsigned m = NS / (4 * fs);
-    return p.T[(m - ML) + (n - 1) * m + k];
-}
-template <typename TwPtr>
-__device__ __forceinline__ float2 tw_get(TwPtr tw, unsigned k, unsigned fs, unsigned n) { return tw[n * k * fs]; }
-
-// ---- small powers of two and N = 2 * 4^L up to 512 (2, 4, 8, 16, 32, 128, 512; 2048 and 8192 have their own kernels below): compile-time stages in LDS
-// kissfft factors 2 * 4^L as 4, 4, ..., 4, 2 with the radix-2 stage innermost.  One 256-thread workgroup
-// handles 4096 points (8192 for the largest size): max(1, 4096 / N) transforms.  Coalesced load with the
-// digit reversal applied on the LDS side, then register passes over LDS (one pad float2 per 8 keeps the
-// 8-point first pass conflict-free): [radix-2 + radix-4 on 8 consecutive positions], then pairs of radix-4
-// stages on 16 points per thread, a single radix-4 stage if one is left, coalesced store.  Every index is
-// a compile-time shift; butterflies, twiddle indices and stage order are kissfft's (bit-identical).
-template <int LOG2N>
-struct FftP2 {
-    static constexpr int N = 1 << LOG2N, L4 = LOG2N / 2;
-    static constexpr bool ODD = (LOG2N & 1) != 0; // a radix-2 stage innermost
-    static constexpr int E = N >= 4096 ? N : 4096; // points per workgroup
-    static constexpr int T = E / N;                // transforms per workgroup
-    // one pad float2 per 8.  Round 6 modelled every LDS access of the kernels on this image (tools/p2_lds_model.py: 50 % of the LDS-array cycles at 256
-    // points are bank conflicts, SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE measures 47 %) and tried one pad per 16 for 128 points and more, which halves
-    // them in the model -- measured: 256 channels + 0.8 %, 1024 channels - 3.7 %, 512 - 1.5 %, the 128-point transform - 2.3 %
-    // (profiles/r06_p2_lds_padding.txt): the LDS array is not what these kernels wait for.  Kept at 8.
-    __device__ static __forceinline__ int phys(int e) { return e + (e >> 3); }
-    static constexpr int LDS_ELEMS = E + (E >> 3) + 8;
-    // leaf position of input index n: the top bit is the radix-2 digit, base-4 digits reverse onto N/4, N/16, ...
-    __device__ static __forceinline__ int leaf_pos(int n)
-    {
-        int P = ODD ? n >> (2 * L4) : 0;
-#pragma unroll
-        for (int i = 0; i < L4; ++i) P += ((n >> (2 * i)) & 3) * (N >> (2 * i + 2));
-        return P;
-    }
-};
-
-// LB: the workgroup barriers between the stages order LDS traffic only and the caller keeps global requests in flight across them
-// (pfb_p2_kernel): `s_waitcnt lgkmcnt(0); s_barrier` instead of __syncthreads(), whose fence also waits for those requests (vmcnt(0))
-template <bool LB>
-__device__ __forceinline__ void fftp2_barrier()
-{
-    if constexpr (LB) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else __syncthreads();
-}
-template <int LOG2N, bool INV, int M, typename TwPtr, bool LB = false>
-__device__ __forceinline__ void fftp2_rest(float2 *Ls, TwPtr tw, int tid)
-{
-    using F = FftP2<LOG2N>;
-    constexpr int N = F::N, E = F::E;
-    if constexpr (M * 4 <= N / 4) { // two stages: sub-lengths M and 4M on 16 points base + j*M
-        constexpr int FS = N / (4 * M), FS2 = N / (16 * M);
-#pragma unroll 1
-        for (int g = tid; g < E / 16; g += 256) {
-            const int xf = g / (N / 16), gl = g % (N / 16);
-            const int blk = gl / M, kk = gl % M;
-            const int base = xf * N + blk * 16 * M + kk;
-            float2 a[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) a[j] = Ls[F::phys(base + j * M)];
-            const float2 t1 = tw_get(tw, (unsigned)kk, (unsigned)FS, 1), t2 = tw_get(tw, (unsigned)kk, (unsigned)FS, 2), t3 = tw_get(tw, (unsigned)kk, (unsigned)FS, 3);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) bfly4<INV>(a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3], t1, t2, t3);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k2 = kk + u * M;
-                bfly4<INV>(a[u], a[u + 4], a[u + 8], a[u + 12], tw_get(tw, (unsigned)k2, (unsigned)FS2, 1), tw_get(tw, (unsigned)k2, (unsigned)FS2, 2), tw_get(tw, (unsigned)k2, (unsigned)FS2, 3));
-            }
-#pragma unroll
-            for (int j = 0; j < 16; ++j) Ls[F::phys(base + j * M)] = a[j];
-        }
-        fftp2_barrier<LB>();
-        fftp2_rest<LOG2N, INV, 16 * M, TwPtr, LB>(Ls, tw, tid);
-    } else if constexpr (M <= N / 4) { // one stage left
-        constexpr int FS = N / (4 * M);
-#pragma unroll 1
-        for (int g = tid; g < E / 4; g += 256) {
-            const int xf = g / (N / 4), gl = g % (N / 4);
-            const int blk = gl / M, kk = gl % M;
-            const int base = xf * N + blk * 4 * M + kk;
-            float2 a0 = Ls[F::phys(base)], a1 = Ls[F::phys(base + M)], a2 = Ls[F::phys(base + 2 * M)], a3 = Ls[F::phys(base + 3 * M)];
-            bfly4<INV>(a0, a1, a2, a3, tw_get(tw, (unsigned)kk, (unsigned)FS, 1), tw_get(tw, (unsigned)kk, (unsigned)FS, 2), tw_get(tw, (unsigned)kk, (unsigned)FS, 3));
-            Ls[F::phys(base)] = a0; Ls[F::phys(base + M)] = a1; Ls[F::phys(base + 2 * M)] = a2; Ls[F::phys(base + 3 * M)] = a3;
-        }
-        fftp2_barrier<LB>();
-    }
-}
-
-// every stage of the transforms of one workgroup image in LDS (leaf order in, natural order out); ends with a workgroup barrier
-template <int LOG2N, bool INV, bool LB = false>
-__device__ __forceinline__ void fftp2_lds_stages(float2 *Ls, const float2 *__restrict__ tw, const float2 *__restrict__ Tord, int tid)
-{
-    using F = FftP2<LOG2N>;
-    constexpr int N = F::N, E = F::E;
-    if constexpr (!F::ODD) {
-        fftp2_rest<LOG2N, INV, 1, const float2 *, LB>(Ls, tw, tid); // powers of four: stages m = 1, 4, ... straight away
-    } else if constexpr (N == 2) {
-        for (int g = tid; g < E / 2; g += 256) {
-            float2 a0 = Ls[F::phys(2 * g)], a1 = Ls[F::phys(2 * g + 1)];
-            bfly2(a0, a1, tw[0]);
-            Ls[F::phys(2 * g)] = a0; Ls[F::phys(2 * g + 1)] = a1;
-        }
-        fftp2_barrier<LB>();
-    } else {
-        // first pass: radix-2 (m = 1) then radix-4 (m = 2) on 8 consecutive positions
-        constexpr int FS = N / 8;
-        const float2 one = tw[0], w1 = tw[FS], w2 = tw[2 * FS], w3 = tw[3 * FS];
-#pragma unroll 1
-        for (int g = tid; g < E / 8; g += 256) {
-            float2 a[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] = Ls[F::phys(8 * g + j)];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) bfly2(a[2 * q], a[2 * q + 1], one);
-            bfly4<INV>(a[0], a[2], a[4], a[6], one, one, one);
-            bfly4<INV>(a[1], a[3], a[5], a[7], w1, w2, w3);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) Ls[F::phys(8 * g + j)] = a[j];
-        }
-        fftp2_barrier<LB>();
-        if constexpr (LOG2N == 9) fftp2_rest<LOG2N, INV, 8, TwProgram<512, 2>, LB>(Ls, TwProgram<512, 2>{Tord}, tid); // 512: the stage-ordered copy (+6 %; nothing below)
-        else fftp2_rest<LOG2N, INV, 8, const float2 *, LB>(Ls, tw, tid);
-    }
-}
 
 template <int LOG2N, bool INV>
 __global__ __launch_bounds__(256) void fft_p2_kernel(const float2 *in, float2 *out, const float2 *__restrict__ tw, const float2 *__restrict__ Tord,
@@ -462,459 +332,6 @@ static hipError_t launch_fft_p2(const float2 *in, float2 *out, const float2 *tw,
     if (inv) hipLaunchKernelGGL(ki, dim3(grid), dim3(256), lds, s, in, out, tw, Tord, nbatch, in_stride);
     else hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lds, s, in, out, tw, Tord, nbatch, in_stride);
     return hipGetLastError();
-}
-
-// ---- polyphase channelizer with M = 32, 128, 256, 512 or 1024 channels in ONE kernel (round 4): branch filters into the LDS image, then the
-// M-point transform of fft_p2_kernel on the image, then the rows out -- 16 bytes per sample through HBM instead of the 32 of the two-pass
-// form (pfb_api.hip: pfb_branch_kernel + the plan's transform).  v[t][m] = fold_p x[(t + p) M + m] * h[M p + m] (ascending p: dsputils.rs:31),
-// kissfft's M-point forward transform across the branches of each row: the bits of oracle orc_pfb_channelizer.
-// A workgroup iteration is 4096 points.  Up to 256 channels: 16 rows of each of its G = 256 / M row streams, thread (m, g) walks stream g;
-// above: 4096 / M rows of ONE stream, a thread owns M / 256 channels.  A stream is a contiguous range of rows whose P - 1 rows of filter
-// history are carried in registers, so an input row is loaded once (M * 8 contiguous bytes), and the next iteration's rows are requested
-// before this one's arithmetic.
-// PAIR: a thread owns two NEIGHBOURING channels (2 m, 2 m + 1) and loads them with one 16-byte access (M / 2 threads per row, so more
-// row streams per workgroup and 8 rows per iteration); otherwise one channel per thread (or M / 256 channels, 256 apart), 8-byte loads.
-#ifndef REDIO_EXP_PFB_NT
-#define REDIO_EXP_PFB_NT 3 // bit 0: non-temporal row loads, bit 1: non-temporal row stores (pfb_kernels.hip: why)
-#endif
-typedef float p2_v2f __attribute__((ext_vector_type(2)));
-typedef float p2_v4f __attribute__((ext_vector_type(4)));
-template <int LOG2M, int P, bool FUSED, bool PAIR>
-__global__ __launch_bounds__(256) void pfb_p2_kernel(const float2 *__restrict__ x, const float *__restrict__ h, const float2 *__restrict__ tw,
-                                                     const float2 *__restrict__ Tord, float2 *__restrict__ out, long rows, long rps, int ngroups)
-{
-    using F = FftP2<LOG2M>;
-    constexpr int M = F::N;
-    constexpr int NP = PAIR ? (M <= 512 ? 1 : M / 512) : (M <= 256 ? 1 : M / 256); // loads per thread and row
-    constexpr int CPT = PAIR ? 2 * NP : NP, MT = M / CPT, G = 256 / MT, TR = 16 / CPT; // channels per thread, threads per row, streams, rows per iteration
-    static_assert(F::E == 4096 && G * TR * M == 4096 && P >= 2 && P <= 16 && MT <= 256, "shape");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float2 *Ls = reinterpret_cast<float2 *>(smem);
-    const int tid = threadIdx.x, m = tid % MT, g = tid / MT;
-    auto chan = [&](int c) { return PAIR ? 2 * m + (c & 1) + 512 * (c >> 1) : m + 256 * c; }; // channel of slot c
-    const long s0 = (long)blockIdx.x * G;                 // first stream of this workgroup: the one with the most rows
-    const long t0 = (s0 + g) * rps, last_in_row = rows + P - 2;
-    const long rows0 = (s0 * rps + rps < rows ? rps : rows - s0 * rps);
-    const int iters = (int)((rows0 + TR - 1) / TR);       // workgroup-uniform
-    float gt[CPT][P];
-#pragma unroll
-    for (int c = 0; c < CPT; ++c)
-#pragma unroll
-        for (int p = 0; p < P; ++p) gt[c][p] = h[M * p + chan(c)];
-    float2 hist[CPT][P - 1], ra[CPT][TR], rb[CPT][TR];
-    // The transform's twiddles live in LDS for the life of the workgroup (round 5): read from global memory inside the stages they are vector
-    // loads whose wait (vmcnt: loads return in order) also waits for the NEXT iteration's rows requested at the top of this one -- and every
-    // barrier below is an LDS-only barrier for the same reason (__syncthreads() waits for all requests in flight).  M <= 1024 entries.
-    float2 *Ltw = Ls + F::LDS_ELEMS, *Ltord = Ltw + M; // the M-entry table; for 512 channels also the stage-ordered copy (510 entries) behind it
-    for (int i = tid; i < M; i += 256) Ltw[i] = tw[i];
-    if constexpr (LOG2M == 9)
-        for (int i = tid; i < 510; i += 256) Ltord[i] = Tord[i];
-    // rows past the stream's end are clamped (their outputs are never stored); ONE path, never skipped: the compiler can then count the
-    // requests in flight at every use instead of waiting for all of them
-    auto ld_row = [&](long r, float2 *dst /* [CPT], stride given by `step` */, int step) {
-        const float2 *rowp = x + (long)M * (r < last_in_row ? r : last_in_row);
-#pragma unroll
-        for (int q = 0; q < NP; ++q) {
-            if (PAIR) {
-#if REDIO_EXP_PFB_NT & 1
-                const p2_v4f v = __builtin_nontemporal_load(reinterpret_cast<const p2_v4f *>(rowp + 2 * m + 512 * q));
-#else
-                const float4 v = *reinterpret_cast<const float4 *>(rowp + 2 * m + 512 * q);
-#endif
-                dst[(2 * q) * step] = make_float2(v.x, v.y); dst[(2 * q + 1) * step] = make_float2(v.z, v.w);
-            } else {
-#if REDIO_EXP_PFB_NT & 1
-                const p2_v2f v = __builtin_nontemporal_load(reinterpret_cast<const p2_v2f *>(rowp + m + 256 * q));
-                dst[q * step] = make_float2(v.x, v.y);
-#else
-                dst[q * step] = rowp[m + 256 * q];
-#endif
-            }
-        }
-    };
-#pragma unroll
-    for (int p = 0; p < P - 1; ++p) ld_row(t0 + p, &hist[0][p], P - 1);
-#pragma unroll
-    for (int ti = 0; ti < TR; ++ti) ld_row(t0 + P - 1 + ti, &ra[0][ti], TR);
-    const int cpg = M / ngroups;
-    fftp2_barrier<true>(); // the twiddle copy is complete
-    // one iteration: rows tb .. tb + TR - 1 from `cur`, the next iteration's rows requested into `nx` (the loop below is unrolled by two with
-    // the two register sets swapping roles: a copy nx -> cur of a loop-carried array lands behind the iteration's stores and waits for them)
-    auto iteration = [&](int it, float2(&cur)[CPT][TR], float2(&nx)[CPT][TR]) {
-        const long tb = t0 + (long)TR * it;
-#pragma unroll
-        for (int ti = 0; ti < TR; ++ti) ld_row(tb + TR + P - 1 + ti, &nx[0][ti], TR);
-#pragma unroll
-        for (int c = 0; c < CPT; ++c) {
-            const int lp = (TR * g) * M + F::leaf_pos(chan(c));
-#pragma unroll
-            for (int ti = 0; ti < TR; ++ti) { // output row tb + ti: input rows tb + ti + p, p = 0 .. P - 1 (the window is [hist | cur])
-                float2 acc = make_float2(0.f, 0.f);
-#pragma unroll
-                for (int p = 0; p < P; ++p) acc = mac<FUSED>(ti + p < P - 1 ? hist[c][ti + p] : cur[c][ti + p - (P - 1)], gt[c][p], acc);
-                Ls[F::phys(lp + ti * M)] = acc;
-            }
-            float2 hn[P - 1]; // the last P - 1 rows of [hist | cur]
-#pragma unroll
-            for (int p = 0; p < P - 1; ++p) hn[p] = p + TR < P - 1 ? hist[c][p + TR] : cur[c][p + TR - (P - 1)];
-#pragma unroll
-            for (int p = 0; p < P - 1; ++p) hist[c][p] = hn[p];
-        }
-        fftp2_barrier<true>();
-        fftp2_lds_stages<LOG2M, false, true>(Ls, Ltw, Ltord, tid);
-#pragma unroll 2
-        for (int e = 2 * tid; e < 4096; e += 512) { // two neighbouring channels per thread: one 16-byte store
-            const int xf = e / M, n = e % M, gg = xf / TR, ti = xf % TR;
-            const long sbase = (s0 + gg) * rps, row = sbase + (long)TR * it + ti, rend = sbase + rps < rows ? sbase + rps : rows;
-            if (row < rend) {
-                const float2 v0 = Ls[F::phys(e)], v1 = Ls[F::phys(e + 1)];
-                float2 *o16 = ngroups == 1 ? out + row * M + n : out + (long)(n / cpg) * rows * cpg + row * cpg + (n % cpg);
-                if (ngroups == 1 || cpg >= 2) {
-#if REDIO_EXP_PFB_NT & 2
-                    __builtin_nontemporal_store(p2_v4f{v0.x, v0.y, v1.x, v1.y}, reinterpret_cast<p2_v4f *>(o16));
-#else
-                    *reinterpret_cast<float4 *>(o16) = make_float4(v0.x, v0.y, v1.x, v1.y);
-#endif
-                }
-                else { out[(long)n * rows + row] = v0; out[(long)(n + 1) * rows + row] = v1; }
-            }
-        }
-        fftp2_barrier<true>();
-    };
-    for (int it = 0; it < iters; it += 2) {
-        iteration(it, ra, rb);
-        if (it + 1 < iters) iteration(it + 1, rb, ra); // workgroup-uniform
-    }
-}
-
-bool pfb_p2_supported(int nchan, int taps_per_branch)
-{
-    return (nchan == 32 || nchan == 128 || nchan == 256 || nchan == 512 || nchan == 1024) && (taps_per_branch == 4 || taps_per_branch == 8 || taps_per_branch == 16);
-}
-template <int LOG2M, int P, bool PAIR>
-static hipError_t launch_pfb_p2_t(const float2 *x, const float *h, const float2 *tw, const float2 *Tord, float2 *out, long rows, int ngroups, bool fused,
-                                  hipStream_t s)
-{
-    using F = FftP2<LOG2M>;
-    constexpr int M = F::N, NP = PAIR ? (M <= 512 ? 1 : M / 512) : (M <= 256 ? 1 : M / 256), CPT = PAIR ? 2 * NP : NP, G = 256 / (M / CPT), TR = 16 / CPT;
-    if (LOG2M == 9 && !Tord) return hipErrorInvalidValue;
-    // the image + the twiddles the shape needs (M entries; 512 channels: + the 510-entry stage-ordered copy).  Round 5 reserved 1024 entries
-    // for every shape: 45.1 KB, three workgroups per CU where four were launched (advisor, round 5); now 37.2-39 KB up to 256 channels
-    const size_t lds = (size_t)(F::LDS_ELEMS + (LOG2M == 9 ? 1022 : M)) * sizeof(float2);
-    // contiguous row ranges per stream, a multiple of the iteration's rows; about four workgroups per CU -- also for 512 / 1024 channels,
-    // where three are resident: sized for three the launch is 16 % SLOWER (0.866 -> 1.027 ms, profiles/r06_c4gen_ab.txt: the fourth
-    // quarter of the streams is what evens out the tail); at least 64 rows (the P - 1 row prologue)
-    long streams = 4L * num_cus() * G;
-    long rps = (rows + streams - 1) / streams;
-    rps = ((rps + TR - 1) / TR) * TR;
-    if (rps < 64) rps = 64;
-    const long nstreams = (rows + rps - 1) / rps;
-    const unsigned grid = (unsigned)((nstreams + G - 1) / G);
-    if (fused) hipLaunchKernelGGL((pfb_p2_kernel<LOG2M, P, true, PAIR>), dim3(grid), dim3(256), lds, s, x, h, tw, Tord, out, rows, rps, ngroups);
-    else hipLaunchKernelGGL((pfb_p2_kernel<LOG2M, P, false, PAIR>), dim3(grid), dim3(256), lds, s, x, h, tw, Tord, out, rows, rps, ngroups);
-    return hipGetLastError();
-}
-// out: [row][M] (ngroups == 1) or [group][row][M / ngroups]; tw: the M-entry forward table; Tord: the 512-point plan's stage-ordered copy (512 channels only)
-hipError_t launch_pfb_p2(const float2 *x, const float *h, const float2 *tw, const float2 *Tord, float2 *out, long rows, int nchan, int taps_per_branch,
-                         int ngroups, bool fused, hipStream_t s)
-{
-    if (rows <= 0) return hipSuccess;
-    if (!pfb_p2_supported(nchan, taps_per_branch) || ngroups < 1 || nchan % ngroups) return hipErrorNotSupported;
-    if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return hipErrorNotSupported; // 16-byte stores
-    // 16-byte row loads (two neighbouring channels per thread, 16-byte aligned input) where a thread owns several channels anyway: 512 channels
-    // 0.993 -> 0.972 ms, 1024 channels 1.031 -> 0.957 ms per 2^28 samples; up to 256 channels the second channel's window costs more registers
-    // than the wider load saves (256 channels, 16 taps: 0.96 -> 1.57 ms), so those keep one channel per thread (profiles/r04_channelizer_pair_loads_ab.txt).
-    // Measurement builds: REDIO_PFB_NO_PAIR forces the 8-byte form, REDIO_PFB_PAIR the 16-byte form
-    const bool pair = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (nchan >= 512 || measure_env("REDIO_PFB_PAIR")) && !measure_env("REDIO_PFB_NO_PAIR");
-#define REDIO_PFB_P2(L, Q)                                                                                                    \
-    if (nchan == (1 << L) && taps_per_branch == Q)                                                                            \
-        return pair ? launch_pfb_p2_t<L, Q, true>(x, h, tw, Tord, out, rows, ngroups, fused, s) : launch_pfb_p2_t<L, Q, false>(x, h, tw, Tord, out, rows, ngroups, fused, s);
-    REDIO_PFB_P2(5, 4) REDIO_PFB_P2(5, 8) REDIO_PFB_P2(5, 16) REDIO_PFB_P2(7, 4) REDIO_PFB_P2(7, 8) REDIO_PFB_P2(7, 16) REDIO_PFB_P2(8, 4) REDIO_PFB_P2(8, 8) REDIO_PFB_P2(8, 16)
-    REDIO_PFB_P2(9, 4) REDIO_PFB_P2(9, 8) REDIO_PFB_P2(9, 16) REDIO_PFB_P2(10, 4) REDIO_PFB_P2(10, 8) REDIO_PFB_P2(10, 16)
-#undef REDIO_PFB_P2
-    return hipErrorNotSupported;
-}
-
-// ---- every 2^a 3^b 5^c size up to 8192 without a kernel of its own (the sizes kiss_fft_next_fast_size returns; see the
-// dispatch list): the same scheme with a compile-time factor list ----
-// kissfft's factor order (4s, then 2, then 3, 5; fft_plan_stages) evaluated at compile time; radix-4 neighbours run
-// as register pairs -- as do any two neighbours of up to 25 points (3x2, 5x5, 5x2, 5x4 ...) -- and a stage left
-// over as one pass over padded LDS; 4096 / N (at least one) transforms per
-// workgroup.  Butterflies, twiddle indices and stage order are the table-driven kernel's, so results are the same bits.
-template <int N>
-struct FftCt {
-    static constexpr int isqrt() { int r = 0; while ((r + 1) * (r + 1) <= N) ++r; return r; }
-    static constexpr int MAXS = 16;
-    struct List { int n; int p[MAXS], m[MAXS], fs[MAXS]; };
-    static constexpr List make()
-    {
-        List l{};
-        int p = 4, n = N, fstride = 1;
-        const int fsq = isqrt();
-        do {
-            while (n % p) {
-                switch (p) {
-                case 4: p = 2; break;
-                case 2: p = 3; break;
-                default: p += 2; break;
-                }
-                if (p > fsq) p = n;
-            }
-            n /= p;
-            l.p[l.n] = p; l.m[l.n] = n; l.fs[l.n] = fstride;
-            fstride *= p;
-            ++l.n;
-        } while (n > 1);
-        return l;
-    }
-    static constexpr List L = make();
-    static constexpr int T = N >= 4096 ? 1 : 4096 / N;
-    static constexpr int E = T * N;
-    static constexpr int LDS_ELEMS = E + (E >> 3) + 8;
-    __device__ static __forceinline__ int phys(int e) { return e + (e >> 3); }
-    __device__ static __forceinline__ int leaf_pos(int n)
-    {
-        int P = 0;
-#pragma unroll
-        for (int s = 0; s < L.n; ++s) P += ((n / L.fs[s]) % L.p[s]) * L.m[s];
-        return P;
-    }
-    static constexpr bool supported()
-    {
-        for (int s = 0; s < L.n; ++s)
-            if (L.p[s] > 5) return false;
-        return true;
-    }
-    // the stage-ordered twiddle copy of the plan (redio_api.hip): stage s holds T[toff(s) + (n - 1) m + k] = tw[n k fstride],
-    // n = 1 .. p - 1, k < m, so lanes with neighbouring k read neighbouring entries
-    static constexpr int toff(int s)
-    {
-        int o = 0;
-        for (int u = 0; u < s; ++u) o += (L.p[u] - 1) * L.m[u];
-        return o;
-    }
-};
-
-struct CtView { // one transform inside the padded batch image
-    float2 *p; int off;
-    __device__ __forceinline__ float2 &operator[](int i) const { const int e = off + i; return p[e + (e >> 3)]; }
-};
-
-// one radix-P butterfly on P contiguous register values: index k inside the sub-length m, twiddle stride fs
-// (the argument lists of fft_stage_butterfly_gk)
-template <int P, bool INV>
-__device__ __forceinline__ void fftct_bfly(float2 (&a)[P], const float2 *__restrict__ Ts, const float2 *__restrict__ tw, int k, int fs, int m)
-{
-    if constexpr (P == 2) bfly2(a[0], a[1], Ts[k]);
-    else if constexpr (P == 3) bfly3(a[0], a[1], a[2], Ts[k], Ts[m + k], tw[fs * m]);
-    else if constexpr (P == 4) bfly4<INV>(a[0], a[1], a[2], a[3], Ts[k], Ts[m + k], Ts[2 * m + k]);
-    else bfly5(a[0], a[1], a[2], a[3], a[4], Ts[k], Ts[m + k], Ts[2 * m + k], Ts[3 * m + k], tw[fs * m], tw[fs * 2 * m]);
-}
-
-template <int NTH>
-__device__ __forceinline__ void fftct_sync()
-{
-    if constexpr (NTH == 64) wave_lds_fence(); // the image belongs to one wave: LDS operations of a wave complete in order
-    else __syncthreads();
-}
-
-template <int N, bool INV, int S, int NTH = 256, int EPTS = FftCt<N>::E>
-__device__ __forceinline__ void fftct_stages(float2 *Ls, const float2 *__restrict__ tw, const float2 *__restrict__ T, int tid)
-{
-    using F = FftCt<N>;
-    if constexpr (S >= 0) {
-        constexpr int P = F::L.p[S], M = F::L.m[S], FS = F::L.fs[S];
-        constexpr int PO = S >= 1 ? F::L.p[S >= 1 ? S - 1 : 0] : 0; // the next stage out
-        if constexpr (S >= 1 && P * PO <= 25) {
-            // two stages in registers: P*PO points base + j*M; inner radix P (sub-length M), outer radix PO (sub-length P*M)
-            constexpr int FS2 = F::L.fs[S - 1], G = P * PO;
-#pragma unroll 1
-            for (int g = tid; g < EPTS / G; g += NTH) {
-                const int xf = g / (N / G), gl = g % (N / G);
-                const int blk = gl / M, kk = gl % M;
-                const int base = xf * N + blk * G * M + kk;
-                float2 a[G];
-#pragma unroll
-                for (int j = 0; j < G; ++j) a[j] = Ls[F::phys(base + j * M)];
-#pragma unroll
-                for (int q = 0; q < PO; ++q) {
-                    float2 b[P];
-#pragma unroll
-                    for (int i = 0; i < P; ++i) b[i] = a[q * P + i];
-                    fftct_bfly<P, INV>(b, T + F::toff(S), tw, kk, FS, M);
-#pragma unroll
-                    for (int i = 0; i < P; ++i) a[q * P + i] = b[i];
-                }
-#pragma unroll
-                for (int u = 0; u < P; ++u) {
-                    float2 b[PO];
-#pragma unroll
-                    for (int i = 0; i < PO; ++i) b[i] = a[u + P * i];
-                    fftct_bfly<PO, INV>(b, T + F::toff(S - 1), tw, kk + u * M, FS2, P * M);
-#pragma unroll
-                    for (int i = 0; i < PO; ++i) a[u + P * i] = b[i];
-                }
-#pragma unroll
-                for (int j = 0; j < G; ++j) Ls[F::phys(base + j * M)] = a[j];
-            }
-            fftct_sync<NTH>();
-            fftct_stages<N, INV, S - 2, NTH, EPTS>(Ls, tw, T, tid);
-        } else {
-#pragma unroll 1
-            for (int bb = tid; bb < EPTS / P; bb += NTH) {
-                const int xf = bb / (N / P), b = bb % (N / P);
-                const int base = xf * N + (b / M) * P * M + (b % M);
-                float2 a[P];
-#pragma unroll
-                for (int j = 0; j < P; ++j) a[j] = Ls[F::phys(base + j * M)];
-                fftct_bfly<P, INV>(a, T + F::toff(S), tw, b % M, FS, M);
-#pragma unroll
-                for (int j = 0; j < P; ++j) Ls[F::phys(base + j * M)] = a[j];
-            }
-            fftct_sync<NTH>();
-            fftct_stages<N, INV, S - 1, NTH, EPTS>(Ls, tw, T, tid);
-        }
-    }
-}
-
-// 600 ... 1280 points (launch_fft_ct): every wave owns its own transforms (about 1024 points, at least one transform) in its
-// own LDS image, so the passes are separated by compiler fences instead of workgroup barriers
-template <int N>
-struct FftCtW {
-    static constexpr int TW = N >= 1024 ? 1 : 1024 / N;      // transforms per wave
-    static constexpr int EW = TW * N;
-    static constexpr int LDS_W = (EW + (EW >> 3) + 8 + 1) & ~1; // float2 per wave
-};
-template <int N, bool INV>
-__global__ __launch_bounds__(256) void fft_ct_wave_kernel(const float2 *in, float2 *out, const float2 *__restrict__ tw, const float2 *__restrict__ T, long nbatch, long in_stride)
-{
-    using F = FftCt<N>;
-    using W = FftCtW<N>;
-    static_assert(F::supported(), "radices up to 5 only");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float2 *Ls = reinterpret_cast<float2 *>(smem) + w * W::LDS_W;
-    const long b0 = ((long)blockIdx.x * 4 + w) * W::TW;
-    if (b0 >= nbatch) return; // wave-uniform; no workgroup barrier in this kernel
-#pragma unroll 4
-    for (int e = lane; e < W::EW; e += 64) {
-        const int xf = e / N, n = e % N;
-        const long b = (b0 + xf < nbatch) ? b0 + xf : nbatch - 1;
-        Ls[F::phys(xf * N + F::leaf_pos(n))] = in[b * in_stride + n];
-    }
-    wave_lds_fence();
-    fftct_stages<N, INV, F::L.n - 1, 64, W::EW>(Ls, tw, T, lane);
-#pragma unroll 4
-    for (int e = lane; e < W::EW; e += 64) {
-        const int xf = e / N;
-        if (b0 + xf < nbatch) out[(b0 + xf) * N + (e % N)] = Ls[F::phys(e)];
-    }
-}
-
-template <int N, bool INV>
-__global__ __launch_bounds__(256) void fft_ct_kernel(const float2 *in, float2 *out, const float2 *__restrict__ tw, const float2 *__restrict__ T, long nbatch, long in_stride)
-{
-    using F = FftCt<N>;
-    static_assert(F::supported(), "radices up to 5 only");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float2 *Ls = reinterpret_cast<float2 *>(smem);
-    const int tid = threadIdx.x;
-    const long b0 = (long)blockIdx.x * F::T;
-#pragma unroll 4
-    for (int e = tid; e < F::E; e += 256) {
-        const int xf = e / N, n = e % N;
-        const long b = (b0 + xf < nbatch) ? b0 + xf : nbatch - 1;
-        Ls[F::phys(xf * N + F::leaf_pos(n))] = in[b * in_stride + n];
-    }
-    __syncthreads();
-    fftct_stages<N, INV, F::L.n - 1>(Ls, tw, T, tid);
-#pragma unroll 4
-    for (int e = tid; e < F::E; e += 256) {
-        const int xf = e / N;
-        if (b0 + xf < nbatch) out[(b0 + xf) * N + (e % N)] = Ls[F::phys(e)];
-    }
-}
-
-// one transform per NTH-thread workgroup: 1281 ... 2048 points with 128 threads (two waves meet at the barriers instead of
-// four), more than 5120 points with 512 (more waves to hide the LDS round trips of a 50-70 KiB image)
-template <int N, bool INV, int NTH = 128>
-__global__ __launch_bounds__(NTH) void fft_ct_pair_kernel(const float2 *in, float2 *out, const float2 *__restrict__ tw, const float2 *__restrict__ T, long in_stride)
-{
-    using F = FftCt<N>;
-    static_assert(F::supported(), "radices up to 5 only");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float2 *Ls = reinterpret_cast<float2 *>(smem);
-    const int tid = threadIdx.x;
-    const float2 *src = in + (long)blockIdx.x * in_stride;
-#pragma unroll 4
-    for (int n = tid; n < N; n += NTH) Ls[F::phys(F::leaf_pos(n))] = src[n];
-    __syncthreads();
-    fftct_stages<N, INV, F::L.n - 1, NTH, N>(Ls, tw, T, tid);
-    float2 *dst = out + (long)blockIdx.x * N;
-#pragma unroll 4
-    for (int n = tid; n < N; n += NTH) dst[n] = Ls[F::phys(n)];
-}
-
-template <int N>
-static hipError_t launch_fft_ct(const FftPlanDev &p, const float2 *in, float2 *out, long nbatch, long in_stride, bool inv, hipStream_t s)
-{
-    using F = FftCt<N>;
-    // the compile-time list must be the plan's (it is the same algorithm; a mismatch would mean a different build)
-    if (p.nstages != F::L.n || !p.tw_pass) return hipErrorNotSupported;
-    for (int i = 0; i < F::L.n; ++i)
-        if (p.st[i].p != F::L.p[i] || p.st[i].m != F::L.m[i] || p.st[i].fstride != F::L.fs[i]) return hipErrorNotSupported;
-    // measured per size: one transform (or a few) per wave wins from 600 to 1280 points (+2 ... +21 %) and at 384 (+13 %);
-    // smaller sizes leave lanes idle in the 16-point passes, larger ones take too much LDS per workgroup
-    if constexpr ((N >= 600 && N <= 1280) || N == 384) {
-        using W = FftCtW<N>;
-        const size_t ldsw = (size_t)4 * W::LDS_W * sizeof(float2);
-        auto wf = fft_ct_wave_kernel<N, false>;
-        auto wi = fft_ct_wave_kernel<N, true>;
-        if (ldsw > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(inv ? wi : wf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-            if (e != hipSuccess) return e;
-        }
-        const long nwaves = (nbatch + W::TW - 1) / W::TW;
-        const unsigned gridw = (unsigned)((nwaves + 3) / 4);
-        if (inv) hipLaunchKernelGGL(wi, dim3(gridw), dim3(256), ldsw, s, in, out, p.tw, p.tw_pass, nbatch, in_stride);
-        else hipLaunchKernelGGL(wf, dim3(gridw), dim3(256), ldsw, s, in, out, p.tw, p.tw_pass, nbatch, in_stride);
-        return hipGetLastError();
-    } else if constexpr (N > 1280 && N <= 2048) { // measured +9 ... +18 % over two transforms per 256-thread workgroup; slower above 2048
-        const size_t ldsp = (size_t)(N + (N >> 3) + 8) * sizeof(float2);
-        if (inv) hipLaunchKernelGGL((fft_ct_pair_kernel<N, true>), dim3((unsigned)nbatch), dim3(128), ldsp, s, in, out, p.tw, p.tw_pass, in_stride);
-        else hipLaunchKernelGGL((fft_ct_pair_kernel<N, false>), dim3((unsigned)nbatch), dim3(128), ldsp, s, in, out, p.tw, p.tw_pass, in_stride);
-        return hipGetLastError();
-    } else if constexpr (N > 8192) { // 8193 ... 16384 points: the image takes most of a CU's LDS; sixteen waves on it
-        const size_t ldsp = (size_t)(N + (N >> 3) + 8) * sizeof(float2);
-        auto kf10 = fft_ct_pair_kernel<N, false, 1024>;
-        auto ki10 = fft_ct_pair_kernel<N, true, 1024>;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(inv ? ki10 : kf10), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-        if (e != hipSuccess) return e;
-        if (inv) hipLaunchKernelGGL(ki10, dim3((unsigned)nbatch), dim3(1024), ldsp, s, in, out, p.tw, p.tw_pass, in_stride);
-        else hipLaunchKernelGGL(kf10, dim3((unsigned)nbatch), dim3(1024), ldsp, s, in, out, p.tw, p.tw_pass, in_stride);
-        return hipGetLastError();
-    } else if constexpr (N > 5120) { // eight waves on one transform: measured +10 ... +26 % over four (5120 itself is faster with four)
-        const size_t ldsp = (size_t)(N + (N >> 3) + 8) * sizeof(float2);
-        auto kf5 = fft_ct_pair_kernel<N, false, 512>;
-        auto ki5 = fft_ct_pair_kernel<N, true, 512>;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(inv ? ki5 : kf5), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-        if (e != hipSuccess) return e;
-        if (inv) hipLaunchKernelGGL(ki5, dim3((unsigned)nbatch), dim3(512), ldsp, s, in, out, p.tw, p.tw_pass, in_stride);
-        else hipLaunchKernelGGL(kf5, dim3((unsigned)nbatch), dim3(512), ldsp, s, in, out, p.tw, p.tw_pass, in_stride);
-        return hipGetLastError();
-    } else {
-        const size_t lds = (size_t)F::LDS_ELEMS * sizeof(float2);
-        auto kf = fft_ct_kernel<N, false>;
-        auto ki = fft_ct_kernel<N, true>;
-        if (lds > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(inv ? ki : kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        const unsigned grid = (unsigned)((nbatch + F::T - 1) / F::T);
-        if (inv) hipLaunchKernelGGL(ki, dim3(grid), dim3(256), lds, s, in, out, p.tw, p.tw_pass, nbatch, in_stride);
-        else hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lds, s, in, out, p.tw, p.tw_pass, nbatch, in_stride);
-        return hipGetLastError();
-    }
 }
 
 // ---- any N that fits LDS: one workgroup per transform ----------------------------------------
@@ -2906,98 +2323,78 @@ hipError_t launch_fft(const FftPlanDev &p, const float2 *in, float2 *out, long n
     if (in_stride <= 0) in_stride = p.nfft; // consecutive messages; smaller strides give overlapping blocks (overlap-save)
     if (nbatch <= 0) return hipSuccess;
     const bool inv = p.inverse != 0;
-    if (p.nfft == 1024) {
+    FftRouteInfo r = fft_route(p.nfft, p.st, p.nstages);
+    if (r.route == FFT_ROUTE_CT) { // sizes with a compile-time pass list (fft_ct.h)
+        hipError_t e = hipErrorNotSupported;
+        switch (p.nfft) {
+#define REDIO_CT(NN) case NN: e = launch_fft_ct<NN>(p, in, out, nbatch, in_stride, inv, s); break;
+            REDIO_FFT_CT_SIZES(REDIO_CT)
+#undef REDIO_CT
+        default: break;
+        }
+        if (e != hipErrorNotSupported) return e;
+        r = fft_route_unlisted(p.nfft, false); // a plan without the stage-ordered twiddle copy: the table-driven kernels
+    }
+    // the multi-pass and tile-pass programs read the plan's pass-ordered tables; without them, the global-memory stages
+    if ((r.route == FFT_ROUTE_MULTIPASS || r.route == FFT_ROUTE_TILE_PASSES) && !p.tw_pass) r.route = FFT_ROUTE_GLOBAL;
+    // the C-ABI layer reads the same two facts from the route and stages such calls BEFORE it launches
+    if ((in == out && !r.in_place_ok) || (r.needs_work && !work)) return hipErrorInvalidValue;
+    switch (r.route) {
+    case FFT_ROUTE_WAVE1K: {
         const size_t lds = 4 * FFT1K_LDS * sizeof(float2);
         const unsigned grid = (unsigned)((nbatch + 4 * FFT1K_RUN - 1) / (4 * FFT1K_RUN));
         if (inv) hipLaunchKernelGGL(fft1k_wave_kernel<true>, dim3(grid), dim3(256), lds, s, in, out, p.tw, nbatch, in_stride);
         else hipLaunchKernelGGL(fft1k_wave_kernel<false>, dim3(grid), dim3(256), lds, s, in, out, p.tw, nbatch, in_stride);
         return hipGetLastError();
     }
-    switch (p.nfft) { // 2 * 4^L, and the two powers of four below 64
-    case 2: return launch_fft_p2<1>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
-    case 4: return launch_fft_p2<2>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
-    case 8: return launch_fft_p2<3>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
-    case 16: return launch_fft_p2<4>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
-    case 32: return launch_fft_p2<5>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
-    case 128: return launch_fft_p2<7>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
-    case 512: return launch_fft_p2<9>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
-    case 2048: {
-        const unsigned grid = (unsigned)((nbatch + 3) / 4);
-        if (!p.tw_pass) return hipErrorInvalidValue;
-        if (inv) hipLaunchKernelGGL(fft2k_wave_kernel<true>, dim3(grid), dim3(256), 0, s, in, out, p.tw_pass, nbatch, in_stride);
-        else hipLaunchKernelGGL(fft2k_wave_kernel<false>, dim3(grid), dim3(256), 0, s, in, out, p.tw_pass, nbatch, in_stride);
-        return hipGetLastError();
-    }
-    case 8192:
-        if (!p.tw_pass) return hipErrorInvalidValue;
-        if (inv) hipLaunchKernelGGL(fft8k_wave_kernel<true>, dim3((unsigned)nbatch), dim3(256), 0, s, in, out, p.tw, p.tw_pass, in_stride);
-        else hipLaunchKernelGGL(fft8k_wave_kernel<false>, dim3((unsigned)nbatch), dim3(256), 0, s, in, out, p.tw, p.tw_pass, in_stride);
-        return hipGetLastError();
-    default: break;
-    }
-    if (p.nfft == 64) {
+    case FFT_ROUTE_P2:
+        switch (p.nfft) { // 2 * 4^L, and the two powers of four below 64
+        case 2: return launch_fft_p2<1>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
+        case 4: return launch_fft_p2<2>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
+        case 8: return launch_fft_p2<3>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
+        case 16: return launch_fft_p2<4>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
+        case 32: return launch_fft_p2<5>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
+        case 128: return launch_fft_p2<7>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
+        case 512: return launch_fft_p2<9>(in, out, p.tw, p.tw_pass, nbatch, in_stride, inv, s);
+        default: return hipErrorNotSupported;
+        }
+    case FFT_ROUTE_64: {
         const size_t lds = 4 * FFT1K_LDS * sizeof(float2);
         const unsigned grid = (unsigned)((nbatch + 63) / 64);
         if (inv) hipLaunchKernelGGL(fft64_kernel<true>, dim3(grid), dim3(256), lds, s, in, out, p.tw, nbatch, in_stride);
         else hipLaunchKernelGGL(fft64_kernel<false>, dim3(grid), dim3(256), lds, s, in, out, p.tw, nbatch, in_stride);
         return hipGetLastError();
     }
-    if (p.nfft == 256) {
+    case FFT_ROUTE_256: {
         const size_t lds = 4 * FFT1K_LDS * sizeof(float2);
         const unsigned grid = (unsigned)((nbatch + 15) / 16);
         if (inv) hipLaunchKernelGGL(fft256_kernel<true>, dim3(grid), dim3(256), lds, s, in, out, p.tw, nbatch, in_stride);
         else hipLaunchKernelGGL(fft256_kernel<false>, dim3(grid), dim3(256), lds, s, in, out, p.tw, nbatch, in_stride);
         return hipGetLastError();
     }
-    if (p.nfft == 4096) {
+    case FFT_ROUTE_ONE_WAVE: {
         const unsigned grid = (unsigned)((nbatch + 3) / 4);
         if (!p.tw_pass) return hipErrorInvalidValue;
-        if (inv) hipLaunchKernelGGL(fft4k_wave_kernel<true>, dim3(grid), dim3(256), 0, s, in, out, p.tw_pass, nbatch, in_stride);
-        else hipLaunchKernelGGL(fft4k_wave_kernel<false>, dim3(grid), dim3(256), 0, s, in, out, p.tw_pass, nbatch, in_stride);
-        return hipGetLastError();
-    }
-    if (p.nfft == 16384) {
-        if (!p.tw_pass) return hipErrorInvalidValue;
-        if (inv) hipLaunchKernelGGL(fft16k_wave_kernel<true>, dim3((unsigned)nbatch), dim3(256), 0, s, in, out, p.tw, p.tw_pass, in_stride);
-        else hipLaunchKernelGGL(fft16k_wave_kernel<false>, dim3((unsigned)nbatch), dim3(256), 0, s, in, out, p.tw, p.tw_pass, in_stride);
-        return hipGetLastError();
-    }
-    {   // sizes with a compile-time pass list
-        hipError_t e = hipErrorNotSupported;
-        switch (p.nfft) {
-#define REDIO_CT(NN) case NN: e = launch_fft_ct<NN>(p, in, out, nbatch, in_stride, inv, s); break;
-            REDIO_CT(6) REDIO_CT(9) REDIO_CT(10) REDIO_CT(12) REDIO_CT(15) REDIO_CT(18) REDIO_CT(20) REDIO_CT(24)
-            REDIO_CT(25) REDIO_CT(27) REDIO_CT(30) REDIO_CT(36) REDIO_CT(40) REDIO_CT(45) REDIO_CT(48) REDIO_CT(50)
-            REDIO_CT(54) REDIO_CT(60) REDIO_CT(72) REDIO_CT(75) REDIO_CT(80) REDIO_CT(81) REDIO_CT(90) REDIO_CT(96)
-            REDIO_CT(100) REDIO_CT(108) REDIO_CT(120) REDIO_CT(125) REDIO_CT(135) REDIO_CT(144) REDIO_CT(150) REDIO_CT(160)
-            REDIO_CT(162) REDIO_CT(180) REDIO_CT(192) REDIO_CT(200) REDIO_CT(216) REDIO_CT(225) REDIO_CT(240) REDIO_CT(243)
-            REDIO_CT(250) REDIO_CT(270) REDIO_CT(288) REDIO_CT(300) REDIO_CT(320) REDIO_CT(324) REDIO_CT(360) REDIO_CT(375)
-            REDIO_CT(384) REDIO_CT(400) REDIO_CT(405) REDIO_CT(432) REDIO_CT(450) REDIO_CT(480) REDIO_CT(486) REDIO_CT(500)
-            REDIO_CT(540) REDIO_CT(576) REDIO_CT(600) REDIO_CT(625) REDIO_CT(640) REDIO_CT(648) REDIO_CT(675) REDIO_CT(720)
-            REDIO_CT(729) REDIO_CT(750) REDIO_CT(768) REDIO_CT(800) REDIO_CT(810) REDIO_CT(864) REDIO_CT(900) REDIO_CT(960)
-            REDIO_CT(972) REDIO_CT(1000) REDIO_CT(1080) REDIO_CT(1125) REDIO_CT(1152) REDIO_CT(1200) REDIO_CT(1215) REDIO_CT(1250)
-            REDIO_CT(1280) REDIO_CT(1296) REDIO_CT(1350) REDIO_CT(1440) REDIO_CT(1458) REDIO_CT(1500) REDIO_CT(1536) REDIO_CT(1600)
-            REDIO_CT(1620) REDIO_CT(1728) REDIO_CT(1800) REDIO_CT(1875) REDIO_CT(1920) REDIO_CT(1944) REDIO_CT(2000) REDIO_CT(2025)
-            REDIO_CT(2160) REDIO_CT(2187) REDIO_CT(2250) REDIO_CT(2304) REDIO_CT(2400) REDIO_CT(2430) REDIO_CT(2500) REDIO_CT(2560)
-            REDIO_CT(2592) REDIO_CT(2700) REDIO_CT(2880) REDIO_CT(2916) REDIO_CT(3000) REDIO_CT(3072) REDIO_CT(3125) REDIO_CT(3200)
-            REDIO_CT(3240) REDIO_CT(3375) REDIO_CT(3456) REDIO_CT(3600) REDIO_CT(3645) REDIO_CT(3750) REDIO_CT(3840) REDIO_CT(3888)
-            REDIO_CT(4000) REDIO_CT(4050) REDIO_CT(4320) REDIO_CT(4374) REDIO_CT(4500) REDIO_CT(4608) REDIO_CT(4800) REDIO_CT(4860)
-            REDIO_CT(5000) REDIO_CT(5120) REDIO_CT(5184) REDIO_CT(5400) REDIO_CT(5625) REDIO_CT(5760) REDIO_CT(5832) REDIO_CT(6000)
-            REDIO_CT(6075) REDIO_CT(6144) REDIO_CT(6250) REDIO_CT(6400) REDIO_CT(6480) REDIO_CT(6561) REDIO_CT(6750) REDIO_CT(6912)
-            REDIO_CT(7200) REDIO_CT(7290) REDIO_CT(7500) REDIO_CT(7680) REDIO_CT(7776) REDIO_CT(8000) REDIO_CT(8100)
-            REDIO_CT(8640) REDIO_CT(8748) REDIO_CT(9000) REDIO_CT(9216) REDIO_CT(9375) REDIO_CT(9600) REDIO_CT(9720) REDIO_CT(10000)
-            REDIO_CT(10125) REDIO_CT(10240) REDIO_CT(10368) REDIO_CT(10800) REDIO_CT(10935) REDIO_CT(11250) REDIO_CT(11520) REDIO_CT(11664)
-            REDIO_CT(12000) REDIO_CT(12150) REDIO_CT(12288) REDIO_CT(12500) REDIO_CT(12800) REDIO_CT(12960) REDIO_CT(13122) REDIO_CT(13500)
-            REDIO_CT(13824) REDIO_CT(14400) REDIO_CT(14580) REDIO_CT(15000) REDIO_CT(15360) REDIO_CT(15552) REDIO_CT(15625) REDIO_CT(16000)
-            REDIO_CT(16200)
-#undef REDIO_CT
-        default: break;
+        if (p.nfft == 2048) {
+            if (inv) hipLaunchKernelGGL(fft2k_wave_kernel<true>, dim3(grid), dim3(256), 0, s, in, out, p.tw_pass, nbatch, in_stride);
+            else hipLaunchKernelGGL(fft2k_wave_kernel<false>, dim3(grid), dim3(256), 0, s, in, out, p.tw_pass, nbatch, in_stride);
+        } else {
+            if (inv) hipLaunchKernelGGL(fft4k_wave_kernel<true>, dim3(grid), dim3(256), 0, s, in, out, p.tw_pass, nbatch, in_stride);
+            else hipLaunchKernelGGL(fft4k_wave_kernel<false>, dim3(grid), dim3(256), 0, s, in, out, p.tw_pass, nbatch, in_stride);
         }
-        if (e != hipErrorNotSupported) return e;
+        return hipGetLastError();
     }
-    bool generic = false;
-    for (int i = 0; i < p.nstages; ++i) generic |= p.st[i].p > 5;
-    if (!generic && p.nfft <= 8192) {
+    case FFT_ROUTE_FOUR_WAVE:
+        if (!p.tw_pass) return hipErrorInvalidValue;
+        if (p.nfft == 8192) {
+            if (inv) hipLaunchKernelGGL(fft8k_wave_kernel<true>, dim3((unsigned)nbatch), dim3(256), 0, s, in, out, p.tw, p.tw_pass, in_stride);
+            else hipLaunchKernelGGL(fft8k_wave_kernel<false>, dim3((unsigned)nbatch), dim3(256), 0, s, in, out, p.tw, p.tw_pass, in_stride);
+        } else {
+            if (inv) hipLaunchKernelGGL(fft16k_wave_kernel<true>, dim3((unsigned)nbatch), dim3(256), 0, s, in, out, p.tw, p.tw_pass, in_stride);
+            else hipLaunchKernelGGL(fft16k_wave_kernel<false>, dim3((unsigned)nbatch), dim3(256), 0, s, in, out, p.tw, p.tw_pass, in_stride);
+        }
+        return hipGetLastError();
+    case FFT_ROUTE_LDS_BATCHED: {
         int T = 2048 / p.nfft;
         if (T < 1) T = 1;
         if (T > nbatch) T = (int)nbatch;
@@ -3015,8 +2412,10 @@ hipError_t launch_fft(const FftPlanDev &p, const float2 *in, float2 *out, long n
         else hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lds, s, p, in, out, nbatch, in_stride, T, G);
         return hipGetLastError();
     }
-    const size_t lds = (size_t)p.nfft * sizeof(float2) * (generic ? 2 : 1);
-    if (lds <= 128 * 1024) {
+    case FFT_ROUTE_LDS: {
+        bool generic = false;
+        for (int i = 0; i < p.nstages; ++i) generic |= p.st[i].p > 5;
+        const size_t lds = (size_t)p.nfft * sizeof(float2) * (generic ? 2 : 1);
         auto kf = fft_lds_kernel<false>;
         auto ki = fft_lds_kernel<true>;
         if (lds > 48 * 1024) {
@@ -3029,20 +2428,18 @@ hipError_t launch_fft(const FftPlanDev &p, const float2 *in, float2 *out, long n
         else hipLaunchKernelGGL(kf, dim3((unsigned)nbatch), dim3(nt), lds, s, p, in, out, in_stride);
         return hipGetLastError();
     }
-    if (fftbig_size(p.nfft) && p.tw_pass) { // 32768, 65536, 131072 ... 16777216 (16384 above)
-        if (in == out) return hipErrorNotSupported; // the first pass is a global transposition: the C-ABI layer stages in-place calls
+    case FFT_ROUTE_MULTIPASS: { // 32768, 65536, 131072 ... 16777216 (16384 above)
         const int lgN = __builtin_ctz((unsigned)p.nfft);
         return inv ? launch_fftbig<true>(in, out, p.tw, p.tw_pass, nbatch, in_stride, lgN, s)
                    : launch_fftbig<false>(in, out, p.tw, p.tw_pass, nbatch, in_stride, lgN, s);
     }
-    if (!generic && p.nfft > 16384 && p.tw_pass) { // radix-2/3/4/5 sizes that are not powers of two: one pass per group of stages
-        if (in == out) return hipErrorNotSupported; // the first pass is a global transposition: the C-ABI layer stages in-place calls
+    case FFT_ROUTE_TILE_PASSES: // radix-2/3/4/5 sizes that are not powers of two: one pass per group of stages
         if (nbatch * (long)((p.nfft + 15) / 16) > 0x7fffffffl) return hipErrorInvalidValue;
         return inv ? launch_fft_tile_passes<true>(p, in, out, nbatch, in_stride, s) : launch_fft_tile_passes<false>(p, in, out, nbatch, in_stride, s);
+    case FFT_ROUTE_GLOBAL: break;
+    default: return hipErrorNotSupported;
     }
-    // global-memory stages.  The C-ABI layer routes in-place calls through a temporary and supplies `work`
-    // (nbatch * nfft elements) when a generic-radix stage needs an out-of-place step.
-    if (in == out || (generic && !work)) return hipErrorNotSupported;
+    // global-memory stages; `work` (nbatch * nfft elements) where a generic-radix stage needs an out-of-place step
     const long total = nbatch * p.nfft;
     const unsigned egrid = (unsigned)((total + 255) / 256);
     float2 *cur = out, *other = work;

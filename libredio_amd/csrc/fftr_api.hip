@@ -7,12 +7,6 @@
 
 using namespace redio;
 
-static inline int hip_rc(hipError_t e) { return e == hipSuccess ? REDIO_OK : REDIO_ERR_HIP_BASE - (int)e; }
-#define RD_TRY(expr)                             \
-    do {                                         \
-        hipError_t _e = (expr);                  \
-        if (_e != hipSuccess) return hip_rc(_e); \
-    } while (0)
 
 struct redio_fftr {
     int device;
@@ -39,12 +33,7 @@ extern "C" int redio_fftr_create(redio_fftr **h, int nfft, int inverse)
     p->fused = nfft == 2 * FFTR1K_M; p->cplx_stages = false; p->cplx = nullptr; p->d_stw = nullptr; p->d_scratch = nullptr; p->scratch_rows = 0;
     int rc = REDIO_OK;
     if (p->M > 1) rc = redio_fft_create(&p->cplx, p->M, p->inverse);
-    if (rc == REDIO_OK && p->cplx) {
-        const FftPlanDev *d = redio_fft_plan_dev(p->cplx);
-        bool generic = false;
-        for (int i = 0; i < d->nstages; ++i) generic |= d->st[i].p > 5;
-        p->cplx_stages = generic && (size_t)p->M * sizeof(float2) * 2 > 128 * 1024; // launch_fft: the global-memory stages need `work`
-    }
+    if (rc == REDIO_OK && p->cplx) p->cplx_stages = redio_fft_stages(p->cplx, false); // never in place: the scratch is on one side
     if (rc == REDIO_OK) {
         std::vector<float2> stw((size_t)(p->M / 2 > 0 ? p->M / 2 : 1), make_float2(0.f, 0.f));
         fftr_super_tw(p->M, p->inverse, stw.data());
@@ -78,15 +67,10 @@ extern "C" int redio_fftr_reserve(redio_fftr *h, size_t nbatch)
 {
     if (!h) return REDIO_ERR_ARG;
     if (h->fused || h->M == 1) return REDIO_OK; // no scratch on these paths
-    RD_TRY(hipSetDevice(h->device));
+    REDIO_TRY(hipSetDevice(h->device));
     if (h->cplx_stages)
         if (int rc = redio_fft_reserve(h->cplx, nbatch)) return rc;
-    if (nbatch <= h->scratch_rows) return REDIO_OK;
-    if (int rc = redio_free(h->d_scratch)) return rc;
-    h->d_scratch = nullptr; h->scratch_rows = 0;
-    if (int rc = redio_malloc(&h->d_scratch, nbatch * (size_t)h->M * sizeof(float2))) return rc;
-    h->scratch_rows = nbatch;
-    return REDIO_OK;
+    return scratch_grow(&h->d_scratch, &h->scratch_rows, nbatch, (size_t)h->M * sizeof(float2));
 }
 
 extern "C" int redio_fftr_enqueue_strided(redio_fftr *h, const void *d_in, void *d_out, size_t nbatch, long in_stride, long out_stride, void *stream)
@@ -100,15 +84,14 @@ extern "C" int redio_fftr_enqueue_strided(redio_fftr *h, const void *d_in, void 
     if (in_stride <= 0 || out_stride < out_row || (real_stride & 1)) return REDIO_ERR_ARG;
     if (((uintptr_t)d_in & 7) || ((uintptr_t)d_out & 7)) return REDIO_ERR_ARG; // both sides are read and written as cf32
     hipStream_t st = (hipStream_t)stream;
-    RD_TRY(hipSetDevice(h->device));
+    REDIO_TRY(hipSetDevice(h->device));
     if (h->fused)
         return hip_rc(launch_fftr1k(h->inverse != 0, d_in, d_out, redio_fft_twiddles_dev(h->cplx), h->d_stw, (long)nbatch, in_stride, out_stride, st));
     if (M == 1) // Z = the row itself
         return hip_rc(launch_fftr_split(h->inverse != 0, (const float2 *)d_in, h->inverse ? in_stride : in_stride / 2, (float2 *)d_out,
                                         h->inverse ? out_stride / 2 : out_stride, h->d_stw, M, (long)nbatch, st));
     if (nbatch > h->scratch_rows) { // grown on first use unless redio_fftr_reserve() sized it; never during graph capture
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return REDIO_ERR_NOT_RESERVED;
+        if (stream_capturing(st)) return REDIO_ERR_NOT_RESERVED;
         if (int rc = redio_fftr_reserve(h, nbatch)) return rc;
     }
     float2 *scratch = (float2 *)h->d_scratch;
@@ -116,7 +99,7 @@ extern "C" int redio_fftr_enqueue_strided(redio_fftr *h, const void *d_in, void 
         if (int rc = redio_fft_enqueue_strided(h->cplx, d_in, scratch, nbatch, in_stride / 2, stream)) return rc;
         return hip_rc(launch_fftr_split(false, scratch, M, (float2 *)d_out, out_stride, h->d_stw, M, (long)nbatch, st));
     }
-    RD_TRY(launch_fftr_split(true, (const float2 *)d_in, in_stride, scratch, M, h->d_stw, M, (long)nbatch, st));
+    REDIO_TRY(launch_fftr_split(true, (const float2 *)d_in, in_stride, scratch, M, h->d_stw, M, (long)nbatch, st));
     if (out_stride == N) return redio_fft_enqueue(h->cplx, scratch, d_out, nbatch, stream);
     for (size_t b = 0; b < nbatch; ++b) // the complex plan writes packed rows: spaced-out rows go one launch each
         if (int rc = redio_fft_enqueue(h->cplx, scratch + b * (size_t)M, (float *)d_out + b * (size_t)out_stride, 1, stream)) return rc;

@@ -242,8 +242,6 @@ static unsigned grid_for(long n, int per = 256, long cap = 16384)
 } // namespace redio
 using namespace redio;
 
-static inline int hip_rc(hipError_t e) { return e == hipSuccess ? REDIO_OK : REDIO_ERR_HIP_BASE - (int)e; }
-#define IN_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return hip_rc(_e); } while (0)
 
 extern "C" int redio_data_to_samples(const void *d_bytes, size_t nbytes, void *d_out, void *stream)
 {
@@ -305,7 +303,7 @@ extern "C" int redio_discretize(const void *d_in, size_t n, void *d_out_u8, void
     if (n == 0) return REDIO_OK;
     if (!d_in || !d_out_u8 || !d_scratch_u32) return REDIO_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    IN_TRY(hipMemsetAsync(d_scratch_u32, 0, sizeof(unsigned), st)); // fold starts at 0.0
+    REDIO_TRY(hipMemsetAsync(d_scratch_u32, 0, sizeof(unsigned), st)); // fold starts at 0.0
     hipLaunchKernelGGL(max_kernel, dim3(grid_for((long)n, 1024) > 2048 ? 2048 : grid_for((long)n, 1024)), dim3(256), 0, st, (const float *)d_in, (long)n, (unsigned *)d_scratch_u32);
     hipLaunchKernelGGL(slice_kernel, dim3(grid_for((long)n / 4, 1024, 0xffffffL)), dim3(256), 0, st, (const float *)d_in, (long)n, (const unsigned *)d_scratch_u32,
                        (uint8_t *)d_out_u8);
@@ -357,9 +355,9 @@ static int trig_reserve(redio_trigger *t, size_t need, hipStream_t st)
     size_t nc = t->cap;
     while (nc < need) nc *= 2;
     float *nb = nullptr;
-    IN_TRY(hipMalloc((void **)&nb, nc * sizeof(float)));
-    IN_TRY(hipMemcpyAsync(nb, t->d_buf, t->len * sizeof(float), hipMemcpyDeviceToDevice, st));
-    IN_TRY(hipStreamSynchronize(st));
+    REDIO_TRY(hipMalloc((void **)&nb, nc * sizeof(float)));
+    REDIO_TRY(hipMemcpyAsync(nb, t->d_buf, t->len * sizeof(float), hipMemcpyDeviceToDevice, st));
+    REDIO_TRY(hipStreamSynchronize(st));
     hipFree(t->d_buf);
     t->d_buf = nb;
     t->cap = nc;
@@ -377,18 +375,18 @@ extern "C" int redio_trigger_feed(redio_trigger *t, const void *d_blocks, size_t
     if (!t) return REDIO_ERR_ARG;
     if (nblocks == 0) return REDIO_OK;
     if (!d_blocks || block == 0) return REDIO_ERR_ARG;
-    IN_TRY(hipSetDevice(t->device));
+    REDIO_TRY(hipSetDevice(t->device));
     hipStream_t st = (hipStream_t)stream;
     if (nblocks > t->sums_cap) {
         hipFree(t->d_sums); t->d_sums = nullptr; t->sums_cap = 0;
-        IN_TRY(hipMalloc((void **)&t->d_sums, nblocks * sizeof(float)));
+        REDIO_TRY(hipMalloc((void **)&t->d_sums, nblocks * sizeof(float)));
         t->sums_cap = nblocks;
     }
     int rc = redio_block_sums(d_blocks, nblocks, block, t->d_sums, st);
     if (rc) return rc;
     std::vector<float> s(nblocks);
-    IN_TRY(hipMemcpyAsync(s.data(), t->d_sums, nblocks * sizeof(float), hipMemcpyDeviceToHost, st));
-    IN_TRY(hipStreamSynchronize(st));
+    REDIO_TRY(hipMemcpyAsync(s.data(), t->d_sums, nblocks * sizeof(float), hipMemcpyDeviceToHost, st));
+    REDIO_TRY(hipStreamSynchronize(st));
 
     const long trigger_duration = 50;  // :41
     const size_t block_size = 512;     // :38 (only in the OOM bound)
@@ -416,15 +414,15 @@ extern "C" int redio_trigger_feed(redio_trigger *t, const void *d_blocks, size_t
         if (src.empty()) return REDIO_OK;
         if (src.size() > t->seg_cap) {
             hipFree(t->d_src); hipFree(t->d_dst); t->d_src = t->d_dst = nullptr; t->seg_cap = 0;
-            IN_TRY(hipMalloc((void **)&t->d_src, src.size() * 2 * sizeof(long)));
-            IN_TRY(hipMalloc((void **)&t->d_dst, src.size() * 2 * sizeof(long)));
+            REDIO_TRY(hipMalloc((void **)&t->d_src, src.size() * 2 * sizeof(long)));
+            REDIO_TRY(hipMalloc((void **)&t->d_dst, src.size() * 2 * sizeof(long)));
             t->seg_cap = src.size() * 2;
         }
-        IN_TRY(hipMemcpyAsync(t->d_src, src.data(), src.size() * sizeof(long), hipMemcpyHostToDevice, st));
-        IN_TRY(hipMemcpyAsync(t->d_dst, dst.data(), dst.size() * sizeof(long), hipMemcpyHostToDevice, st));
+        REDIO_TRY(hipMemcpyAsync(t->d_src, src.data(), src.size() * sizeof(long), hipMemcpyHostToDevice, st));
+        REDIO_TRY(hipMemcpyAsync(t->d_dst, dst.data(), dst.size() * sizeof(long), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(gather_blocks_kernel, dim3((unsigned)src.size()), dim3(256), 0, st, (const float *)d_blocks, t->d_src, t->d_dst,
                            (int)block, t->d_buf);
-        IN_TRY(hipStreamSynchronize(st)); // src/dst are reused
+        REDIO_TRY(hipStreamSynchronize(st)); // src/dst are reused
         src.clear(); dst.clear();
         return REDIO_OK;
     };
@@ -432,7 +430,7 @@ extern "C" int redio_trigger_feed(redio_trigger *t, const void *d_blocks, size_t
         t->trigger -= 1;                                              // :46
         if (t->len > 1000 * (size_t)trigger_duration * block_size) {  // :52-54
             rc = flush(); if (rc) return rc;
-            IN_TRY(hipMemsetAsync(t->d_buf, 0, sizeof(float), st));
+            REDIO_TRY(hipMemsetAsync(t->d_buf, 0, sizeof(float), st));
             t->len = 1;
         }
         if (t->threshold == 0.0f) t->threshold = s[b];                // :57-59
@@ -448,7 +446,7 @@ extern "C" int redio_trigger_feed(redio_trigger *t, const void *d_blocks, size_t
         }
         if (t->trigger == 0) {                                         // :78-81
             rc = flush(); if (rc) return rc;
-            if (t->len) IN_TRY(hipMemcpyAsync((float *)d_out + total, t->d_buf, t->len * sizeof(float), hipMemcpyDeviceToDevice, st));
+            if (t->len) REDIO_TRY(hipMemcpyAsync((float *)d_out + total, t->d_buf, t->len * sizeof(float), hipMemcpyDeviceToDevice, st));
             lens[nemit] = t->len; // fits: checked by the dry run above
             total += t->len;
             ++nemit;
@@ -457,7 +455,7 @@ extern "C" int redio_trigger_feed(redio_trigger *t, const void *d_blocks, size_t
     }
     rc = flush();
     if (rc) return rc;
-    IN_TRY(hipStreamSynchronize(st));
+    REDIO_TRY(hipStreamSynchronize(st));
     if (nemit_out) *nemit_out = nemit;
     if (total_out) *total_out = total;
     return REDIO_OK;

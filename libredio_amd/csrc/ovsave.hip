@@ -39,8 +39,6 @@ __global__ __launch_bounds__(256) void ovsave_scale_out_kernel(const float2 *__r
 } // namespace redio
 using namespace redio;
 
-static inline int hip_rc(hipError_t e) { return e == hipSuccess ? REDIO_OK : REDIO_ERR_HIP_BASE - (int)e; }
-#define OV_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return hip_rc(_e); } while (0)
 
 struct redio_ovsave {
     int device, nfft;
@@ -134,38 +132,38 @@ extern "C" int redio_ovsave_enqueue(redio_ovsave *h, const void *d_in, size_t n_
     const size_t nout = redio_ovsave_nout(h, n_in);
     if (nout == 0) return REDIO_OK;
     if (!d_in || !d_out || d_in == d_out) return REDIO_ERR_ARG;
-    OV_TRY(hipSetDevice(h->device));
+    REDIO_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     const size_t nblk = nout / h->hop;
     const float scale = 1.0f / (float)h->nfft;
     if (h->nfft == 1024) {
-        OV_TRY(launch_ovsave1k((const float2 *)d_in, (long)h->hop, redio_fft_twiddles_dev(h->fw), redio_fft_twiddles_dev(h->bw), h->d_Hc,
+        REDIO_TRY(launch_ovsave1k((const float2 *)d_in, (long)h->hop, redio_fft_twiddles_dev(h->fw), redio_fft_twiddles_dev(h->bw), h->d_Hc,
                                (float2 *)d_out, (long)nblk, scale, st));
         return REDIO_OK;
     }
     if (h->nfft == 2048) {
-        OV_TRY(launch_ovsave2k((const float2 *)d_in, (long)h->hop, redio_fft_twiddles_pass_dev(h->fw), redio_fft_twiddles_pass_dev(h->bw), h->d_Hc,
+        REDIO_TRY(launch_ovsave2k((const float2 *)d_in, (long)h->hop, redio_fft_twiddles_pass_dev(h->fw), redio_fft_twiddles_pass_dev(h->bw), h->d_Hc,
                                (float2 *)d_out, (long)nblk, scale, st));
         return REDIO_OK;
     }
     if (h->nfft == 8192) {
-        OV_TRY(launch_ovsave8k((const float2 *)d_in, (long)h->hop, redio_fft_twiddles_pass_dev(h->fw), redio_fft_twiddles_pass_dev(h->bw), h->d_Hc,
+        REDIO_TRY(launch_ovsave8k((const float2 *)d_in, (long)h->hop, redio_fft_twiddles_pass_dev(h->fw), redio_fft_twiddles_pass_dev(h->bw), h->d_Hc,
                                (float2 *)d_out, (long)nblk, scale, st));
         return REDIO_OK;
     }
     if (h->nfft == 4096) { // block load, both transforms, product, scale and store in one kernel (fft_kernels.hip)
-        OV_TRY(launch_ovsave4k((const float2 *)d_in, (long)h->hop, redio_fft_twiddles_pass_dev(h->fw), redio_fft_twiddles_pass_dev(h->bw), h->d_Hc,
+        REDIO_TRY(launch_ovsave4k((const float2 *)d_in, (long)h->hop, redio_fft_twiddles_pass_dev(h->fw), redio_fft_twiddles_pass_dev(h->bw), h->d_Hc,
                                (float2 *)d_out, (long)nblk, scale, st));
         return REDIO_OK;
     }
     if (h->nfft == 16384) {
-        OV_TRY(launch_ovsave16k((const float2 *)d_in, (long)h->hop, redio_fft_twiddles_dev(h->fw), redio_fft_twiddles_dev(h->bw),
+        REDIO_TRY(launch_ovsave16k((const float2 *)d_in, (long)h->hop, redio_fft_twiddles_dev(h->fw), redio_fft_twiddles_dev(h->bw),
                                 redio_fft_twiddles_pass_dev(h->fw), redio_fft_twiddles_pass_dev(h->bw), h->d_Hc,
                                 (float2 *)d_out, (long)nblk, scale, st));
         return REDIO_OK;
     }
     if (h->nfft == F64K_N) { // three passes per chunk; one launch per step runs the middle pass of chunk k, the last of k - 1 and the first of k + 1 (fft_kernels.hip)
-        OV_TRY(launch_ovsave64k((const float2 *)d_in, (long)h->hop, h->d_a, h->d_b, redio_fft_twiddles_dev(h->fw), redio_fft_twiddles_dev(h->bw),
+        REDIO_TRY(launch_ovsave64k((const float2 *)d_in, (long)h->hop, h->d_a, h->d_b, redio_fft_twiddles_dev(h->fw), redio_fft_twiddles_dev(h->bw),
                                 redio_fft_twiddles_pass_dev(h->fw), redio_fft_twiddles_pass_dev(h->bw), h->d_Hc, (float2 *)d_out, (long)nblk,
                                 (long)h->chunk_blocks, scale, st, true));
         return REDIO_OK;
@@ -174,7 +172,7 @@ extern "C" int redio_ovsave_enqueue(redio_ovsave *h, const void *d_in, size_t n_
         const size_t nb = (nblk - b0 < h->chunk_blocks) ? nblk - b0 : h->chunk_blocks;
         const long total = (long)(nb * (size_t)h->nfft);
         if (ovsave_big_size(h->nfft)) { // the product and the scaled copy ride on the inverse transform's first and last pass
-            OV_TRY(launch_ovsave_big(*redio_fft_plan_dev(h->fw), *redio_fft_plan_dev(h->bw), (const float2 *)d_in + b0 * h->hop, (long)h->hop, h->d_a,
+            REDIO_TRY(launch_ovsave_big(*redio_fft_plan_dev(h->fw), *redio_fft_plan_dev(h->bw), (const float2 *)d_in + b0 * h->hop, (long)h->hop, h->d_a,
                                      h->d_b, h->d_Hc, (float2 *)d_out + b0 * h->hop, (long)nb, scale, st));
             continue;
         }
@@ -186,7 +184,7 @@ extern "C" int redio_ovsave_enqueue(redio_ovsave *h, const void *d_in, size_t n_
         const long no = (long)(nb * h->hop);
         hipLaunchKernelGGL(ovsave_scale_out_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, st, h->d_b,
                            (float2 *)d_out + b0 * h->hop, (long)nb, h->nfft, (long)h->hop, scale);
-        OV_TRY(hipGetLastError());
+        REDIO_TRY(hipGetLastError());
     }
     return REDIO_OK;
 }

@@ -14,8 +14,6 @@
 
 using namespace redio;
 
-static inline int hip_rc(hipError_t e) { return e == hipSuccess ? REDIO_OK : REDIO_ERR_HIP_BASE - (int)e; }
-#define OVR_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return hip_rc(_e); } while (0)
 
 struct redio_ovsave_real {
     int device, nfft;
@@ -97,15 +95,13 @@ extern "C" int redio_ovsave_real_reserve(redio_ovsave_real *h, size_t n_in)
     size_t rows = redio_ovsave_real_nout(h, n_in) / h->hop;
     if (rows > h->chunk_blocks) rows = h->chunk_blocks;
     if (rows <= h->scratch_rows) return REDIO_OK;
-    OVR_TRY(hipSetDevice(h->device));
+    REDIO_TRY(hipSetDevice(h->device));
     if (int rc = redio_fftr_reserve(h->fw, rows)) return rc;
     if (int rc = redio_fftr_reserve(h->bw, rows)) return rc;
-    if (int rc = redio_free(h->d_spec)) return rc;
-    h->d_spec = nullptr; h->scratch_rows = 0;
-    if (int rc = redio_free(h->d_rows)) return rc;
-    h->d_rows = nullptr;
-    if (int rc = redio_malloc(&h->d_spec, rows * (size_t)(h->nfft / 2 + 1) * sizeof(float2))) return rc;
-    if (int rc = redio_malloc(&h->d_rows, rows * (size_t)h->nfft * sizeof(float))) return rc;
+    size_t spec_rows = h->scratch_rows, rows_rows = h->scratch_rows; // one capacity for both buffers: it counts only once both have grown
+    h->scratch_rows = 0;
+    if (int rc = scratch_grow(&h->d_spec, &spec_rows, rows, (size_t)(h->nfft / 2 + 1) * sizeof(float2))) return rc;
+    if (int rc = scratch_grow(&h->d_rows, &rows_rows, rows, (size_t)h->nfft * sizeof(float))) return rc;
     h->scratch_rows = rows;
     return REDIO_OK;
 }
@@ -117,7 +113,7 @@ int redio_ovsave_real_enqueue_any(redio_ovsave_real *h, const void *d_in, size_t
     if (nout == 0) return REDIO_OK;
     if (!d_in || !d_out || d_in == d_out) return REDIO_ERR_ARG;
     if (((uintptr_t)d_in & 3) || ((uintptr_t)d_out & 7)) return REDIO_ERR_ARG;
-    OVR_TRY(hipSetDevice(h->device));
+    REDIO_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     const size_t nblk = nout / h->hop;
     const float scale = 1.0f / (float)h->nfft;
@@ -128,8 +124,7 @@ int redio_ovsave_real_enqueue_any(redio_ovsave_real *h, const void *d_in, size_t
                                            redio_fftr_super_dev(h->bw), h->d_Hc, out, (long)nblk, scale, st));
     const size_t need = nblk < h->chunk_blocks ? nblk : h->chunk_blocks;
     if (need > h->scratch_rows) { // grown on first use unless redio_ovsave_real_reserve() sized it; never during graph capture
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return REDIO_ERR_NOT_RESERVED;
+        if (stream_capturing(st)) return REDIO_ERR_NOT_RESERVED;
         if (int rc = redio_ovsave_real_reserve(h, n_in)) return rc;
     }
     const long N = h->nfft, nbins = N / 2 + 1;
@@ -140,12 +135,12 @@ int redio_ovsave_real_enqueue_any(redio_ovsave_real *h, const void *d_in, size_t
         if (aligned) {
             if (int rc = redio_fftr_enqueue_strided(h->fw, xb, h->d_spec, nb, (long)h->hop, nbins, stream)) return rc;
         } else { // the transform reads pairs: pack the blocks into the real scratch first
-            OVR_TRY(launch_ovsave_real_rows(xb, (float *)h->d_rows, (long)nb, N, (long)h->hop, st));
+            REDIO_TRY(launch_ovsave_real_rows(xb, (float *)h->d_rows, (long)nb, N, (long)h->hop, st));
             if (int rc = redio_fftr_enqueue_strided(h->fw, h->d_rows, h->d_spec, nb, N, nbins, stream)) return rc;
         }
-        OVR_TRY(launch_ovsave_real_mul((float2 *)h->d_spec, h->d_Hc, (long)nb, (int)nbins, st));
+        REDIO_TRY(launch_ovsave_real_mul((float2 *)h->d_spec, h->d_Hc, (long)nb, (int)nbins, st));
         if (int rc = redio_fftr_enqueue_strided(h->bw, h->d_spec, h->d_rows, nb, nbins, N, stream)) return rc;
-        OVR_TRY(launch_ovsave_real_scale_out((const float *)h->d_rows, out + b0 * h->hop, (long)nb, N, (long)h->hop, scale, st));
+        REDIO_TRY(launch_ovsave_real_scale_out((const float *)h->d_rows, out + b0 * h->hop, (long)nb, N, (long)h->hop, scale, st));
     }
     return REDIO_OK;
 }

@@ -12,7 +12,7 @@ hipError_t launch_pfb_u8(const void *bytes, const float *h, const float2 *tw64, 
                          hipStream_t s);
 hipError_t launch_pfb(const float2 *x, const float *h, const float2 *tw64, float2 *out, long rows, int taps_per_branch,
                       int ngroups, bool fused, hipStream_t s);
-// fft_kernels.hip: 32, 128, 256, 512 or 1024 channels with 4, 8 or 16 taps per branch in one kernel (branch filters + the M-point transform in LDS)
+// pfb_p2.hip: 32, 128, 256, 512 or 1024 channels with 4, 8 or 16 taps per branch in one kernel (branch filters + the M-point transform in LDS)
 bool pfb_p2_supported(int nchan, int taps_per_branch);
 hipError_t launch_pfb_p2(const float2 *x, const float *h, const float2 *tw, const float2 *Tord, float2 *out, long rows, int nchan, int taps_per_branch,
                          int ngroups, bool fused, hipStream_t s);
@@ -76,7 +76,6 @@ __global__ __launch_bounds__(256) void pfb_regroup_kernel(const float2 *__restri
 } // namespace redio
 using namespace redio;
 
-static inline int hip_rc(hipError_t e) { return e == hipSuccess ? REDIO_OK : REDIO_ERR_HIP_BASE - (int)e; }
 
 struct redio_pfb {
     int device, nchan, taps_per_branch;
@@ -199,8 +198,7 @@ extern "C" int redio_pfb_enqueue(redio_pfb *h, const void *d_in, size_t n_in, vo
         const size_t total = rows * (size_t)h->nchan;
         hipStream_t st = (hipStream_t)stream;
         if (total > h->v_elems || (ngroups > 1 && total > h->w_elems)) { // un-reserved: grow on first use, never inside a capture
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return REDIO_ERR_NOT_RESERVED;
+            if (stream_capturing(st)) return REDIO_ERR_NOT_RESERVED;
             const int rc = redio_pfb_reserve(h, n_in, ngroups | REDIO_PFB_RESERVE_TWO_PASS);
             if (rc != REDIO_OK) return rc;
         }
@@ -259,8 +257,7 @@ extern "C" int redio_pfb_enqueue_u8(redio_pfb *h, const void *d_bytes, size_t nb
         if (e != hipErrorNotSupported) return hip_rc(e);
     }
     if (n_in > h->conv_elems) { // other shapes, un-reserved (redio_pfb_reserve_u8): grow on first use, never inside a capture
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return REDIO_ERR_NOT_RESERVED;
+        if (stream_capturing((hipStream_t)stream)) return REDIO_ERR_NOT_RESERVED;
         e = hipStreamSynchronize((hipStream_t)stream);
         if (e != hipSuccess) return hip_rc(e);
         const int rc = redio_pfb_reserve_u8(h, nbytes, ngroups);

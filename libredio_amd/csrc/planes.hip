@@ -153,7 +153,6 @@ __global__ __launch_bounds__(256) void planes_kernel(uint32_t *rows, uint32_t *p
 } // namespace redio
 using namespace redio;
 
-static inline int hip_rc(hipError_t e) { return e == hipSuccess ? REDIO_OK : REDIO_ERR_HIP_BASE - (int)e; }
 
 constexpr size_t PLANES_NT_BYTES = (size_t)256 << 20; // the last-level cache: a larger message is not there when its consumer starts
 

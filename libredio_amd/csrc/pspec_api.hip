@@ -16,8 +16,6 @@ using namespace redio;
 
 static_assert(PSPEC_SEG == REDIO_PSPEC_SEG, "the header's constant is the kernels'");
 
-static inline int hip_rc(hipError_t e) { return e == hipSuccess ? REDIO_OK : REDIO_ERR_HIP_BASE - (int)e; }
-#define PS_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return hip_rc(_e); } while (0)
 
 struct redio_pspec {
     int device, nfft;
@@ -48,11 +46,7 @@ extern "C" int redio_pspec_create(redio_pspec **h, int nfft, size_t integrate, s
     p->fused = nfft == 1024;
     p->packs = window_host != nullptr || step != (size_t)nfft;
     p->split = 0; p->fft = fft; p->d_win = nullptr; p->d_rows = p->d_part = nullptr; p->rows_cap = p->part_cap = 0;
-    const FftPlanDev *d = redio_fft_plan_dev(fft);
-    bool generic = false;
-    for (int i = 0; i < d->nstages; ++i) generic |= d->st[i].p > 5;
-    // launch_fft: the multi-pass sizes do not run in place, and the global-memory stages of a large size with a prime factor above 5 need `work`
-    p->fft_stages = (p->packs && nfft > 16384) || (generic && (size_t)nfft * sizeof(float2) * 2 > 128 * 1024);
+    p->fft_stages = redio_fft_stages(fft, p->packs); // a packed chunk is transformed in place
     // at most 64 MiB of cf32 rows per chunk (the overlap-save operators' work-buffer size), a whole number of segments, at least one
     p->chunk_segs = ((size_t)64 << 20) / ((size_t)nfft * sizeof(float2) * PSPEC_SEG);
     if (p->chunk_segs < 1) p->chunk_segs = 1;
@@ -106,16 +100,6 @@ static bool splits(const redio_pspec *h, size_t nrows, bool fused_kernel)
     return h->split == 2 || (h->split == 0 && nrows < (size_t)PSPEC_SPLIT_ROWS);
 }
 
-static int grow(void **p, size_t *cap, size_t need, size_t elem)
-{
-    if (need <= *cap) return REDIO_OK;
-    if (int rc = redio_free(*p)) return rc;
-    *p = nullptr; *cap = 0;
-    if (int rc = redio_malloc(p, need * elem)) return rc;
-    *cap = need;
-    return REDIO_OK;
-}
-
 static size_t rows_needed(const redio_pspec *h, size_t nrows)
 {
     const size_t all = nrows * h->K, most = h->chunk_segs * PSPEC_SEG;
@@ -125,14 +109,14 @@ static size_t rows_needed(const redio_pspec *h, size_t nrows)
 static int reserve_rows(redio_pspec *h, size_t nrows, bool fused_kernel, bool transforms)
 {
     if (nrows == 0) return REDIO_OK;
-    PS_TRY(hipSetDevice(h->device));
+    REDIO_TRY(hipSetDevice(h->device));
     if (splits(h, nrows, fused_kernel))
-        if (int rc = grow(&h->d_part, &h->part_cap, nrows * h->S * (size_t)h->nfft, sizeof(float))) return rc;
+        if (int rc = scratch_grow(&h->d_part, &h->part_cap, nrows * h->S * (size_t)h->nfft, sizeof(float))) return rc;
     if (!transforms) return REDIO_OK;
     const size_t ntr = rows_needed(h, nrows);
     if (h->fft_stages)
         if (int rc = redio_fft_reserve(h->fft, ntr)) return rc;
-    return grow(&h->d_rows, &h->rows_cap, ntr * (size_t)h->nfft, sizeof(float2));
+    return scratch_grow(&h->d_rows, &h->rows_cap, ntr * (size_t)h->nfft, sizeof(float2));
 }
 
 extern "C" int redio_pspec_reserve(redio_pspec *h, size_t n_in)
@@ -140,12 +124,6 @@ extern "C" int redio_pspec_reserve(redio_pspec *h, size_t n_in)
     if (!h) return REDIO_ERR_ARG;
     // the partials are sized as the segment mode and redio_pspec_enqueue_spectra need them, whatever redio_pspec_set_split says now
     return reserve_rows(h, redio_pspec_nrows(h, n_in), false, !h->fused);
-}
-
-static bool capturing(hipStream_t st)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
 }
 
 // the accumulate and fold half over packed spectra: segments [q0, q1) of the call, whose transform g_base is spec's first row
@@ -163,7 +141,7 @@ extern "C" int redio_pspec_enqueue(redio_pspec *h, const void *d_in, size_t n_in
     const size_t N = (size_t)h->nfft;
     const char *a = (const char *)d_in, *o = (const char *)d_out; // the ranges read and written must not overlap
     if (a < o + nrows * N * sizeof(float) && o < a + n_in * sizeof(float2)) return REDIO_ERR_ARG;
-    PS_TRY(hipSetDevice(h->device));
+    REDIO_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     const float2 *x = (const float2 *)d_in;
     float *out = (float *)d_out;
@@ -171,11 +149,11 @@ extern "C" int redio_pspec_enqueue(redio_pspec *h, const void *d_in, size_t n_in
     const bool short_part = split && nrows * h->S * N > h->part_cap;
     const bool short_rows = !h->fused && rows_needed(h, nrows) * N > h->rows_cap;
     if (short_part || short_rows) { // grown on first use unless redio_pspec_reserve() sized it; never during graph capture
-        if (capturing(st)) return REDIO_ERR_NOT_RESERVED;
+        if (stream_capturing(st)) return REDIO_ERR_NOT_RESERVED;
         if (int rc = reserve_rows(h, nrows, h->fused, !h->fused)) return rc;
     }
     if (h->fused) {
-        PS_TRY(launch_pspec1k(x, (long)h->step, (long)h->K, h->d_win, redio_fft_twiddles_dev(h->fft), split ? (float *)h->d_part : out,
+        REDIO_TRY(launch_pspec1k(x, (long)h->step, (long)h->K, h->d_win, redio_fft_twiddles_dev(h->fft), split ? (float *)h->d_part : out,
                               (long)(split ? nrows * h->S : nrows), split, st));
     } else {
         const size_t nseg = nrows * h->S;
@@ -187,7 +165,7 @@ extern "C" int redio_pspec_enqueue(redio_pspec *h, const void *d_in, size_t n_in
             pspec_segment((long)q1 - 1, (long)h->K, (long)h->S, g1, cnt);
             const size_t ntr = (size_t)(g1 + cnt - g0);
             if (h->packs) {
-                PS_TRY(launch_pspec_rows(x + (size_t)g0 * h->step, h->d_win, rows, (long)ntr, (long)N, (long)h->step, st));
+                REDIO_TRY(launch_pspec_rows(x + (size_t)g0 * h->step, h->d_win, rows, (long)ntr, (long)N, (long)h->step, st));
                 if (int rc = redio_fft_enqueue(h->fft, rows, rows, ntr, stream)) return rc;
             } else {
                 if (int rc = redio_fft_enqueue(h->fft, x + (size_t)g0 * N, rows, ntr, stream)) return rc;
@@ -195,7 +173,7 @@ extern "C" int redio_pspec_enqueue(redio_pspec *h, const void *d_in, size_t n_in
             if (int rc = accumulate(h, rows, q0, q1, g0, out, split, st)) return rc;
         }
     }
-    if (split) PS_TRY(launch_pspec_fold((const float *)h->d_part, out, (long)nrows, (long)N, (long)h->S, st));
+    if (split) REDIO_TRY(launch_pspec_fold((const float *)h->d_part, out, (long)nrows, (long)N, (long)h->S, st));
     return REDIO_OK;
 }
 
@@ -208,14 +186,14 @@ extern "C" int redio_pspec_enqueue_spectra(redio_pspec *h, const void *d_spectra
     const size_t N = (size_t)h->nfft;
     const char *a = (const char *)d_spectra, *o = (const char *)d_out;
     if (a < o + nrows * N * sizeof(float) && o < a + nbatch * N * sizeof(float2)) return REDIO_ERR_ARG;
-    PS_TRY(hipSetDevice(h->device));
+    REDIO_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     const bool split = splits(h, nrows, false);
     if (split && nrows * h->S * N > h->part_cap) {
-        if (capturing(st)) return REDIO_ERR_NOT_RESERVED;
+        if (stream_capturing(st)) return REDIO_ERR_NOT_RESERVED;
         if (int rc = reserve_rows(h, nrows, false, false)) return rc;
     }
     if (int rc = accumulate(h, (const float2 *)d_spectra, 0, nrows * h->S, 0, (float *)d_out, split, st)) return rc;
-    if (split) PS_TRY(launch_pspec_fold((const float *)h->d_part, (float *)d_out, (long)nrows, (long)N, (long)h->S, st));
+    if (split) REDIO_TRY(launch_pspec_fold((const float *)h->d_part, (float *)d_out, (long)nrows, (long)N, (long)h->S, st));
     return REDIO_OK;
 }

@@ -13,14 +13,7 @@
 
 using namespace redio;
 
-// ---------------------------------------------------------------- errors
-static inline int hip_rc(hipError_t e) { return e == hipSuccess ? REDIO_OK : REDIO_ERR_HIP_BASE - (int)e; }
-#define RD_TRY(expr)                         \
-    do {                                     \
-        hipError_t _e = (expr);              \
-        if (_e != hipSuccess) return hip_rc(_e); \
-    } while (0)
-
+// ---------------------------------------------------------------- errors (hip_rc, REDIO_TRY: redio_internal.h)
 extern "C" const char *redio_strerror(int code)
 {
     switch (code) {
@@ -84,7 +77,7 @@ extern "C" int redio_host_alloc(void **host, void **dev, size_t bytes)
     if (!host || !dev) return REDIO_ERR_ARG;
     *host = *dev = nullptr;
     void *h = nullptr, *d = nullptr;
-    RD_TRY(hipHostMalloc(&h, bytes ? bytes : 1, hipHostMallocMapped));
+    REDIO_TRY(hipHostMalloc(&h, bytes ? bytes : 1, hipHostMallocMapped));
     hipError_t e = hipHostGetDevicePointer(&d, h, 0);
     if (e != hipSuccess) { hipHostFree(h); return hip_rc(e); }
     *host = h; *dev = d;
@@ -96,7 +89,7 @@ extern "C" int redio_stream_create(void **stream)
 {
     if (!stream) return REDIO_ERR_ARG;
     hipStream_t s;
-    RD_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    REDIO_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     *stream = s;
     return REDIO_OK;
 }
@@ -125,7 +118,7 @@ extern "C" int redio_graph_end(void *stream, redio_graph **g)
     if (!stream || !g) return REDIO_ERR_ARG;
     *g = nullptr;
     hipGraph_t graph = nullptr;
-    RD_TRY(hipStreamEndCapture((hipStream_t)stream, &graph));
+    REDIO_TRY(hipStreamEndCapture((hipStream_t)stream, &graph));
     hipGraphExec_t exec = nullptr;
     hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     if (e != hipSuccess) { hipGraphDestroy(graph); return hip_rc(e); }
@@ -153,7 +146,7 @@ extern "C" int redio_event_create(void **event)
 {
     if (!event) return REDIO_ERR_ARG;
     hipEvent_t e;
-    RD_TRY(hipEventCreate(&e));
+    REDIO_TRY(hipEventCreate(&e));
     *event = e;
     return REDIO_OK;
 }
@@ -161,7 +154,7 @@ extern "C" int redio_event_create_sync(void **event)
 {
     if (!event) return REDIO_ERR_ARG;
     hipEvent_t e;
-    RD_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    REDIO_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     *event = e;
     return REDIO_OK;
 }
@@ -176,7 +169,7 @@ extern "C" int redio_event_record(void *event, void *stream) { return hip_rc(hip
 extern "C" int redio_event_elapsed_ms(void *start, void *stop, float *ms)
 {
     if (!ms) return REDIO_ERR_ARG;
-    RD_TRY(hipEventSynchronize((hipEvent_t)stop));
+    REDIO_TRY(hipEventSynchronize((hipEvent_t)stop));
     return hip_rc(hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop));
 }
 
@@ -237,7 +230,7 @@ extern "C" int redio_fir_enqueue(redio_fir *h, const void *d_in, size_t n_in, vo
     size_t nout = redio_fir_nout(h, n_in);
     if (nout == 0) return REDIO_OK;
     if (!d_in || !d_out || d_in == d_out) return REDIO_ERR_ARG;
-    RD_TRY(hipSetDevice(h->device));
+    REDIO_TRY(hipSetDevice(h->device));
     return hip_rc(launch_fir(d_in, (long)n_in, h->d_taps, h->taps_pal, (int)h->ntaps, (long)h->decim, d_out, (long)nout,
                              (h->flags & REDIO_FIR_COMPLEX) != 0, (h->flags & REDIO_FIR_FUSED) != 0, (hipStream_t)stream));
 }
@@ -288,7 +281,7 @@ extern "C" int redio_convolve_f32(const float *u, size_t nu, const float *v, siz
         }
         c = ConvCache();
         c.device = dev;
-        RD_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+        REDIO_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
     }
     if (!c.plan || c.taps.size() != nv || memcmp(c.taps.data(), v, nv * sizeof(float)) != 0) {
         if (c.plan) redio_fir_destroy(c.plan);
@@ -304,31 +297,31 @@ extern "C" int redio_convolve_f32(const float *u, size_t nu, const float *v, siz
             if (c.pin_out) hipHostFree(c.pin_out);
             c.pin_in = c.pin_out = nullptr; c.pin_cap = 0;
             const size_t cap = nu < 4096 ? 4096 : nu;
-            RD_TRY(hipHostMalloc((void **)&c.pin_in, cap * sizeof(float), hipHostMallocMapped));
-            RD_TRY(hipHostMalloc((void **)&c.pin_out, cap * sizeof(float), hipHostMallocMapped));
-            RD_TRY(hipHostGetDevicePointer((void **)&c.pin_in_dev, c.pin_in, 0));
-            RD_TRY(hipHostGetDevicePointer((void **)&c.pin_out_dev, c.pin_out, 0));
+            REDIO_TRY(hipHostMalloc((void **)&c.pin_in, cap * sizeof(float), hipHostMallocMapped));
+            REDIO_TRY(hipHostMalloc((void **)&c.pin_out, cap * sizeof(float), hipHostMallocMapped));
+            REDIO_TRY(hipHostGetDevicePointer((void **)&c.pin_in_dev, c.pin_in, 0));
+            REDIO_TRY(hipHostGetDevicePointer((void **)&c.pin_out_dev, c.pin_out, 0));
             c.pin_cap = cap;
         }
         memcpy(c.pin_in, u, nu * sizeof(float));
         int rc = redio_fir_enqueue(c.plan, c.pin_in_dev, nu, c.pin_out_dev, c.stream);
         if (rc) return rc;
-        RD_TRY(hipStreamSynchronize(c.stream));
+        REDIO_TRY(hipStreamSynchronize(c.stream));
         memcpy(out, c.pin_out, n * sizeof(float));
     } else {
         if (nu > c.d_cap) {
             if (c.d_in) hipFree(c.d_in);
             if (c.d_out) hipFree(c.d_out);
             c.d_in = c.d_out = nullptr; c.d_cap = 0;
-            RD_TRY(hipMalloc((void **)&c.d_in, nu * sizeof(float)));
-            RD_TRY(hipMalloc((void **)&c.d_out, nu * sizeof(float)));
+            REDIO_TRY(hipMalloc((void **)&c.d_in, nu * sizeof(float)));
+            REDIO_TRY(hipMalloc((void **)&c.d_out, nu * sizeof(float)));
             c.d_cap = nu;
         }
-        RD_TRY(hipMemcpyAsync(c.d_in, u, nu * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        REDIO_TRY(hipMemcpyAsync(c.d_in, u, nu * sizeof(float), hipMemcpyHostToDevice, c.stream));
         int rc = redio_fir_enqueue(c.plan, c.d_in, nu, c.d_out, c.stream);
         if (rc) return rc;
-        RD_TRY(hipMemcpyAsync(out, c.d_out, n * sizeof(float), hipMemcpyDeviceToHost, c.stream));
-        RD_TRY(hipStreamSynchronize(c.stream));
+        REDIO_TRY(hipMemcpyAsync(out, c.d_out, n * sizeof(float), hipMemcpyDeviceToHost, c.stream));
+        REDIO_TRY(hipStreamSynchronize(c.stream));
     }
     if (nout) *nout = n;
     return REDIO_OK;
@@ -338,6 +331,7 @@ extern "C" int redio_convolve_f32(const float *u, size_t nu, const float *v, siz
 struct redio_fft {
     int device;
     FftPlanDev dev;
+    FftRouteInfo route; // fft_route(dev), decided once here (not in `dev`: that image is a kernel argument)
     float2 *d_tw, *d_tw_pass;
     int *d_leaf, *d_leaf_pos;
     float2 *d_tmp; // for in-place calls on the global-memory path
@@ -359,6 +353,7 @@ extern "C" int redio_fft_create(redio_fft **h, int nfft, int inverse)
     p->dev.nfft = nfft; p->dev.inverse = inverse ? 1 : 0;
     p->dev.nstages = fft_plan_stages(nfft, p->dev.st, FFT_MAX_STAGES);
     if (p->dev.nstages < 0) { delete p; return REDIO_ERR_UNSUPPORTED; }
+    p->route = fft_route(nfft, p->dev.st, p->dev.nstages);
     // twiddles evaluated in double and rounded once, phase = -+ 2 pi i / nfft (kiss_fft_alloc)
     std::vector<float2> tw((size_t)nfft);
     const double pi = 3.141592653589793238462643383279502884197169399375105820974944;
@@ -434,6 +429,9 @@ extern "C" int redio_fft_destroy(redio_fft *h)
     delete h;
     return REDIO_OK;
 }
+// launch_fft's hipErrorNotSupported: no kernel for this plan
+static int fft_rc(hipError_t e) { return e == hipErrorNotSupported ? REDIO_ERR_UNSUPPORTED : hip_rc(e); }
+
 // sizes the staging buffer of the sizes that need one (in-place calls on the global-memory path, prime factors above 5
 // beyond LDS) for up to nbatch messages per call; every other size never stages and needs no reservation
 extern "C" int redio_fft_reserve(redio_fft *h, size_t nbatch)
@@ -441,31 +439,31 @@ extern "C" int redio_fft_reserve(redio_fft *h, size_t nbatch)
     if (!h) return REDIO_ERR_ARG;
     const size_t need = 2 * nbatch * (size_t)h->dev.nfft;
     if (need <= h->tmp_elems) return REDIO_OK;
-    RD_TRY(hipSetDevice(h->device));
-    if (h->d_tmp) RD_TRY(hipFree(h->d_tmp));
+    REDIO_TRY(hipSetDevice(h->device));
+    if (h->d_tmp) REDIO_TRY(hipFree(h->d_tmp));
     h->d_tmp = nullptr; h->tmp_elems = 0;
-    RD_TRY(hipMalloc((void **)&h->d_tmp, need * sizeof(float2)));
+    REDIO_TRY(hipMalloc((void **)&h->d_tmp, need * sizeof(float2)));
     h->tmp_elems = need;
     return REDIO_OK;
 }
-// the retry of a launch that asked for staging: tmp = [input copy | work], grown on first use / growth only
+// whether a call stages: in place on a route whose first pass is a global transposition, or a route that needs `work`
+bool redio_fft_stages(const redio_fft *h, bool in_place) { return h && ((in_place && !h->route.in_place_ok) || h->route.needs_work); }
+
+// a call that stages: tmp = [input copy | work], grown on first use / growth only
 static int fft_enqueue_staged(redio_fft *h, const float2 *d_in, float2 *d_out, size_t nbatch, long in_stride, hipStream_t st)
 {
     const size_t need = nbatch * (size_t)h->dev.nfft;
     if (2 * need > h->tmp_elems) { // grown on first use unless redio_fft_reserve() sized it; never during graph capture
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return REDIO_ERR_NOT_RESERVED;
+        if (stream_capturing(st)) return REDIO_ERR_NOT_RESERVED;
         int rc = redio_fft_reserve(h, nbatch);
         if (rc) return rc;
     }
     const float2 *src = d_in;
     if (d_in == d_out) { // only reachable with contiguous messages (in_stride == nfft)
-        RD_TRY(hipMemcpyAsync(h->d_tmp, d_in, need * sizeof(float2), hipMemcpyDeviceToDevice, st));
+        REDIO_TRY(hipMemcpyAsync(h->d_tmp, d_in, need * sizeof(float2), hipMemcpyDeviceToDevice, st));
         src = h->d_tmp;
     }
-    hipError_t e = launch_fft(h->dev, src, d_out, (long)nbatch, st, in_stride, h->d_tmp + need);
-    if (e == hipErrorNotSupported) return REDIO_ERR_UNSUPPORTED;
-    return hip_rc(e);
+    return fft_rc(launch_fft(h->dev, src, d_out, (long)nbatch, st, in_stride, h->d_tmp + need));
 }
 
 extern "C" int redio_fft_enqueue(redio_fft *h, const void *d_in, void *d_out, size_t nbatch, void *stream)
@@ -473,12 +471,11 @@ extern "C" int redio_fft_enqueue(redio_fft *h, const void *d_in, void *d_out, si
     if (!h) return REDIO_ERR_ARG;
     if (nbatch == 0) return REDIO_OK;
     if (!d_in || !d_out) return REDIO_ERR_ARG;
-    RD_TRY(hipSetDevice(h->device));
-    hipError_t e = launch_fft(h->dev, (const float2 *)d_in, (float2 *)d_out, (long)nbatch, (hipStream_t)stream);
+    REDIO_TRY(hipSetDevice(h->device));
     // global-memory path in place, or a prime factor above 5 in a size that does not fit LDS: stage through the
-    // plan-owned temporary (a caller that needs graph capture runs the sequence once before capturing)
-    if (e == hipErrorNotSupported) return fft_enqueue_staged(h, (const float2 *)d_in, (float2 *)d_out, nbatch, 0, (hipStream_t)stream);
-    return hip_rc(e);
+    // plan-owned temporary (a caller that needs graph capture calls redio_fft_reserve before capturing)
+    if (redio_fft_stages(h, d_in == d_out)) return fft_enqueue_staged(h, (const float2 *)d_in, (float2 *)d_out, nbatch, 0, (hipStream_t)stream);
+    return fft_rc(launch_fft(h->dev, (const float2 *)d_in, (float2 *)d_out, (long)nbatch, (hipStream_t)stream));
 }
 
 // messages that start every in_stride samples (in_stride < nfft: overlapping blocks, as overlap-save
@@ -488,10 +485,9 @@ extern "C" int redio_fft_enqueue_strided(redio_fft *h, const void *d_in, void *d
     if (!h) return REDIO_ERR_ARG;
     if (nbatch == 0) return REDIO_OK;
     if (!d_in || !d_out || d_in == d_out || in_stride <= 0) return REDIO_ERR_ARG;
-    RD_TRY(hipSetDevice(h->device));
-    hipError_t e = launch_fft(h->dev, (const float2 *)d_in, (float2 *)d_out, (long)nbatch, (hipStream_t)stream, in_stride);
-    if (e == hipErrorNotSupported) return fft_enqueue_staged(h, (const float2 *)d_in, (float2 *)d_out, nbatch, in_stride, (hipStream_t)stream);
-    return hip_rc(e);
+    REDIO_TRY(hipSetDevice(h->device));
+    if (redio_fft_stages(h, false)) return fft_enqueue_staged(h, (const float2 *)d_in, (float2 *)d_out, nbatch, in_stride, (hipStream_t)stream);
+    return fft_rc(launch_fft(h->dev, (const float2 *)d_in, (float2 *)d_out, (long)nbatch, (hipStream_t)stream, in_stride));
 }
 
 // the list preconditions of include/redio.h that can be checked: a pointer for every entry that yields output, in != out
@@ -507,7 +503,7 @@ static size_t fft_list_nout(const void *, size_t n) { return n; }
 extern "C" int redio_fft_enqueue_list(redio_fft *h, const redio_msg *msgs, size_t count, void *stream)
 {
     if (!h || !list_args_ok(msgs, count, fft_list_nout, h)) return REDIO_ERR_ARG;
-    RD_TRY(hipSetDevice(h->device));
+    REDIO_TRY(hipSetDevice(h->device));
     if (h->dev.nfft != 1024) { // one launch per entry (the other sizes' kernels take one contiguous batch)
         for (size_t i = 0; i < count; ++i)
             if (int rc = redio_fft_enqueue(h, msgs[i].in, msgs[i].out, msgs[i].n, stream)) return rc;
@@ -521,11 +517,11 @@ extern "C" int redio_fft_enqueue_list(redio_fft *h, const redio_msg *msgs, size_
         if (msgs[i].n == 0) continue;
         in[k] = (const float2 *)msgs[i].in; out[k] = (float2 *)msgs[i].out; nb[k] = (long)msgs[i].n;
         if (++k == REDIO_LIST_MAX) {
-            RD_TRY(launch_fft1k_list(h->dev, in, out, nb, k, (hipStream_t)stream));
+            REDIO_TRY(launch_fft1k_list(h->dev, in, out, nb, k, (hipStream_t)stream));
             k = 0;
         }
     }
-    if (k) RD_TRY(launch_fft1k_list(h->dev, in, out, nb, k, (hipStream_t)stream));
+    if (k) REDIO_TRY(launch_fft1k_list(h->dev, in, out, nb, k, (hipStream_t)stream));
     return REDIO_OK;
 }
 
@@ -618,17 +614,12 @@ extern "C" int redio_chain_reserve(redio_chain *h, size_t n_in)
     if (!h) return REDIO_ERR_ARG;
     const size_t ny = redio_chain_nblocks(h, n_in) * (size_t)h->nfft;
     if (ny <= h->mid_elems) return REDIO_OK;
-    RD_TRY(hipSetDevice(h->fir->device));
-    if (h->d_mid) RD_TRY(hipFree(h->d_mid));
+    REDIO_TRY(hipSetDevice(h->fir->device));
+    if (h->d_mid) REDIO_TRY(hipFree(h->d_mid));
     h->d_mid = nullptr; h->mid_elems = 0;
-    RD_TRY(hipMalloc((void **)&h->d_mid, ny * sizeof(float2)));
+    REDIO_TRY(hipMalloc((void **)&h->d_mid, ny * sizeof(float2)));
     h->mid_elems = ny;
     return REDIO_OK;
-}
-static bool stream_is_capturing(hipStream_t st)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
 }
 extern "C" int redio_chain_enqueue(redio_chain *h, const void *d_in, size_t n_in, void *d_out, void *stream)
 {
@@ -636,7 +627,7 @@ extern "C" int redio_chain_enqueue(redio_chain *h, const void *d_in, size_t n_in
     size_t nblk = redio_chain_nblocks(h, n_in);
     if (nblk == 0) return REDIO_OK;
     if (!d_in || !d_out || d_in == d_out) return REDIO_ERR_ARG;
-    RD_TRY(hipSetDevice(h->fir->device));
+    REDIO_TRY(hipSetDevice(h->fir->device));
     const bool fused_math = (h->fir->flags & REDIO_FIR_FUSED) != 0;
     if (redio_chain_is_fused(h)) {
         hipError_t e = launch_chain(h->fft->dev, (const float2 *)d_in, (long)n_in, h->fir->d_taps, h->fir->taps_pal, (int)h->fir->ntaps,
@@ -648,12 +639,12 @@ extern "C" int redio_chain_enqueue(redio_chain *h, const void *d_in, size_t n_in
     // here on first use -- an allocation, so never while the stream is being captured into a graph.
     size_t ny = nblk * (size_t)h->nfft;
     if (ny > h->mid_elems) {
-        if (stream_is_capturing((hipStream_t)stream)) return REDIO_ERR_NOT_RESERVED;
+        if (stream_capturing((hipStream_t)stream)) return REDIO_ERR_NOT_RESERVED;
         int rc = redio_chain_reserve(h, n_in);
         if (rc) return rc;
     }
     size_t need_in = (ny - 1) * h->fir->decim + h->fir->ntaps; // inputs feeding the kept blocks
-    RD_TRY(launch_fir(d_in, (long)need_in, h->fir->d_taps, h->fir->taps_pal, (int)h->fir->ntaps, (long)h->fir->decim, h->d_mid, (long)ny,
+    REDIO_TRY(launch_fir(d_in, (long)need_in, h->fir->d_taps, h->fir->taps_pal, (int)h->fir->ntaps, (long)h->fir->decim, h->d_mid, (long)ny,
                       true, fused_math, (hipStream_t)stream));
     return redio_fft_enqueue(h->fft, h->d_mid, d_out, nblk, stream);
 }
@@ -668,7 +659,7 @@ extern "C" int redio_chain_enqueue_list(redio_chain *h, const redio_msg *msgs, s
             if (int rc = redio_chain_enqueue(h, msgs[i].in, msgs[i].n, msgs[i].out, stream)) return rc;
         return REDIO_OK;
     }
-    RD_TRY(hipSetDevice(h->fir->device));
+    REDIO_TRY(hipSetDevice(h->fir->device));
     const bool fused_math = (h->fir->flags & REDIO_FIR_FUSED) != 0;
     const int K = (int)h->fir->ntaps;
     const long D = (long)h->fir->decim;
@@ -684,11 +675,11 @@ extern "C" int redio_chain_enqueue_list(redio_chain *h, const redio_msg *msgs, s
         if ((reinterpret_cast<uintptr_t>(msgs[i].in) & 15) != 0) { rest = true; continue; }
         x[k] = (const float2 *)msgs[i].in; out[k] = (float2 *)msgs[i].out; nb[k] = (long)nblk;
         if (++k == REDIO_LIST_MAX) {
-            RD_TRY(launch_chain_list(K, D, x, out, nb, k, h->fir->d_taps, h->fir->taps_pal, h->fft->dev.tw, fused_math, (hipStream_t)stream));
+            REDIO_TRY(launch_chain_list(K, D, x, out, nb, k, h->fir->d_taps, h->fir->taps_pal, h->fft->dev.tw, fused_math, (hipStream_t)stream));
             k = 0;
         }
     }
-    if (k) RD_TRY(launch_chain_list(K, D, x, out, nb, k, h->fir->d_taps, h->fir->taps_pal, h->fft->dev.tw, fused_math, (hipStream_t)stream));
+    if (k) REDIO_TRY(launch_chain_list(K, D, x, out, nb, k, h->fir->d_taps, h->fir->taps_pal, h->fft->dev.tw, fused_math, (hipStream_t)stream));
     if (rest) // the others through the single call behind them on the same stream (its two-kernel path: the same bits)
         for (size_t i = 0; i < count; ++i)
             if (redio_chain_nblocks(h, msgs[i].n) && (reinterpret_cast<uintptr_t>(msgs[i].in) & 15) != 0)
@@ -702,11 +693,11 @@ extern "C" int redio_chain_reserve_u8(redio_chain *h, size_t nbytes)
 {
     if (!h) return REDIO_ERR_ARG;
     const size_t n_in = nbytes / 2;
-    RD_TRY(hipSetDevice(h->fir->device));
+    REDIO_TRY(hipSetDevice(h->fir->device));
     if (n_in > h->conv_elems) {
-        if (h->d_conv) RD_TRY(hipFree(h->d_conv));
+        if (h->d_conv) REDIO_TRY(hipFree(h->d_conv));
         h->d_conv = nullptr; h->conv_elems = 0;
-        RD_TRY(hipMalloc((void **)&h->d_conv, n_in * sizeof(float2)));
+        REDIO_TRY(hipMalloc((void **)&h->d_conv, n_in * sizeof(float2)));
         h->conv_elems = n_in;
     }
     return redio_chain_reserve(h, n_in);
@@ -720,7 +711,7 @@ extern "C" int redio_chain_enqueue_u8(redio_chain *h, const void *d_bytes, size_
     const size_t nblk = redio_chain_nblocks(h, n_in);
     if (nblk == 0) return REDIO_OK;
     if (!d_bytes || !d_out || d_bytes == d_out) return REDIO_ERR_ARG;
-    RD_TRY(hipSetDevice(h->fir->device));
+    REDIO_TRY(hipSetDevice(h->fir->device));
     if (redio_chain_is_fused(h)) {
         hipError_t e = launch_chain_u8(h->fft->dev, d_bytes, h->fir->d_taps, h->fir->taps_pal, (int)h->fir->ntaps, (long)h->fir->decim, (float2 *)d_out, (long)nblk,
                                        (h->fir->flags & REDIO_FIR_FUSED) != 0, (hipStream_t)stream);
@@ -728,8 +719,8 @@ extern "C" int redio_chain_enqueue_u8(redio_chain *h, const void *d_bytes, size_
     }
     // other shapes, or bytes that are not 4-byte aligned: convert into a plan-owned buffer, then the cf32 entry point (same results)
     if (n_in > h->conv_elems) { // un-reserved (redio_chain_reserve_u8): grow on first use, never inside a capture
-        if (stream_is_capturing((hipStream_t)stream)) return REDIO_ERR_NOT_RESERVED;
-        RD_TRY(hipStreamSynchronize((hipStream_t)stream)); // launches that still read the old buffer
+        if (stream_capturing((hipStream_t)stream)) return REDIO_ERR_NOT_RESERVED;
+        REDIO_TRY(hipStreamSynchronize((hipStream_t)stream)); // launches that still read the old buffer
         int rc = redio_chain_reserve_u8(h, nbytes);
         if (rc) return rc;
     }

@@ -5,9 +5,40 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include "../../include/redio.h"
 #include "fft_core.h"
+#include "fft_route.h"
+
+// ---- host helpers of every *_api / plan file: the error mapping, the early return, "is this stream capturing", scratch growth ----
+static inline int hip_rc(hipError_t e) { return e == hipSuccess ? REDIO_OK : REDIO_ERR_HIP_BASE - (int)e; }
+#define REDIO_TRY(expr)                          \
+    do {                                         \
+        hipError_t _e = (expr);                  \
+        if (_e != hipSuccess) return hip_rc(_e); \
+    } while (0)
 
 namespace redio {
+
+#pragma GCC visibility push(hidden) // library-internal: not in the exported symbol set
+// a plan never allocates while its stream is being captured into a graph: it returns REDIO_ERR_NOT_RESERVED instead
+inline bool stream_capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+// plan-owned scratch of `need` elements of `elem` bytes: nothing if it is large enough, else free, redio_malloc, and the new
+// capacity only once the allocation succeeded
+inline int scratch_grow(void **p, size_t *cap, size_t need, size_t elem)
+{
+    if (need <= *cap) return REDIO_OK;
+    if (int rc = redio_free(*p)) return rc;
+    *p = nullptr; *cap = 0;
+    if (int rc = redio_malloc(p, need * elem)) return rc;
+    *cap = need;
+    return REDIO_OK;
+}
+#pragma GCC visibility pop
 
 // Launch-geometry knobs for measurement (tools/ablate.sh, tools/chain_variants.py ...): read from the environment ONLY in a
 // -DREDIO_MEASURE build (make EXTRA=-DREDIO_MEASURE OUT=../_build_measure).  The shipped library reads no environment variable.
@@ -45,13 +76,18 @@ struct FftPlanDev {
     unsigned magic_m[FFT_MAX_STAGES]; // ceil(2^32 / m) per stage and ceil(2^32 / nfft): exact quotients by __umulhi for
     unsigned magic_n;                 // dividends below 2^16 * ... (b * m < 2^32), which LDS-resident sizes satisfy
 };
-// in != out on the paths that say so (hipErrorNotSupported otherwise: the C-ABI layer stages the input); work
-// (nfft*nbatch float2) is needed by the global-memory path when the size has a prime factor above 5
 // per-pass twiddle tables of the multi-pass transforms: element count for nfft (0: none needed) and the device-side build
 size_t fftbig_tables_elems(int nfft);
 hipError_t fftbig_tables_build(const float2 *tw, float2 *tables, int nfft, hipStream_t s);
+// the route of the plan (fft_route.h) decides the kernels.  A route without in_place_ok wants in != out, one with
+// needs_work wants work (nfft * nbatch float2): hipErrorInvalidValue otherwise -- the C-ABI layer stages such calls before it
+// launches.  hipErrorNotSupported: no kernel for this plan
 hipError_t launch_fft(const FftPlanDev &p, const float2 *in, float2 *out, long nbatch, hipStream_t s, long in_stride = 0,
                       float2 *work = nullptr);
+#pragma GCC visibility push(hidden)
+template <int N> // fft_ct.h, instantiated for the sizes of REDIO_FFT_CT_SIZES by fft_ct_lo.hip / fft_ct_hi.hip
+hipError_t launch_fft_ct(const FftPlanDev &p, const float2 *in, float2 *out, long nbatch, long in_stride, bool inv, hipStream_t s);
+#pragma GCC visibility pop
 // one launch over a list of count (1 ... REDIO_LIST_MAX) messages of nbatch[i] >= 1 consecutive transforms each; nfft 1024 only
 hipError_t launch_fft1k_list(const FftPlanDev &p, const float2 *const *in, float2 *const *out, const long *nbatch, int count, hipStream_t s);
 
@@ -151,6 +187,9 @@ int redio_ovsave_real_enqueue_any(redio_ovsave_real *h, const void *d_in, size_t
 
 // redio_api.hip: the device twiddle table behind a public FFT handle (library-internal)
 struct redio_fft;
+// whether a call on this plan goes through its staging buffer (in_place: with d_in == d_out).  A plan that owns a redio_fft and must
+// work under graph capture asks here, once, whether its own *_reserve has to call redio_fft_reserve
+__attribute__((visibility("hidden"))) bool redio_fft_stages(const redio_fft *h, bool in_place);
 const redio::FftPlanDev *redio_fft_plan_dev(const redio_fft *h);
 const float2 *redio_fft_twiddles_dev(const redio_fft *h);
 const float2 *redio_fft_twiddles_pass_dev(const redio_fft *h); // the pass-ordered copy (multi-pass sizes), else null

@@ -225,8 +225,6 @@ __global__ __launch_bounds__(256) void binconv_kernel(const uint8_t *__restrict_
 } // namespace redio
 using namespace redio;
 
-static inline int hip_rc(hipError_t e) { return e == hipSuccess ? REDIO_OK : REDIO_ERR_HIP_BASE - (int)e; }
-#define RN_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return hip_rc(_e); } while (0)
 
 struct redio_rle {
     int device;
@@ -270,35 +268,35 @@ extern "C" int redio_rle_feed(redio_rle *r, const void *d_in, size_t n, void *d_
     if (!r) return REDIO_ERR_ARG;
     if (n == 0) return REDIO_OK;
     if (!d_in) return REDIO_ERR_ARG;
-    RN_TRY(hipSetDevice(r->device));
+    REDIO_TRY(hipSetDevice(r->device));
     hipStream_t st = (hipStream_t)stream;
     const uint8_t *x = (const uint8_t *)d_in;
     const long ntiles = (long)((n + RUN_TILE - 1) / RUN_TILE);
     if ((size_t)ntiles > r->tiles_cap) {
         hipFree(r->d_tiles); r->d_tiles = nullptr; r->tiles_cap = 0;
-        RN_TRY(hipMalloc((void **)&r->d_tiles, (size_t)ntiles * sizeof(unsigned)));
+        REDIO_TRY(hipMalloc((void **)&r->d_tiles, (size_t)ntiles * sizeof(unsigned)));
         r->tiles_cap = (size_t)ntiles;
     }
     hipLaunchKernelGGL(rle_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, st, x, (long)n, r->have_prev, r->prev, r->d_tiles);
     hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(1024), 0, st, r->d_tiles, ntiles, r->d_total);
     unsigned long long total = 0;
-    RN_TRY(hipMemcpyAsync(&total, r->d_total, sizeof(total), hipMemcpyDeviceToHost, st));
+    REDIO_TRY(hipMemcpyAsync(&total, r->d_total, sizeof(total), hipMemcpyDeviceToHost, st));
     uint8_t last = 0;
-    RN_TRY(hipMemcpyAsync(&last, x + n - 1, 1, hipMemcpyDeviceToHost, st));
-    RN_TRY(hipStreamSynchronize(st));
+    REDIO_TRY(hipMemcpyAsync(&last, x + n - 1, 1, hipMemcpyDeviceToHost, st));
+    REDIO_TRY(hipStreamSynchronize(st));
     long last_change = -1; // position of the last change in this call, for the carried run length
     if (total > 0) {
         if (total > cap || !d_vals || !d_counts) return REDIO_ERR_ARG;
         if (total > r->pos_cap) {
             hipFree(r->d_pos); r->d_pos = nullptr; r->pos_cap = 0;
-            RN_TRY(hipMalloc((void **)&r->d_pos, (size_t)total * sizeof(long)));
+            REDIO_TRY(hipMalloc((void **)&r->d_pos, (size_t)total * sizeof(long)));
             r->pos_cap = (size_t)total;
         }
         hipLaunchKernelGGL(rle_positions_kernel, dim3((unsigned)ntiles), dim3(256), 0, st, x, (long)n, r->have_prev, r->prev, r->d_tiles, r->d_pos, (uint8_t *)d_vals);
         hipLaunchKernelGGL(rle_emit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, r->d_pos, (long)total, r->i,
                            (unsigned long long *)d_counts);
-        RN_TRY(hipMemcpyAsync(&last_change, r->d_pos + (total - 1), sizeof(long), hipMemcpyDeviceToHost, st));
-        RN_TRY(hipStreamSynchronize(st));
+        REDIO_TRY(hipMemcpyAsync(&last_change, r->d_pos + (total - 1), sizeof(long), hipMemcpyDeviceToHost, st));
+        REDIO_TRY(hipStreamSynchronize(st));
     }
     // state for the next call: the open run
     if (!r->have_prev) { // the very first sample only seeds x and i = 1 (kpn.rs:18-19)
@@ -332,8 +330,8 @@ extern "C" int redio_rld(const void *d_vals, const void *d_counts, size_t nruns,
     unsigned long long *starts = (unsigned long long *)d_scratch;
     hipLaunchKernelGGL(scan_u64_kernel, dim3(1), dim3(1024), 0, st, (const unsigned long long *)d_counts, (long)nruns, starts, starts + nruns);
     unsigned long long total = 0;
-    RN_TRY(hipMemcpyAsync(&total, starts + nruns, sizeof(total), hipMemcpyDeviceToHost, st));
-    RN_TRY(hipStreamSynchronize(st));
+    REDIO_TRY(hipMemcpyAsync(&total, starts + nruns, sizeof(total), hipMemcpyDeviceToHost, st));
+    REDIO_TRY(hipStreamSynchronize(st));
     if (nout) *nout = (size_t)total;
     if (total == 0) return REDIO_OK;
     if (total > cap || !d_out) return REDIO_ERR_ARG;
@@ -372,7 +370,7 @@ extern "C" int redio_binconv(const void *d_bits, size_t nmsg, size_t nbits, cons
         if (off > nbits) return REDIO_ERR_ASSERT;
     }
     int *d_tab = nullptr;
-    RN_TRY(hipMalloc((void **)&d_tab, 128 * sizeof(int)));
+    REDIO_TRY(hipMalloc((void **)&d_tab, 128 * sizeof(int)));
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemcpyAsync(d_tab, hs, nfields * sizeof(int), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_tab + 64, hw, nfields * sizeof(int), hipMemcpyHostToDevice, st);

@@ -63,12 +63,6 @@ bool src_make_table(int converter, std::vector<float> &c, int &half_len, int &in
 
 using namespace redio;
 
-static inline int hip_rc(hipError_t e) { return e == hipSuccess ? REDIO_OK : REDIO_ERR_HIP_BASE - (int)e; }
-#define SRC_TRY(expr)                               \
-    do {                                            \
-        hipError_t _e = (expr);                     \
-        if (_e != hipSuccess) return hip_rc(_e);    \
-    } while (0)
 
 enum { SRC_MAX_RATIO = 256, SRC_SHIFT = 12 };
 
@@ -132,25 +126,25 @@ static bool is_bad_src_ratio(double r) { return r < (1.0 / SRC_MAX_RATIO) || r >
 extern "C" int redio_src_reset(redio_src *s)
 {
     if (!s) return REDIO_SRC_ERR_BAD_STATE;
-    SRC_TRY(hipSetDevice(s->device));
+    REDIO_TRY(hipSetDevice(s->device));
     if (s->in_flight) { // queued calls (redio_src_enqueue) may still be running on a non-blocking stream: the memsets below must not pass them
-        SRC_TRY(hipDeviceSynchronize());
+        REDIO_TRY(hipDeviceSynchronize());
         s->in_flight = 0;
     }
     s->last_ratio = 0.0;
     s->last_position = 0.0;
     if (s->converter >= 3) { // zoh_reset / linear_reset
         s->zl_reset = 1;
-        SRC_TRY(hipMemset(s->d_last, 0, (size_t)s->nchan * sizeof(float)));
-        SRC_TRY(hipStreamSynchronize(nullptr));
+        REDIO_TRY(hipMemset(s->d_last, 0, (size_t)s->nchan * sizeof(float)));
+        REDIO_TRY(hipStreamSynchronize(nullptr));
         return REDIO_OK;
     }
     s->b_current = s->b_end = 0;
     s->b_real_end = -1;
     s->cur = 0;
-    SRC_TRY(hipMemset(s->d_buf_base[0], 0, ((size_t)s->front + (size_t)s->nchan * s->buf_stride) * sizeof(float)));
-    SRC_TRY(hipMemset(s->d_buf_base[1], 0, ((size_t)s->front + (size_t)s->nchan * s->buf_stride) * sizeof(float)));
-    SRC_TRY(hipStreamSynchronize(nullptr)); // later work runs on non-blocking streams, which do not wait for the default stream
+    REDIO_TRY(hipMemset(s->d_buf_base[0], 0, ((size_t)s->front + (size_t)s->nchan * s->buf_stride) * sizeof(float)));
+    REDIO_TRY(hipMemset(s->d_buf_base[1], 0, ((size_t)s->front + (size_t)s->nchan * s->buf_stride) * sizeof(float)));
+    REDIO_TRY(hipStreamSynchronize(nullptr)); // later work runs on non-blocking streams, which do not wait for the default stream
     return REDIO_OK;
 }
 
@@ -261,20 +255,20 @@ static int ensure_scratch(redio_src *s, size_t nout)
     hipFree(s->d_pos); hipFree(s->d_start); hipFree(s->d_inc); hipFree(s->d_scale);
     s->d_pos = s->d_start = s->d_inc = nullptr; s->d_scale = nullptr; s->d_cap = 0;
     size_t cap = nout + nout / 4 + 1024;
-    SRC_TRY(hipMalloc((void **)&s->d_pos, cap * sizeof(int)));
-    SRC_TRY(hipMalloc((void **)&s->d_start, cap * sizeof(int)));
-    SRC_TRY(hipMalloc((void **)&s->d_inc, cap * sizeof(int)));
-    SRC_TRY(hipMalloc((void **)&s->d_scale, cap * sizeof(double)));
+    REDIO_TRY(hipMalloc((void **)&s->d_pos, cap * sizeof(int)));
+    REDIO_TRY(hipMalloc((void **)&s->d_start, cap * sizeof(int)));
+    REDIO_TRY(hipMalloc((void **)&s->d_inc, cap * sizeof(int)));
+    REDIO_TRY(hipMalloc((void **)&s->d_scale, cap * sizeof(double)));
     s->d_cap = cap;
     if (s->h_pos) hipHostFree(s->h_pos);
     if (s->h_start) hipHostFree(s->h_start);
     if (s->h_inc) hipHostFree(s->h_inc);
     if (s->h_scale) hipHostFree(s->h_scale);
     s->h_pos = s->h_start = s->h_inc = nullptr; s->h_scale = nullptr;
-    SRC_TRY(hipHostMalloc((void **)&s->h_pos, cap * sizeof(int), hipHostMallocDefault));
-    SRC_TRY(hipHostMalloc((void **)&s->h_start, cap * sizeof(int), hipHostMallocDefault));
-    SRC_TRY(hipHostMalloc((void **)&s->h_inc, cap * sizeof(int), hipHostMallocDefault));
-    SRC_TRY(hipHostMalloc((void **)&s->h_scale, cap * sizeof(double), hipHostMallocDefault));
+    REDIO_TRY(hipHostMalloc((void **)&s->h_pos, cap * sizeof(int), hipHostMallocDefault));
+    REDIO_TRY(hipHostMalloc((void **)&s->h_start, cap * sizeof(int), hipHostMallocDefault));
+    REDIO_TRY(hipHostMalloc((void **)&s->h_inc, cap * sizeof(int), hipHostMallocDefault));
+    REDIO_TRY(hipHostMalloc((void **)&s->h_scale, cap * sizeof(double), hipHostMallocDefault));
     return REDIO_OK;
 }
 
@@ -300,7 +294,7 @@ static int prepare_data(redio_src *f, const SrcInput &in, long in_count, long &i
         len = f->b_end - f->b_current;
         // memmove(buffer, buffer + b_current - half, half + len): through the other image
         const int other = f->cur ^ 1;
-        SRC_TRY(launch_src_copy_rows(f->d_buf[f->cur], f->buf_stride, f->b_current - half, f->d_buf[other], f->buf_stride, 0,
+        REDIO_TRY(launch_src_copy_rows(f->d_buf[f->cur], f->buf_stride, f->b_current - half, f->d_buf[other], f->buf_stride, 0,
                                      (long)half + len, f->nchan, st));
         f->cur = other;
         f->b_current = half;
@@ -313,9 +307,9 @@ static int prepare_data(redio_src *f, const SrcInput &in, long in_count, long &i
     if (len < 0 || f->b_end + len > f->b_len) return REDIO_SRC_ERR_SINC_PREPARE_DATA_BAD_LEN;
     if (len > 0) {
         if (in.host) {
-            SRC_TRY(hipMemcpyAsync(f->d_buf[f->cur] + f->b_end, in.host + in_used, (size_t)len * sizeof(float), hipMemcpyHostToDevice, st));
+            REDIO_TRY(hipMemcpyAsync(f->d_buf[f->cur] + f->b_end, in.host + in_used, (size_t)len * sizeof(float), hipMemcpyHostToDevice, st));
         } else {
-            SRC_TRY(launch_src_copy_rows(in.dev, in.in_stride, in_used, f->d_buf[f->cur], f->buf_stride, f->b_end, len, f->nchan, st));
+            REDIO_TRY(launch_src_copy_rows(in.dev, in.in_stride, in_used, f->d_buf[f->cur], f->buf_stride, f->b_end, len, f->nchan, st));
         }
     }
     f->b_end += len;
@@ -325,7 +319,7 @@ static int prepare_data(redio_src *f, const SrcInput &in, long in_count, long &i
             len = f->b_end - f->b_current;
             if (half + len > f->b_len) return REDIO_SRC_ERR_SINC_PREPARE_DATA_BAD_LEN; // include/samplerate.h (iv): the library's move would overrun its buffer
             const int other = f->cur ^ 1;
-            SRC_TRY(launch_src_copy_rows(f->d_buf[f->cur], f->buf_stride, f->b_current - half, f->d_buf[other], f->buf_stride, 0,
+            REDIO_TRY(launch_src_copy_rows(f->d_buf[f->cur], f->buf_stride, f->b_current - half, f->d_buf[other], f->buf_stride, 0,
                                          (long)half + len, f->nchan, st));
             f->cur = other;
             f->b_current = half;
@@ -334,7 +328,7 @@ static int prepare_data(redio_src *f, const SrcInput &in, long in_count, long &i
         f->b_real_end = f->b_end;
         len = half + 5;
         if (len < 0 || f->b_end + len > f->b_len) len = f->b_len - f->b_end;
-        SRC_TRY(launch_src_fill_rows(f->d_buf[f->cur], f->buf_stride, f->b_end, len, f->nchan, 0.0f, st));
+        REDIO_TRY(launch_src_fill_rows(f->d_buf[f->cur], f->buf_stride, f->b_end, len, f->nchan, 0.0f, st));
         f->b_end += len;
     }
     return REDIO_OK;
@@ -364,8 +358,8 @@ static int prepare_uniform(redio_src *f, int inc)
     std::vector<double> all(3 * guard + L.size() + R.size(), 0.0);
     std::copy(L.begin(), L.end(), all.begin() + (long)guard);
     std::copy(R.begin(), R.end(), all.begin() + (long)(2 * guard + L.size()));
-    SRC_TRY(hipMalloc((void **)&f->d_tabs, all.size() * sizeof(double)));
-    SRC_TRY(hipMemcpy(f->d_tabs, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice));
+    REDIO_TRY(hipMalloc((void **)&f->d_tabs, all.size() * sizeof(double)));
+    REDIO_TRY(hipMemcpy(f->d_tabs, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice));
     f->d_cl = f->d_tabs + guard;
     f->d_cr = f->d_tabs + 2 * guard + L.size();
     // at zero phase the right wing starts one increment in and R[t] == L[t] bit for bit over its whole length: both wings
@@ -383,8 +377,8 @@ static int prepare_fast_taps(redio_src *f, int S, double scale)
 {
     if (f->d_T2 && f->fast_scale == scale && f->nm >= 0 && f->nm == ((f->ncl + f->ncr + S + 127) & ~127)) return REDIO_OK;
     std::vector<double> L((size_t)f->ncl), R((size_t)f->ncr);
-    SRC_TRY(hipMemcpy(L.data(), f->d_cl, L.size() * sizeof(double), hipMemcpyDeviceToHost));
-    SRC_TRY(hipMemcpy(R.data(), f->d_cr, R.size() * sizeof(double), hipMemcpyDeviceToHost));
+    REDIO_TRY(hipMemcpy(L.data(), f->d_cl, L.size() * sizeof(double), hipMemcpyDeviceToHost));
+    REDIO_TRY(hipMemcpy(R.data(), f->d_cr, R.size() * sizeof(double), hipMemcpyDeviceToHost));
     const int KH = f->ncl + f->ncr;
     std::vector<float> H((size_t)KH);
     for (int j = 0; j < f->ncl; ++j) H[(size_t)j] = (float)(scale * L[(size_t)j]);                       // far end first
@@ -394,8 +388,8 @@ static int prepare_fast_taps(redio_src *f, int S, double scale)
     for (int m = 0; m < nm; ++m)
         T[(size_t)m] = make_float2(m < KH ? H[(size_t)m] : 0.0f, (m - S >= 0 && m - S < KH) ? H[(size_t)(m - S)] : 0.0f);
     hipFree(f->d_T2); f->d_T2 = nullptr;
-    SRC_TRY(hipMalloc((void **)&f->d_T2, T.size() * sizeof(float2)));
-    SRC_TRY(hipMemcpy(f->d_T2, T.data(), T.size() * sizeof(float2), hipMemcpyHostToDevice));
+    REDIO_TRY(hipMalloc((void **)&f->d_T2, T.size() * sizeof(float2)));
+    REDIO_TRY(hipMemcpy(f->d_T2, T.data(), T.size() * sizeof(float2), hipMemcpyHostToDevice));
     f->nm = nm; f->fast_scale = scale;
     // the same taps by phase for the phase-split kernel: Hp[p][j] = H[S*j + p], zero filled to whole chunks of 32 taps
     hipFree(f->d_Hp); f->d_Hp = nullptr;
@@ -404,8 +398,8 @@ static int prepare_fast_taps(redio_src *f, int S, double scale)
         const int ntap = src_fastp_row(f->fastp_nc);
         std::vector<float> P((size_t)S * ntap, 0.0f);
         for (int m = 0; m < KH; ++m) P[(size_t)(m % S) * ntap + m / S] = H[(size_t)m];
-        SRC_TRY(hipMalloc((void **)&f->d_Hp, P.size() * sizeof(float)));
-        SRC_TRY(hipMemcpy(f->d_Hp, P.data(), P.size() * sizeof(float), hipMemcpyHostToDevice));
+        REDIO_TRY(hipMalloc((void **)&f->d_Hp, P.size() * sizeof(float)));
+        REDIO_TRY(hipMemcpy(f->d_Hp, P.data(), P.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     return REDIO_OK;
 }
@@ -482,7 +476,7 @@ static int try_periodic_epoch(redio_src *f, long first, long count, float *d_out
     // this epoch's tables in the pinned arena (kept until the call's final synchronisation: the uploads are asynchronous)
     const size_t nLd = (size_t)NL * P, nRd = (size_t)NR * P, need = (nLd + nRd) * sizeof(double) + 3 * 256 * sizeof(int);
     if (!f->h_arena) {
-        SRC_TRY(hipHostMalloc((void **)&f->h_arena, (size_t)16 << 20, hipHostMallocDefault));
+        REDIO_TRY(hipHostMalloc((void **)&f->h_arena, (size_t)16 << 20, hipHostMallocDefault));
         f->arena_cap = (size_t)16 << 20; f->arena_used = 0;
     }
     if (f->arena_used + need > f->arena_cap) return 0; // a very long call: the remaining epochs take the general kernel
@@ -503,10 +497,10 @@ static int try_periodic_epoch(redio_src *f, long first, long count, float *d_out
     // device side: one buffer [L | R | ints], same layout as the arena slice, one upload
     if (need > f->pL_cap) {
         hipFree(f->d_pL); f->d_pL = nullptr; f->pL_cap = 0;
-        SRC_TRY(hipMalloc((void **)&f->d_pL, 2 * need));
+        REDIO_TRY(hipMalloc((void **)&f->d_pL, 2 * need));
         f->pL_cap = 2 * need;
     }
-    SRC_TRY(hipMemcpyAsync(f->d_pL, L, need, hipMemcpyHostToDevice, st));
+    REDIO_TRY(hipMemcpyAsync(f->d_pL, L, need, hipMemcpyHostToDevice, st));
     const double *dL = f->d_pL, *dR = dL + nLd;
     const int *dI = reinterpret_cast<const int *>(dR + nRd);
     hipError_t e = launch_src_periodic(f->d_buf[f->cur], f->buf_stride, dL, dR, dI, dI + 256, dI + 512, P, Q, NL, NR,
@@ -545,7 +539,7 @@ static int flush_epoch(redio_src *f, long first, long count, float *d_out, long 
             if (src_uniform_lds(64, S, cl, cr)) {
                 int rc = prepare_uniform(f, inc);
                 if (rc) return rc;
-                SRC_TRY(launch_src_uniform(f->d_buf[f->cur], f->buf_stride, f->d_cl, f->ncl, f->d_cr, f->ncr, f->h_pos[(size_t)first], S,
+                REDIO_TRY(launch_src_uniform(f->d_buf[f->cur], f->buf_stride, f->d_cl, f->ncl, f->d_cr, f->ncr, f->h_pos[(size_t)first], S,
                                            f->h_scale[(size_t)first], d_out + first, out_stride, count, f->nchan, st));
                 return REDIO_OK;
             }
@@ -557,8 +551,8 @@ static int flush_epoch(redio_src *f, long first, long count, float *d_out, long 
         if (handled != 0) return handled;
     }
     ++f->general_launches;
-    SRC_TRY(hipMemcpyAsync(f->d_pos + first, f->h_pos + first, (size_t)count * sizeof(int), hipMemcpyHostToDevice, st));
-    SRC_TRY(hipMemcpyAsync(f->d_start + first, f->h_start + first, (size_t)count * sizeof(int), hipMemcpyHostToDevice, st));
+    REDIO_TRY(hipMemcpyAsync(f->d_pos + first, f->h_pos + first, (size_t)count * sizeof(int), hipMemcpyHostToDevice, st));
+    REDIO_TRY(hipMemcpyAsync(f->d_start + first, f->h_start + first, (size_t)count * sizeof(int), hipMemcpyHostToDevice, st));
     if (f->window_ok && !f->front_short) { // constant increment and scale, positions in order: the LDS-tile form of the general kernel
         const int inc = f->h_inc[(size_t)first];
         const double scale = f->h_scale[(size_t)first];
@@ -574,9 +568,9 @@ static int flush_epoch(redio_src *f, long first, long count, float *d_out, long 
             if (e != hipErrorNotSupported) return hip_rc(e);
         }
     }
-    SRC_TRY(hipMemcpyAsync(f->d_inc + first, f->h_inc + first, (size_t)count * sizeof(int), hipMemcpyHostToDevice, st));
-    SRC_TRY(hipMemcpyAsync(f->d_scale + first, f->h_scale + first, (size_t)count * sizeof(double), hipMemcpyHostToDevice, st));
-    SRC_TRY(launch_src_exact(f->d_buf[f->cur], f->buf_stride, f->d_coeffs, f->coeff_half_len, f->d_pos + first, f->d_start + first,
+    REDIO_TRY(hipMemcpyAsync(f->d_inc + first, f->h_inc + first, (size_t)count * sizeof(int), hipMemcpyHostToDevice, st));
+    REDIO_TRY(hipMemcpyAsync(f->d_scale + first, f->h_scale + first, (size_t)count * sizeof(double), hipMemcpyHostToDevice, st));
+    REDIO_TRY(launch_src_exact(f->d_buf[f->cur], f->buf_stride, f->d_coeffs, f->coeff_half_len, f->d_pos + first, f->d_start + first,
                              f->d_inc + first, f->d_scale + first, d_out + first, out_stride, count, f->nchan, st));
     return REDIO_OK;
 }
@@ -691,7 +685,7 @@ static int zoh_linear_impl(redio_src *f, const float *d_in, long in_stride, long
     const bool lin = f->converter == 4;
     if (input_frames <= 0) return REDIO_OK;
     if (f->zl_reset) { // just reset: the value "before" the stream is its first frame
-        SRC_TRY(launch_src_copy_rows(d_in, in_stride, 0, f->d_last, 1, 0, 1, f->nchan, st));
+        REDIO_TRY(launch_src_copy_rows(d_in, in_stride, 0, f->d_last, 1, 0, 1, f->nchan, st));
         f->zl_reset = 0;
     }
     int rc = ensure_scratch(f, (size_t)output_frames);
@@ -734,12 +728,12 @@ static int zoh_linear_impl(redio_src *f, const float *d_in, long in_stride, long
         in_used = in_count;
     }
     if (out_gen > 0) {
-        SRC_TRY(hipMemcpyAsync(f->d_pos, f->h_pos, (size_t)out_gen * sizeof(int), hipMemcpyHostToDevice, st));
-        SRC_TRY(hipMemcpyAsync(f->d_scale, f->h_scale, (size_t)out_gen * sizeof(double), hipMemcpyHostToDevice, st));
-        SRC_TRY(launch_src_zoh_linear(d_in, in_stride, f->d_last, f->d_pos, f->d_scale, d_out, out_stride, out_gen, f->nchan, lin, st));
+        REDIO_TRY(hipMemcpyAsync(f->d_pos, f->h_pos, (size_t)out_gen * sizeof(int), hipMemcpyHostToDevice, st));
+        REDIO_TRY(hipMemcpyAsync(f->d_scale, f->h_scale, (size_t)out_gen * sizeof(double), hipMemcpyHostToDevice, st));
+        REDIO_TRY(launch_src_zoh_linear(d_in, in_stride, f->d_last, f->d_pos, f->d_scale, d_out, out_stride, out_gen, f->nchan, lin, st));
     }
     f->last_position = input_index;
-    if (in_used > 0) SRC_TRY(launch_src_copy_rows(d_in, in_stride, in_used - 1, f->d_last, 1, 0, 1, f->nchan, st));
+    if (in_used > 0) REDIO_TRY(launch_src_copy_rows(d_in, in_stride, in_used - 1, f->d_last, 1, 0, 1, f->nchan, st));
     f->last_ratio = src_ratio;
     if (in_used_out) *in_used_out = in_used;
     if (out_gen_out) *out_gen_out = out_gen;
@@ -888,7 +882,7 @@ static int try_general_window(redio_src *f, const SrcInput &in, long in_count, f
     const int other = in_place ? f->cur : f->cur ^ 1;
     long j0 = in_place ? a_in0 : (long)b_current - f->front, j1 = b_end;
     if (j0 < 0) j0 = 0;
-    SRC_TRY(launch_src_window_image(f->d_buf[f->cur], f->buf_stride, in.dev, in.in_stride, a_in0, A0, j0, j1, f->d_buf[other], f->nchan, st));
+    REDIO_TRY(launch_src_window_image(f->d_buf[f->cur], f->buf_stride, in.dev, in.in_stride, a_in0, A0, j0, j1, f->d_buf[other], f->nchan, st));
     f->cur = other;
     f->b_current = b_current;
     f->b_end = b_end;
@@ -923,7 +917,7 @@ static int src_process_impl(redio_src *f, const SrcInput &in, long input_frames,
         if (need > f->rows_out_cap) {
             hipFree(f->d_rows_out);
             f->d_rows_out = nullptr; f->rows_out_cap = 0;
-            SRC_TRY(hipMalloc((void **)&f->d_rows_out, (need + 1024) * sizeof(float)));
+            REDIO_TRY(hipMalloc((void **)&f->d_rows_out, (need + 1024) * sizeof(float)));
             f->rows_out_cap = need + 1024;
         }
         d_packed = d_out;
@@ -933,7 +927,7 @@ static int src_process_impl(redio_src *f, const SrcInput &in, long input_frames,
     };
     auto pack_rows = [&](int code) -> int {
         if (code != REDIO_OK || !d_packed || *out_gen_out <= 0) return code;
-        SRC_TRY(launch_src_copy_rows(f->d_rows_out, out_stride, 0, d_packed, *out_gen_out, 0, *out_gen_out, f->nchan, st));
+        REDIO_TRY(launch_src_copy_rows(f->d_rows_out, out_stride, 0, d_packed, *out_gen_out, 0, *out_gen_out, f->nchan, st));
         return REDIO_OK;
     };
     if (f->converter >= 3) {
@@ -1040,11 +1034,6 @@ static int src_process_impl(redio_src *f, const SrcInput &in, long input_frames,
     return pack_rows(REDIO_OK);
 }
 
-static bool src_stream_is_capturing(hipStream_t st)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-}
 
 // redio_src_process without end_of_input and without the wait, where nothing needs one.  A call the single-launch uniform path serves
 // from tables that are already on the device passes everything to its kernels by value: the counts and the next buffer state come
@@ -1058,9 +1047,9 @@ extern "C" int redio_src_enqueue(redio_src *s, const void *d_in, long input_fram
     if (!s) return REDIO_SRC_ERR_BAD_STATE;
     if ((!d_in && input_frames > 0) || (!d_out && output_frames > 0)) return REDIO_SRC_ERR_BAD_DATA_PTR;
     if (in_stride < 0 || out_stride < 0) return REDIO_ERR_ARG;
-    SRC_TRY(hipSetDevice(s->device));
+    REDIO_TRY(hipSetDevice(s->device));
     // the state advances with every call: a replayed capture would repeat this call's offsets on a later call's data
-    if (src_stream_is_capturing((hipStream_t)stream)) return REDIO_ERR_UNSUPPORTED;
+    if (stream_capturing((hipStream_t)stream)) return REDIO_ERR_UNSUPPORTED;
     SrcInput in = {nullptr, (const float *)d_in, in_stride};
     s->zl_channels = 1; // rows are independent mono streams
     int launch_only = 0;
@@ -1094,7 +1083,7 @@ extern "C" int redio_src_process(redio_src *s, const void *d_in, long input_fram
     if (output_frames_gen) *output_frames_gen = 0;
     if (!s) return REDIO_SRC_ERR_BAD_STATE;
     if ((!d_in && input_frames > 0) || (!d_out && output_frames > 0)) return REDIO_SRC_ERR_BAD_DATA_PTR; // an empty side may be NULL in the batched form
-    SRC_TRY(hipSetDevice(s->device));
+    REDIO_TRY(hipSetDevice(s->device));
     SrcInput in = {nullptr, (const float *)d_in, in_stride};
     // pinned-free staging of the per-output parameters means the host arrays must stay untouched until
     // the uploads have run: synchronise at the end of the call (the uploads are tiny)
@@ -1126,20 +1115,20 @@ extern "C" int redio_src_process_host(redio_src *s, const float *data_in, long i
     } else if (data_out + output_frames * nch > data_in) {
         return REDIO_SRC_ERR_DATA_OVERLAP;
     }
-    SRC_TRY(hipSetDevice(s->device));
-    if (!s->host_stream) SRC_TRY(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
+    REDIO_TRY(hipSetDevice(s->device));
+    if (!s->host_stream) REDIO_TRY(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
     hipStream_t st = s->host_stream;
     const size_t out_elems = (size_t)output_frames * nch, in_elems = (size_t)input_frames * nch;
     if (out_elems > s->stage_out_cap) {
         hipFree(s->d_stage_out);
         s->d_stage_out = nullptr; s->stage_out_cap = 0;
-        SRC_TRY(hipMalloc((void **)&s->d_stage_out, (out_elems + 1024) * sizeof(float)));
+        REDIO_TRY(hipMalloc((void **)&s->d_stage_out, (out_elems + 1024) * sizeof(float)));
         s->stage_out_cap = out_elems + 1024;
     }
     if (nch > 1 && out_elems > s->rows_out_cap) {
         hipFree(s->d_rows_out);
         s->d_rows_out = nullptr; s->rows_out_cap = 0;
-        SRC_TRY(hipMalloc((void **)&s->d_rows_out, (out_elems + 1024) * sizeof(float)));
+        REDIO_TRY(hipMalloc((void **)&s->d_rows_out, (out_elems + 1024) * sizeof(float)));
         s->rows_out_cap = out_elems + 1024;
     }
     SrcInput in = {nch == 1 ? data_in : nullptr, nullptr, 0};
@@ -1147,20 +1136,20 @@ extern "C" int redio_src_process_host(redio_src *s, const float *data_in, long i
         if (in_elems > s->stage_in_cap) {
             hipFree(s->d_stage_in);
             s->d_stage_in = nullptr; s->stage_in_cap = 0;
-            SRC_TRY(hipMalloc((void **)&s->d_stage_in, (in_elems + 1024) * sizeof(float)));
+            REDIO_TRY(hipMalloc((void **)&s->d_stage_in, (in_elems + 1024) * sizeof(float)));
             s->stage_in_cap = in_elems + 1024;
         }
-        SRC_TRY(hipMemcpyAsync(s->d_stage_in, data_in, in_elems * sizeof(float), hipMemcpyHostToDevice, st));
+        REDIO_TRY(hipMemcpyAsync(s->d_stage_in, data_in, in_elems * sizeof(float), hipMemcpyHostToDevice, st));
         if (nch == 1) {
             in = {nullptr, s->d_stage_in, (long)s->stage_in_cap};
         } else {
             if (in_elems > s->rows_in_cap) {
                 hipFree(s->d_rows_in);
                 s->d_rows_in = nullptr; s->rows_in_cap = 0;
-                SRC_TRY(hipMalloc((void **)&s->d_rows_in, (in_elems + 1024) * sizeof(float)));
+                REDIO_TRY(hipMalloc((void **)&s->d_rows_in, (in_elems + 1024) * sizeof(float)));
                 s->rows_in_cap = in_elems + 1024;
             }
-            SRC_TRY(launch_src_interleave(s->d_stage_in, s->d_rows_in, input_frames, input_frames, (int)nch, true, st));
+            REDIO_TRY(launch_src_interleave(s->d_stage_in, s->d_rows_in, input_frames, input_frames, (int)nch, true, st));
             in = {nullptr, s->d_rows_in, input_frames};
         }
     }

@@ -24,8 +24,6 @@
 #include <atomic>
 #include <new>
 
-static inline int hip_rc(hipError_t e) { return e == hipSuccess ? REDIO_OK : REDIO_ERR_HIP_BASE - (int)e; }
-#define SC_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return hip_rc(_e); } while (0)
 
 namespace {
 // The seam copies (at most W - 1 samples: 42 KB for the chain) as a kernel of this library instead of a device-to-device hipMemcpyAsync.
@@ -137,7 +135,7 @@ int carry_enqueue(Carry *c, const void *d_new, size_t n, void *d_out, size_t *no
     if (!guard.ok()) return REDIO_ERR_ARG; // another thread is inside this stream: its counters are not ours to move
     if (n == 0) return REDIO_OK;
     if (!d_new) return REDIO_ERR_ARG;
-    SC_TRY(hipSetDevice(c->device));
+    REDIO_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     const char *src = (const char *)d_new;
     const size_t n_call = n;
@@ -153,12 +151,12 @@ int carry_enqueue(Carry *c, const void *d_new, size_t n, void *d_out, size_t *no
     // new tail where it lies instead of copying it to the other buffer's front).  When this call's samples no longer fit behind it, the tail
     // moves to the other buffer's front first; that only re-seats the same samples, so it is committed at once.
     if (c->hist > 0 && c->off + c->hist + m > 2 * c->W) {
-        SC_TRY(seam_copy(c->d_s[c->cur ^ 1], c->d_s[c->cur] + c->off * c->in_elem, c->hist * c->in_elem, st));
+        REDIO_TRY(seam_copy(c->d_s[c->cur ^ 1], c->d_s[c->cur] + c->off * c->in_elem, c->hist * c->in_elem, st));
         c->cur ^= 1;
         c->off = 0;
     }
     char *S = c->d_s[c->cur] + c->off * c->in_elem, *T = c->d_s[c->cur ^ 1];
-    if (c->hist > 0 && m > 0) SC_TRY(seam_copy(S + c->hist * c->in_elem, src, m * c->in_elem, st));
+    if (c->hist > 0 && m > 0) REDIO_TRY(seam_copy(S + c->hist * c->in_elem, src, m * c->in_elem, st));
     char *out = (char *)d_out;
     if (s.nh) {
         const int rc = run(*c, S, s.head_in, out, stream);
@@ -177,17 +175,17 @@ int carry_enqueue(Carry *c, const void *d_new, size_t n, void *d_out, size_t *no
     } else {
         new_hist = c->hist + n - consumed;
         if (consumed >= c->hist) { // lies entirely in the caller's buffer
-            if (new_hist) SC_TRY(seam_copy(T, src + (consumed - c->hist) * c->in_elem, new_hist * c->in_elem, st));
+            if (new_hist) REDIO_TRY(seam_copy(T, src + (consumed - c->hist) * c->in_elem, new_hist * c->in_elem, st));
             flip = true;
         } else if (c->hist == 0) { // a first piece shorter than a window
-            SC_TRY(seam_copy(T, src, n * c->in_elem, st));
+            REDIO_TRY(seam_copy(T, src, n * c->in_elem, st));
             flip = true;
         } else if ((consumed * c->in_elem) % 16 == 0) {
             // starts inside the old tail: then n < W - 1 and the staging buffer holds all of [tail | new] -- the new tail stays where it is
             // (round 6: one dependent operation less per small message; 16-byte alignment of the next call's window kept)
             new_off = c->off + consumed;
         } else {
-            SC_TRY(seam_copy(T, S + consumed * c->in_elem, new_hist * c->in_elem, st));
+            REDIO_TRY(seam_copy(T, S + consumed * c->in_elem, new_hist * c->in_elem, st));
             flip = true;
         }
     }

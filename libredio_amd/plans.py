@@ -72,6 +72,10 @@ class Fft:
         self._h = C.c_void_p()
         check(lib().redio_fft_create(C.byref(self._h), self.nfft, int(bool(inverse))), "fft_create")
 
+    def reserve(self, nbatch):
+        """redio_fft_reserve: the staging buffer of the sizes that need one, for calls of up to nbatch messages (before a graph capture)."""
+        check(lib().redio_fft_reserve(self._h, nbatch), "fft_reserve")
+
     def __call__(self, x, out=None):
         import torch
         assert x.dtype == torch.complex64 and x.numel() % self.nfft == 0, "messages of exactly nfft samples"

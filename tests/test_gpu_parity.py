@@ -133,7 +133,7 @@ CT_SIZES = [9, 10, 12, 15, 18, 20, 24, 25, 27, 30, 36, 40, 45, 48, 50, 54, 60, 7
 
 @pytest.mark.parametrize("n", CT_SIZES)
 def test_fft_compile_time_mixed_radix_sizes(gpu, redio, oracle, n):
-    # every 2^a 3^b 5^c size that has its own compile-time kernel (fft_kernels.hip, REDIO_CT list), ragged batch counts
+    # every 2^a 3^b 5^c size that has its own compile-time kernel (fft_ct.h, the REDIO_FFT_CT_SIZES list of fft_route.h), ragged batch counts
     nb = 7 if n < 2000 else 3
     x = oracle.synth_iq(n + 17, 0, n * nb)
     d = gpu.from_numpy(x).cuda()
