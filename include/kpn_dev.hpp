@@ -1013,5 +1013,33 @@ inline void power_spectrum_stream(Receiver<View<std::complex<float>>> u, Sender<
                                            [&](const View<cf> &d, float *o, size_t *got, void *st) { return redio_pspec_stream_enqueue(s, d.data(), d.len, o, got, st); });
 }
 
+// the receiver's messages straight into the power spectrum: u8 I/Q bytes (rtlsdr::rtlSource, rtlsdr.rs:127-152) -> data_to_samples
+// (rtlsdr.rs:159-162) -> the block above, without the cf32 intermediate (redio_pspec_enqueue_u8: ONE kernel at nfft = 1024); a
+// message holds whole samples (an even byte count)
+inline void power_spectrum_u8(Receiver<View<uint8_t>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {})
+{
+    redio_pspec *h = nullptr;
+    check(redio_pspec_create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
+    struct G { redio_pspec *h; ~G() { redio_pspec_destroy(h); } } g{h};
+    detail::run_block<uint8_t, float>(u, v, [&](const View<uint8_t> &d) { return redio_pspec_nrows(h, d.len / 2) * (size_t)nfft; },
+                                      [&](const View<uint8_t> &d, const View<float> &o, void *st) { return redio_pspec_enqueue_u8(h, d.data(), d.len, o.data(), st); });
+}
+
+// the same as a STREAM (redio_pspec_stream_create_u8: the history is carried as bytes)
+inline void power_spectrum_stream_u8(Receiver<View<uint8_t>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {})
+{
+    redio_pspec *h = nullptr;
+    check(redio_pspec_create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
+    redio_pspec_stream *s = nullptr;
+    const int rc = redio_pspec_stream_create_u8(&s, h);
+    struct G { redio_pspec *h; redio_pspec_stream *s; ~G() { redio_pspec_stream_destroy(s); redio_pspec_destroy(h); } } g{h, s};
+    check(rc);
+    detail::run_stream_block_of<uint8_t, float>(u, v, [&](size_t len) { return redio_pspec_stream_nout(s, len / 2); },
+                                                [&](const View<uint8_t> &d, float *o, size_t *got, void *st) {
+                                                    if (d.len & 1) return (int)REDIO_ERR_ARG;
+                                                    return redio_pspec_stream_enqueue(s, d.data(), d.len / 2, o, got, st);
+                                                });
+}
+
 } // namespace dev
 } // namespace kpn

@@ -216,6 +216,21 @@ int redio_pspec_reserve(redio_pspec *h, size_t n_in);
 int redio_pspec_enqueue(redio_pspec *h, const void *d_in_c32, size_t n_in, void *d_out_f32, void *stream);
 int redio_pspec_enqueue_spectra(redio_pspec *h, const void *d_spectra_c32, size_t nbatch, void *d_out_f32, void *stream);
 int redio_pspec_set_split(redio_pspec *h, int mode);
+/* The receiver's own format in: interleaved u8 I/Q bytes (rtlsdr::data_to_samples, src/rtlsdr/src/rtlsdr.rs:159-162) straight into the
+ * plan -- nbytes / 2 samples, redio_pspec_nrows(h, nbytes / 2) rows, bit for bit the rows redio_data_to_samples + redio_pspec_enqueue
+ * would give on every plan and in every redio_pspec_set_split mode (convert, then the window multiply rounded on its own, then the
+ * transform and the blocked sum above).  N = 1024 is ONE kernel that converts at the load: 2 N / step bytes read and 4 / K written per
+ * sample, no scratch beyond the segment partials.  At N = 2048 and 4096 the plan's transform converts (and windows) at its own load
+ * and writes the spectra into the plan's row scratch; every other size converts inside the row gather into that scratch.  There is
+ * never a whole-message cf32 buffer.
+ * enqueue_u8: launches only, on the caller's stream; every argument is checked before anything is launched.  Odd nbytes, NULL or
+ *   overlapping buffers, d_bytes not 2-byte (a whole sample) or d_out not 4-byte aligned -> REDIO_ERR_ARG; fewer than W samples ->
+ *   REDIO_OK, no launch.
+ * reserve_u8(h, nbytes) sizes the scratch (the in-place transform's staging included) for u8 calls of up to nbytes bytes, after which
+ *   an enqueue_u8 neither allocates nor synchronises; un-reserved it grows on first use (REDIO_ERR_NOT_RESERVED while the stream is
+ *   being captured). */
+int redio_pspec_enqueue_u8(redio_pspec *h, const void *d_bytes, size_t nbytes, void *d_out_f32, void *stream);
+int redio_pspec_reserve_u8(redio_pspec *h, size_t nbytes);
 
 /* ---- C2 chain: FIR (ntaps, decimate decim) -> nfft-point forward FFT of consecutive blocks ----
  * Fused single kernel for nfft = 1024 with (ntaps, decim) in {(127, 5), (127, 3), (127, 1), (63, 5), (63, 1)} on a
@@ -414,7 +429,8 @@ int redio_pfb_exchange_all(redio_comm *const *comms, int ndev, const void *const
  *             needs 4-byte alignment only -- messages may have any length, odd ones included -- and d_out 8-byte alignment)
  *     pspec:  row r from the W = (integrate - 1) step + nfft samples that start at r * integrate * step; *nout counts f32 words
  *             (whole rows of nfft).  The staging buffers hold fewer than W samples each side of a seam -- 8 MiB of history at
- *             nfft = integrate = 1024 -- so a long integration costs that much device memory per stream handle.
+ *             nfft = integrate = 1024 -- so a long integration costs that much device memory per stream handle.  (A u8 stream,
+ *             redio_pspec_stream_create_u8, carries the same samples as bytes: a quarter of that.)
  * enqueue() writes *nout (= redio_*_stream_nout(h, n_new), known before the call) output samples to d_out; the new
  * samples are read in place (only a seam of fewer than one window is staged through a plan-owned buffer).  It only
  * launches kernels and small device copies -- with one exception: a plan shape that runs as two kernels (redio_chain_is_fused() == 0,
@@ -470,6 +486,11 @@ int redio_pspec_stream_reset(redio_pspec_stream *h);
 size_t redio_pspec_stream_nout(const redio_pspec_stream *h, size_t n_new);
 size_t redio_pspec_stream_pending(const redio_pspec_stream *h);
 int redio_pspec_stream_enqueue(redio_pspec_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
+/* the power-spectrum stream fed with the receiver's interleaved u8 I/Q bytes, as the chain / channelizer ones above: d_new points to
+ * bytes (2-byte aligned: an odd address is REDIO_ERR_ARG before anything is launched), n_new still counts SAMPLES; the history is carried as bytes and every window runs redio_pspec_enqueue_u8.
+ * Create reserves for the seam windows (redio_pspec_reserve_u8(plan, largest message's bytes + 2 W) keeps longer bodies allocation-free).
+ * All other redio_pspec_stream_* calls apply unchanged. */
+int redio_pspec_stream_create_u8(redio_pspec_stream **h, redio_pspec *plan);
 
 /* ---- A6: samplerate::resample's native side, src/samplerate/src/samplerate.rs:59-87 ----
  * nchan independent mono streams that share ratio and block lengths (the reference creates one

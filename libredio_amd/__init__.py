@@ -130,7 +130,7 @@ def lib():
         _sig(getattr(L, f"redio_{n}_stream_nout"), sz, vp, sz)
         _sig(getattr(L, f"redio_{n}_stream_pending"), sz, vp)
         _sig(getattr(L, f"redio_{n}_stream_enqueue"), i, vp, vp, sz, vp, C.POINTER(sz), vp)
-    for n in ("chain", "pfb"):
+    for n in ("chain", "pfb", "pspec"):
         _sig(getattr(L, f"redio_{n}_stream_create_u8"), i, C.POINTER(vp), vp)
     _sig(L.redio_chain_enqueue, i, vp, vp, sz, vp, vp)
     _sig(L.redio_chain_enqueue_u8, i, vp, vp, sz, vp, vp)
@@ -173,6 +173,8 @@ def lib():
     _sig(L.redio_pspec_enqueue, i, vp, vp, sz, vp, vp)
     _sig(L.redio_pspec_enqueue_spectra, i, vp, vp, sz, vp, vp)
     _sig(L.redio_pspec_set_split, i, vp, i)
+    _sig(L.redio_pspec_enqueue_u8, i, vp, vp, sz, vp, vp)
+    _sig(L.redio_pspec_reserve_u8, i, vp, sz)
     psz = C.POINTER(sz)
     _sig(L.redio_data_to_samples, i, vp, sz, vp, vp)
     _sig(L.redio_norm_c32, i, vp, sz, vp, vp)

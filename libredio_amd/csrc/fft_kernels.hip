@@ -2318,6 +2318,85 @@ hipError_t launch_ovsave16k(const float2 *x, long hop, const float2 *tw_f, const
     return hipGetLastError();
 }
 
+// ---- the one-wave transforms fed with u8 I/Q bytes (redio_pspec_enqueue_u8): siblings of fft2k_wave_kernel / fft4k_wave_kernel whose
+// load converts (i2f: rtlsdr.rs:159-162) and, with a window, multiplies (rounded on its own) -- the bits of redio_data_to_samples, the
+// window multiply and the kernel above, without the cf32 row in between.  in: one little-endian 16-bit word per sample (I low, Q high),
+// 2-byte aligned; transform xf starts at in + xf in_stride; win: N values; forward only.
+template <bool WIN>
+__device__ __forceinline__ float2 fft_ld_iq(const uint16_t *src, const float *__restrict__ win, unsigned e)
+{
+    const unsigned w = src[e];
+    float2 v = make_float2(i2f(w & 255u), i2f(w >> 8));
+    if (WIN) {
+        const float wn = win[e];
+        v = make_float2(mul_rn(v.x, wn), mul_rn(v.y, wn));
+    }
+    return v;
+}
+template <bool WIN>
+__global__ __launch_bounds__(256, 2) void fft4k_wave_u8_kernel(const uint16_t *__restrict__ in, const float *__restrict__ win, float2 *__restrict__ out,
+                                                               const float2 *__restrict__ tw, long nbatch, long in_stride)
+{
+    __shared__ float2 Ls[4 * F4W_REGION];
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long xf = (long)blockIdx.x * 4 + w;
+    if (xf >= nbatch) return; // wave-uniform
+    const uint16_t *src = in + xf * in_stride;
+    float2 *dst = out + xf * 4096;
+    float2 a[4][16], b[4][16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) a[i][j] = fft_ld_iq<WIN>(src, win, 1024u * (j & 3) + 256u * (j >> 2) + 64u * i + (unsigned)lane);
+    RD_SCHED_BARRIER();
+    fft4k_wave_regs<false>(a, b, TwProgram<4096, 1>{tw}, Ls + w * F4W_REGION, lane);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) (dst + 1024 * (j >> 2) + 256 * (j & 3) + 64 * i)[(unsigned)lane] = a[i][j];
+}
+template <bool WIN>
+__global__ __launch_bounds__(256) void fft2k_wave_u8_kernel(const uint16_t *__restrict__ in, const float *__restrict__ win, float2 *__restrict__ out,
+                                                            const float2 *__restrict__ tw, long nbatch, long in_stride)
+{
+    __shared__ float2 Ls[4 * F4W_REGION];
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long xf = (long)blockIdx.x * 4 + w;
+    if (xf >= nbatch) return; // wave-uniform
+    const uint16_t *src = in + xf * in_stride;
+    float2 *dst = out + xf * 2048;
+    float2 a[4][8], b[2][16];
+#pragma unroll
+    for (int d2 = 0; d2 < 4; ++d2)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a[d2][j] = fft_ld_iq<WIN>(src, win, 64u * (d2 + 4 * (j >> 1) + 16 * (j & 1)) + (unsigned)lane); // j = b0 + 2 d1
+    RD_SCHED_BARRIER();
+    fft2k_wave_regs<false>(a, b, TwProgram<2048, 2>{tw}, Ls + w * F4W_REGION, lane);
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) (dst + 128 * (j & 3) + 512 * (j >> 2) + 64 * r)[(unsigned)lane] = b[r][j];
+}
+// whether the plan's transform has a u8-input sibling: the forward one-wave sizes (2048, 4096)
+bool fft_u8_supported(const FftPlanDev &p)
+{
+    return !p.inverse && p.tw_pass && fft_route(p.nfft, p.st, p.nstages).route == FFT_ROUTE_ONE_WAVE;
+}
+hipError_t launch_fft_u8(const FftPlanDev &p, const uint16_t *in, const float *win, float2 *out, long nbatch, long in_stride, hipStream_t s)
+{
+    if (!fft_u8_supported(p)) return hipErrorNotSupported;
+    if (nbatch <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)((nbatch + 3) / 4);
+    if (p.nfft == 2048) {
+        if (win) hipLaunchKernelGGL(fft2k_wave_u8_kernel<true>, dim3(grid), dim3(256), 0, s, in, win, out, p.tw_pass, nbatch, in_stride);
+        else hipLaunchKernelGGL(fft2k_wave_u8_kernel<false>, dim3(grid), dim3(256), 0, s, in, win, out, p.tw_pass, nbatch, in_stride);
+    } else {
+        if (win) hipLaunchKernelGGL(fft4k_wave_u8_kernel<true>, dim3(grid), dim3(256), 0, s, in, win, out, p.tw_pass, nbatch, in_stride);
+        else hipLaunchKernelGGL(fft4k_wave_u8_kernel<false>, dim3(grid), dim3(256), 0, s, in, win, out, p.tw_pass, nbatch, in_stride);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_fft(const FftPlanDev &p, const float2 *in, float2 *out, long nbatch, hipStream_t s, long in_stride, float2 *work)
 {
     if (in_stride <= 0) in_stride = p.nfft; // consecutive messages; smaller strides give overlapping blocks (overlap-save)

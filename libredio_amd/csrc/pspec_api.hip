@@ -7,6 +7,10 @@
 //                segment instead of a whole row
 //   other N      [row gather with window ->] the plan's own redio_fft -> accumulate -> fold, through plan-owned scratch, in chunks
 //                of whole segments
+// redio_pspec_enqueue_u8 is the same plan fed with the receiver's interleaved u8 I/Q bytes (rtlsdr.rs:159-162), bit for bit
+// redio_data_to_samples + redio_pspec_enqueue: N = 1024 is the fused kernel with the conversion at the load (2 N / step bytes read
+// per sample); at 2048 and 4096 the plan's one-wave transform has a sibling that converts and windows at its own load
+// (fft_kernels.hip, launch_fft_u8); every other N converts inside the row gather -- there is never a whole-message cf32 buffer.
 #include "../../include/redio.h"
 #include "redio_internal.h"
 #include "pspec_core.h"
@@ -23,6 +27,9 @@ struct redio_pspec {
     bool fused;            // N = 1024: one kernel
     bool packs;            // generic path: rows are gathered (window or step != N) before the transform, which then runs in place
     bool fft_stages;       // the plan's transform stages through a buffer of its own at this size (redio_fft_reserve)
+    bool fft_stages_packed; // the same for a packed chunk transformed in place: what a u8 call runs on every plan (== fft_stages when packs)
+    size_t packed_cap;     // transforms per pass for which the in-place transform's staging has been reserved
+    bool fft_u8;           // the transform has a sibling that converts (and windows) bytes at its own load (2048, 4096): a u8 call needs no gather
     int split;             // 0 auto, 1 one wave / thread group per row, 2 one per segment
     redio_fft *fft;
     float *d_win;          // N window values, or null
@@ -47,6 +54,9 @@ extern "C" int redio_pspec_create(redio_pspec **h, int nfft, size_t integrate, s
     p->packs = window_host != nullptr || step != (size_t)nfft;
     p->split = 0; p->fft = fft; p->d_win = nullptr; p->d_rows = p->d_part = nullptr; p->rows_cap = p->part_cap = 0;
     p->fft_stages = redio_fft_stages(fft, p->packs); // a packed chunk is transformed in place
+    p->fft_u8 = fft_u8_supported(*redio_fft_plan_dev(fft));
+    p->fft_stages_packed = !p->fft_u8 && redio_fft_stages(fft, true);
+    p->packed_cap = 0;
     // at most 64 MiB of cf32 rows per chunk (the overlap-save operators' work-buffer size), a whole number of segments, at least one
     p->chunk_segs = ((size_t)64 << 20) / ((size_t)nfft * sizeof(float2) * PSPEC_SEG);
     if (p->chunk_segs < 1) p->chunk_segs = 1;
@@ -106,7 +116,8 @@ static size_t rows_needed(const redio_pspec *h, size_t nrows)
     return all < most ? all : most;
 }
 
-static int reserve_rows(redio_pspec *h, size_t nrows, bool fused_kernel, bool transforms)
+// packed: sized for a u8 call, which gathers rows and transforms them in place on every plan
+static int reserve_rows(redio_pspec *h, size_t nrows, bool fused_kernel, bool transforms, bool packed = false)
 {
     if (nrows == 0) return REDIO_OK;
     REDIO_TRY(hipSetDevice(h->device));
@@ -114,8 +125,10 @@ static int reserve_rows(redio_pspec *h, size_t nrows, bool fused_kernel, bool tr
         if (int rc = scratch_grow(&h->d_part, &h->part_cap, nrows * h->S * (size_t)h->nfft, sizeof(float))) return rc;
     if (!transforms) return REDIO_OK;
     const size_t ntr = rows_needed(h, nrows);
-    if (h->fft_stages)
+    if (packed ? h->fft_stages_packed : h->fft_stages) {
         if (int rc = redio_fft_reserve(h->fft, ntr)) return rc;
+        if ((packed || h->packs) && ntr > h->packed_cap) h->packed_cap = ntr;
+    }
     return scratch_grow(&h->d_rows, &h->rows_cap, ntr * (size_t)h->nfft, sizeof(float2));
 }
 
@@ -169,6 +182,58 @@ extern "C" int redio_pspec_enqueue(redio_pspec *h, const void *d_in, size_t n_in
                 if (int rc = redio_fft_enqueue(h->fft, rows, rows, ntr, stream)) return rc;
             } else {
                 if (int rc = redio_fft_enqueue(h->fft, x + (size_t)g0 * N, rows, ntr, stream)) return rc;
+            }
+            if (int rc = accumulate(h, rows, q0, q1, g0, out, split, st)) return rc;
+        }
+    }
+    if (split) REDIO_TRY(launch_pspec_fold((const float *)h->d_part, out, (long)nrows, (long)N, (long)h->S, st));
+    return REDIO_OK;
+}
+
+extern "C" int redio_pspec_reserve_u8(redio_pspec *h, size_t nbytes)
+{
+    if (!h) return REDIO_ERR_ARG;
+    return reserve_rows(h, redio_pspec_nrows(h, nbytes / 2), false, !h->fused, true);
+}
+
+extern "C" int redio_pspec_enqueue_u8(redio_pspec *h, const void *d_bytes, size_t nbytes, void *d_out, void *stream)
+{
+    if (!h || (nbytes & 1)) return REDIO_ERR_ARG;
+    const size_t nrows = redio_pspec_nrows(h, nbytes / 2);
+    if (nrows == 0) return REDIO_OK;
+    if (!d_bytes || !d_out || ((uintptr_t)d_bytes & 1) || ((uintptr_t)d_out & 3)) return REDIO_ERR_ARG; // a sample-aligned pointer, as the cf32 entry asks for 8
+    const size_t N = (size_t)h->nfft;
+    const char *a = (const char *)d_bytes, *o = (const char *)d_out; // the ranges read and written must not overlap
+    if (a < o + nrows * N * sizeof(float) && o < a + nbytes) return REDIO_ERR_ARG;
+    REDIO_TRY(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint16_t *x = (const uint16_t *)d_bytes; // one word per sample
+    float *out = (float *)d_out;
+    const bool split = splits(h, nrows, h->fused);
+    const size_t pass = rows_needed(h, nrows);
+    const bool short_part = split && nrows * h->S * N > h->part_cap;
+    const bool short_rows = !h->fused && (pass * N > h->rows_cap || (h->fft_stages_packed && pass > h->packed_cap));
+    if (short_part || short_rows) { // grown on first use unless redio_pspec_reserve_u8() sized it; never during graph capture
+        if (stream_capturing(st)) return REDIO_ERR_NOT_RESERVED;
+        if (int rc = reserve_rows(h, nrows, h->fused, !h->fused, true)) return rc;
+    }
+    if (h->fused) {
+        REDIO_TRY(launch_pspec1k_u8(x, (long)h->step, (long)h->K, h->d_win, redio_fft_twiddles_dev(h->fft), split ? (float *)h->d_part : out,
+                                 (long)(split ? nrows * h->S : nrows), split, st));
+    } else {
+        const size_t nseg = nrows * h->S;
+        float2 *rows = (float2 *)h->d_rows;
+        for (size_t q0 = 0; q0 < nseg; q0 += h->chunk_segs) {
+            const size_t q1 = nseg - q0 < h->chunk_segs ? nseg : q0 + h->chunk_segs;
+            long g0, g1, cnt;
+            pspec_segment((long)q0, (long)h->K, (long)h->S, g0, cnt);
+            pspec_segment((long)q1 - 1, (long)h->K, (long)h->S, g1, cnt);
+            const size_t ntr = (size_t)(g1 + cnt - g0);
+            if (h->fft_u8) { // the transform converts and windows at its own load: bytes in, spectra out
+                REDIO_TRY(launch_fft_u8(*redio_fft_plan_dev(h->fft), x + (size_t)g0 * h->step, h->d_win, rows, (long)ntr, (long)h->step, st));
+            } else {
+                REDIO_TRY(launch_pspec_rows_u8(x + (size_t)g0 * h->step, h->d_win, rows, (long)ntr, (long)N, (long)h->step, st));
+                if (int rc = redio_fft_enqueue(h->fft, rows, rows, ntr, stream)) return rc;
             }
             if (int rc = accumulate(h, rows, q0, q1, g0, out, split, st)) return rc;
         }

@@ -6,7 +6,7 @@
 //     seg_s[k]  = ((p_16s + p_16s+1) + ...)         t in [16 s, min(16 s + 16, K)), a left fold that starts from its first term
 //     out[r][k] = ((seg_0 + seg_1) + ...)           a left fold in ascending s
 //
-// Host-compilable (tests/emu_pspec runs the same programs on the CPU).
+// Host-compilable (tests/emu_pspec and tests/emu_pspec_u8 run the same programs on the CPU).
 #pragma once
 #include "fft_core.h"
 
@@ -107,7 +107,43 @@ RD_HD void pspec1k_store(const float (&row)[16], OutPtr dst, int lane)
         for (int j = 0; j < 4; ++j) dst[lane + 64 * q + 256 * j] = row[4 * q + j];
 }
 
+// ---- the same kernel fed with the receiver's interleaved u8 I/Q bytes (redio_pspec_enqueue_u8): a sample is one little-endian 16-bit
+// word, I in the low byte and Q in the high one (rtlsdr.rs:159-162), so a transform that starts on any sample is 2-byte aligned and
+// a wave-wide 16-bit load covers 128 contiguous bytes.  x: 16-bit words.
+RD_HD float2 pspec_iq(unsigned word) { return make_float2(i2f(word & 0xffu), i2f((word >> 8) & 0xffu)); }
+template <typename BPtr>
+RD_HD void pspec1k_load_raw(uint16_t (&r)[16], BPtr x, int lane)
+{
+#pragma unroll
+    for (int t = 0; t < 16; ++t) r[t] = x[lane + 64 * t];
+}
+RD_HD void pspec1k_convert(float2 (&v)[16], const uint16_t (&r)[16])
+{
+#pragma unroll
+    for (int t = 0; t < 16; ++t) v[t] = pspec_iq(r[t]);
+}
+
 // ---- the generic passes' thread programs
+// the row gather from bytes: element n of row b = sample b step + n converted, times win[n] when there is a window
+template <typename BPtr, typename WPtr>
+RD_HD float2 pspec_rows_u8_thread(BPtr x, WPtr win, bool windowed, long b, long n, long step)
+{
+    float2 v = pspec_iq(x[b * step + n]);
+    if (windowed) {
+        const float wn = win[n];
+        v = make_float2(mul_rn(v.x, wn), mul_rn(v.y, wn));
+    }
+    return v;
+}
+// lane step q of the gather: elements 2 q and 2 q + 1 of the packed rows, which share one 16-byte store (the second may open the next row)
+template <typename BPtr, typename WPtr>
+RD_HD void pspec_rows_u8_pair(BPtr x, WPtr win, bool windowed, unsigned q, unsigned N, long step, float2 &v0, float2 &v1)
+{
+    const unsigned i = 2 * q, b = i / N, n = i - b * N;
+    const bool wraps = n + 1 == N;
+    v0 = pspec_rows_u8_thread(x, win, windowed, (long)b, (long)n, step);
+    v1 = pspec_rows_u8_thread(x, win, windowed, (long)(wraps ? b + 1 : b), (long)(wraps ? 0 : n + 1), step);
+}
 // spec: the segment's first spectrum (rows of N bins); returns seg[k]
 template <typename SPtr>
 RD_HD float pspec_accum_thread(SPtr spec, long N, long cnt, long k)

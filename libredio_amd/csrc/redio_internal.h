@@ -84,6 +84,10 @@ hipError_t fftbig_tables_build(const float2 *tw, float2 *tables, int nfft, hipSt
 // launches.  hipErrorNotSupported: no kernel for this plan
 hipError_t launch_fft(const FftPlanDev &p, const float2 *in, float2 *out, long nbatch, hipStream_t s, long in_stride = 0,
                       float2 *work = nullptr);
+// the forward one-wave transforms (2048, 4096) with u8 I/Q bytes in: in holds one 16-bit word per sample (2-byte aligned), transform xf
+// starts at in + xf in_stride, win is null or nfft values multiplied in after the conversion; hipErrorNotSupported for every other plan
+bool fft_u8_supported(const FftPlanDev &p);
+hipError_t launch_fft_u8(const FftPlanDev &p, const uint16_t *in, const float *win, float2 *out, long nbatch, long in_stride, hipStream_t s);
 #pragma GCC visibility push(hidden)
 template <int N> // fft_ct.h, instantiated for the sizes of REDIO_FFT_CT_SIZES by fft_ct_lo.hip / fft_ct_hi.hip
 hipError_t launch_fft_ct(const FftPlanDev &p, const float2 *in, float2 *out, long nbatch, long in_stride, bool inv, hipStream_t s);
@@ -115,6 +119,9 @@ hipError_t launch_ovsave_real_rows(const float *x, float *rows, long nblk, long 
 // transform g_base; dst: N f32 per segment of the call) and the fold of S partials per row (pspec_api.hip).
 hipError_t launch_pspec1k(const float2 *x, long step, long K, const float *win, const float2 *tw, float *dst, long nunits, bool split, hipStream_t s);
 hipError_t launch_pspec_rows(const float2 *x, const float *win, float2 *rows, long ntr, long N, long step, hipStream_t s);
+// the two entry kernels on u8 I/Q bytes: x holds one 16-bit word per sample (2-byte aligned)
+hipError_t launch_pspec1k_u8(const uint16_t *x, long step, long K, const float *win, const float2 *tw, float *dst, long nunits, bool split, hipStream_t s);
+hipError_t launch_pspec_rows_u8(const uint16_t *x, const float *win, float2 *rows, long ntr, long N, long step, hipStream_t s);
 hipError_t launch_pspec_accum(const float2 *spec, float *dst, long q0, long nseg, long N, long K, long g_base, hipStream_t s);
 hipError_t launch_pspec_fold(const float *part, float *out, long nrows, long N, long S, hipStream_t s);
 

@@ -8,7 +8,7 @@
 //     chain        W = (nfft-1)*decim + ntaps      H = nfft*decim     unit = 1 spectrum (nfft samples)
 //     channelizer  W = nchan*taps_per_branch       H = nchan          unit = 1 row (nchan samples)
 //     overlap-save W = nfft                        H = hop            unit = hop output samples (cf32, or f32 for the real operator)
-//     power spectrum W = (integrate-1)*step + nfft H = integrate*step unit = 1 row (nfft f32 from cf32 samples)
+//     power spectrum W = (integrate-1)*step + nfft H = integrate*step unit = 1 row (nfft f32 from cf32 samples, or from u8 I/Q byte pairs)
 // so one layer serves them all.  The handle keeps the stream's unconsumed tail (fewer than W samples) on the device.
 // A call with n new samples
 //   1. appends the first min(n, W-1) new samples to the tail in a plan-owned staging buffer (one small copy),
@@ -54,7 +54,7 @@ hipError_t seam_copy(void *dst, const void *src, size_t bytes, hipStream_t st)
     SEAM_GO(uint8_t)
 #undef SEAM_GO
 }
-enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC }; // _U8: the samples are interleaved u8 I/Q byte pairs
+enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8 }; // _U8: the samples are interleaved u8 I/Q byte pairs
 struct Carry {
     int device = 0;
     Kind kind = K_FIR;
@@ -91,6 +91,7 @@ int run(const Carry &c, const void *d_in, size_t n_in, void *d_out, void *stream
     case K_CHAIN_U8: return redio_chain_enqueue_u8((redio_chain *)c.plan, d_in, 2 * n_in, d_out, stream);
     case K_PFB_U8: return redio_pfb_enqueue_u8((redio_pfb *)c.plan, d_in, 2 * n_in, d_out, 1, stream);
     case K_PSPEC: return redio_pspec_enqueue((redio_pspec *)c.plan, d_in, n_in, d_out, stream);
+    case K_PSPEC_U8: return redio_pspec_enqueue_u8((redio_pspec *)c.plan, d_in, 2 * n_in, d_out, stream);
     case K_OVSAVE_REAL: return redio_ovsave_real_enqueue_any((redio_ovsave_real *)c.plan, d_in, n_in, d_out, stream); // a unit may start on an odd sample
     }
     return REDIO_ERR_ARG;
@@ -135,6 +136,7 @@ int carry_enqueue(Carry *c, const void *d_new, size_t n, void *d_out, size_t *no
     if (!guard.ok()) return REDIO_ERR_ARG; // another thread is inside this stream: its counters are not ours to move
     if (n == 0) return REDIO_OK;
     if (!d_new) return REDIO_ERR_ARG;
+    if (c->kind == K_PSPEC_U8 && ((uintptr_t)d_new & 1)) return REDIO_ERR_ARG; // a whole-sample boundary, refused before the seam copy
     REDIO_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     const char *src = (const char *)d_new;
@@ -347,4 +349,17 @@ extern "C" int redio_pspec_stream_create(redio_pspec_stream **h, redio_pspec *pl
     const int rr = redio_pspec_reserve(plan, 2 * W);
     if (rr) return rr;
     return make(h, K_PSPEC, plan, dev, W, K * step, 8, (size_t)nfft, 4);
+}
+// the same stream fed with the receiver's u8 I/Q bytes: the history is carried as bytes and every window runs redio_pspec_enqueue_u8
+extern "C" int redio_pspec_stream_create_u8(redio_pspec_stream **h, redio_pspec *plan)
+{
+    if (!h) return REDIO_ERR_ARG;
+    *h = nullptr;
+    if (!plan) return REDIO_ERR_ARG;
+    int nfft, dev; size_t K, step;
+    redio_pspec_shape(plan, &nfft, &K, &step, &dev);
+    const size_t W = (K - 1) * step + (size_t)nfft;
+    const int rr = redio_pspec_reserve_u8(plan, 2 * (2 * W)); // seam windows; see redio_pspec_stream_create
+    if (rr) return rr;
+    return make(h, K_PSPEC_U8, plan, dev, W, K * step, 2, (size_t)nfft, 4);
 }

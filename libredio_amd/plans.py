@@ -268,10 +268,10 @@ class Stream:
     (complex64 in, float32 rows out)."""
 
     def __init__(self, plan, u8=False):
-        """u8=True (Chain and Channelizer): the stream arrives as the receiver's interleaved u8 I/Q bytes (uint8 tensors, two
-        bytes per sample; redio_{chain,pfb}_stream_create_u8)."""
+        """u8=True (Chain, Channelizer and PowerSpectrum): the stream arrives as the receiver's interleaved u8 I/Q bytes (uint8
+        tensors, two bytes per sample; redio_{chain,pfb,pspec}_stream_create_u8)."""
         kind = {Fir: "fir", Chain: "chain"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec"}[type(plan).__name__]
-        assert not u8 or kind in ("chain", "pfb")
+        assert not u8 or kind in ("chain", "pfb", "pspec")
         self._kind, self._plan, self._u8 = kind, plan, bool(u8)          # the plan must outlive the stream handle
         self._h = C.c_void_p()
         check(getattr(lib(), f"redio_{kind}_stream_create" + ("_u8" if u8 else ""))(C.byref(self._h), plan._h), f"{kind}_stream_create")
@@ -743,6 +743,21 @@ class PowerSpectrum:
 
     def __call__(self, x, out=None):
         return self._run(lib().redio_pspec_enqueue, x, x.numel(), self.nrows(x.numel()), out)
+
+    def u8(self, raw, out=None):
+        """the receiver's interleaved u8 I/Q bytes in (uint8 tensor, even numel): the rows of data_to_samples + __call__, bit for
+        bit, without the cf32 intermediate (redio_pspec_enqueue_u8)"""
+        import torch
+        assert raw.dtype == torch.uint8 and raw.numel() % 2 == 0, "expected an even number of uint8 bytes"
+        rows = self.nrows(raw.numel() // 2)
+        if out is None:
+            out = torch.empty(rows * self.nfft, dtype=torch.float32, device=raw.device)
+        assert out.dtype == torch.float32 and out.numel() >= rows * self.nfft
+        check(lib().redio_pspec_enqueue_u8(self._h, _dev_ptr(raw), raw.numel(), _dev_ptr(out), current_stream()), "pspec_enqueue_u8")
+        return out[: rows * self.nfft].view(rows, self.nfft)
+
+    def reserve_u8(self, nbytes):
+        check(lib().redio_pspec_reserve_u8(self._h, nbytes), "pspec_reserve_u8")
 
     def spectra(self, X, out=None):
         """the same integration over packed, already transformed rows of nfft bins (a Chain's output): numel // nfft // integrate rows"""

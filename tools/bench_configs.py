@@ -1,5 +1,5 @@
 """Throughput of the non-headline configs of BASELINE.json on one MI355X (own measurements; bench.py
-stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec]..."""
+stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8]..."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, libredio_amd as R
@@ -135,6 +135,40 @@ if "pspec" in which:
               f"time per sample pspec / fft = {ms_p/ms_f:.3f}")
         del plan, out
     del x, outc, fft
+if "pspecu8" in which:
+    # the integrated power spectrum of 2^28 samples that arrive as 2^29 u8 I/Q bytes (made on the device): (u) redio_pspec_enqueue_u8
+    # against (a) redio_pspec_enqueue on the same samples already converted and resident as cf32 and (b) redio_data_to_samples +
+    # redio_pspec_enqueue, what a caller without the u8 entry does.  Timed alternately, twice each, in this one process; the smaller
+    # time of each is printed.  Algorithmic bytes per sample of (u): 2 N / step + 4 / K.  The bar: u < b on every shape; the target
+    # for the fused shapes: u / a <= 1.03.
+    from libredio_amd import bitfount as B
+    g = torch.Generator(device="cuda"); g.manual_seed(1)
+    raw = torch.randint(0, 256, (2 * n,), dtype=torch.uint8, device="cuda", generator=g)
+    x = B.data_to_samples(raw)
+    conv = torch.empty(n, dtype=torch.complex64, device="cuda")
+    win = R.dsputils.lpf_corrected(1024, 0.1)
+    for nfft, k, step, w, mode, label in ((1024, 16, 1024, None, 0, "auto"), (1024, 1024, 1024, None, 2, "mode 2: a wave per segment + fold"),
+                                          (1024, 16, 512, win, 0, "auto, windowed, step 512"), (4096, 16, 4096, None, 0, "generic")):
+        plan = R.PowerSpectrum(nfft, k, step, w)
+        plan.set_split(mode)
+        plan.reserve(n)
+        plan.reserve_u8(2 * n)
+        rows = plan.nrows(n)
+        out = torch.empty(rows * nfft, dtype=torch.float32, device="cuda")
+        reps = 10 if plan.is_fused else 3
+        b = 2 * nfft / step + 4 / k  # algorithmic bytes per input sample
+        def two():
+            B.data_to_samples(raw, out=conv); plan(conv, out=out)
+        ms_u = ms_a = ms_b = 1e30
+        for _ in range(2):
+            ms_u = min(ms_u, timeit(lambda: plan.u8(raw, out=out), n=reps, warm=3))
+            ms_a = min(ms_a, timeit(lambda: plan(x, out=out), n=reps, warm=3))
+            ms_b = min(ms_b, timeit(two, n=reps, warm=3))
+        print(f"PSPEC-U8 {nfft} K={k} step={step} ({label}): {rows} rows  (u) {ms_u:.3f} ms  {n/ms_u/1e6:.1f} GS/s  {b*n/ms_u/1e6:.0f} GB/s algorithmic "
+              f"({b*n/ms_u/1e6/8000:.1%} of 8 TB/s) | (a) cf32 resident: {ms_a:.3f} ms  {n/ms_a/1e6:.1f} GS/s | (b) data_to_samples + cf32: {ms_b:.3f} ms  "
+              f"{n/ms_b/1e6:.1f} GS/s | u/a = {ms_u/ms_a:.3f}  u/b = {ms_u/ms_b:.3f}")
+        del plan, out
+    del raw, x, conv
 if "fftall" in which:
     for nfft in (6, 9, 10, 12, 15, 20, 24, 25, 27, 30, 40, 45, 48, 60, 75, 80, 81, 90, 96, 100, 120, 125, 150, 160, 180, 192, 200, 225, 240, 243, 250, 300, 320, 360, 384, 400, 450, 480, 500, 600, 625, 640, 720, 729, 768, 800, 900, 960, 1000, 1200, 1280, 1440, 1536, 1600, 1800, 1920, 2000, 2187, 2400, 2560, 3072, 3125, 3200, 3600, 3840, 4000, 4800, 5120, 6144, 6400, 6561, 7680, 8000):
         x = R.synth_iq(2, 0, n)[: n // nfft * nfft]
