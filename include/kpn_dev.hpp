@@ -1041,5 +1041,30 @@ inline void power_spectrum_stream_u8(Receiver<View<uint8_t>> u, Sender<View<floa
                                                 });
 }
 
+// the real-input integrated power spectrum (redio_pspec_real_*: |X|^2 of nfft-point kiss_fftr rows that start every `step` real
+// samples, summed over `integrate` transforms; window: empty or nfft values): f32 messages in, rows of nfft / 2 + 1 f32 out,
+// per-message semantics -- the rows that fit in each message, a trailing partial row dropped
+inline void power_spectrum_real(Receiver<View<float>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {})
+{
+    redio_pspec_real *h = nullptr;
+    check(redio_pspec_real_create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
+    struct G { redio_pspec_real *h; ~G() { redio_pspec_real_destroy(h); } } g{h};
+    detail::run_block<float, float>(u, v, [&](const View<float> &d) { return redio_pspec_real_nrows(h, d.len) * redio_pspec_real_nbins(h); },
+                                    [&](const View<float> &d, const View<float> &o, void *st) { return redio_pspec_real_enqueue(h, d.data(), d.len, o.data(), st); });
+}
+
+// the same as a STREAM: messages of any length, odd ones included, give the rows of one call on the whole stream
+inline void power_spectrum_real_stream(Receiver<View<float>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {})
+{
+    redio_pspec_real *h = nullptr;
+    check(redio_pspec_real_create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
+    redio_pspec_real_stream *s = nullptr;
+    const int rc = redio_pspec_real_stream_create(&s, h);
+    struct G { redio_pspec_real *h; redio_pspec_real_stream *s; ~G() { redio_pspec_real_stream_destroy(s); redio_pspec_real_destroy(h); } } g{h, s};
+    check(rc);
+    detail::run_stream_block_of<float, float>(u, v, [&](size_t len) { return redio_pspec_real_stream_nout(s, len); },
+                                              [&](const View<float> &d, float *o, size_t *got, void *st) { return redio_pspec_real_stream_enqueue(s, d.data(), d.len, o, got, st); });
+}
+
 } // namespace dev
 } // namespace kpn

@@ -232,6 +232,46 @@ int redio_pspec_set_split(redio_pspec *h, int mode);
 int redio_pspec_enqueue_u8(redio_pspec *h, const void *d_bytes, size_t nbytes, void *d_out_f32, void *stream);
 int redio_pspec_reserve_u8(redio_pspec *h, size_t nbytes);
 
+/* ---- the real-input integrated power spectrum: |X[k]|^2 of kiss_fftr (tools/kiss_fftr.c) summed over K transforms of REAL samples ----
+ * The power spectrum above for the reference's real f32 streams (the magnitudes of rtlsdr / bitfount, dsputils::convolve,
+ * samplerate::resample) without widening them to cf32 and without computing every bin twice.  The transform is kiss_fftr
+ * (tools/kiss_fftr.c), the bits of a forward redio_fftr_* plan: the complex transform of size M = N / 2 and the published split
+ * loop; the integration is the stated design of DESIGN.md 5.3c, unchanged (the contract of this block: DESIGN.md 5.3d).
+ * N = nfft REAL points, even, 2 <= N <= 2^25; K = integrate; B = N / 2 + 1 bins (redio_pspec_real_nbins):
+ *     transform t of row r reads x[(r K + t) step ... + N), times window[n] when there is a window (NULL: no multiply at all);
+ *     X = kiss_fftr of that row;  p_t[k] = X[k].re * X[k].re + X[k].im * X[k].im for k = 0 ... M (bins 0 and M have imaginary part +0);
+ *     segments of REDIO_PSPEC_SEG transforms, a left fold in ascending t inside each, a left fold over them in ascending s.
+ * All f32, every multiply and add rounded on its own; the order does not depend on launch geometry.  With W = (K - 1) step + N and
+ * H = K step (in real samples) a call of n_in samples gives nrows = (n_in - W) / H + 1 rows (0 when n_in < W; a trailing partial row is
+ * dropped) of B f32 in natural bin order, packed -- B is odd at the fused size, so rows are only 4-byte aligned.  No one-sided
+ * doubling, no dB, no division by sum(w^2): those are the caller's.
+ * create: NULL h, odd nfft, nfft < 2, integrate == 0, step == 0 -> REDIO_ERR_ARG; nfft > 2^25 -> REDIO_ERR_UNSUPPORTED
+ *   (redio_fftr_create's ceiling).  The plan owns a forward redio_fftr of size N.
+ * N = 2048 is ONE kernel in which the spectra never leave the wave's registers (redio_pspec_real_is_fused() == 1): 4 N / step bytes
+ *   read and 4 B / (K step) -- about 2 / K -- written per real sample, half of what the fused redio_fftr alone moves.  Every other
+ *   size gathers (and windows) the rows unless the transform can read the caller's buffer (no window, step == N, 8-byte aligned),
+ *   runs the plan's own redio_fftr and an accumulate pass through plan-owned scratch in chunks of at most 64 MiB of spectra.
+ * reserve(h, n_in) sizes all plan-owned scratch for calls of up to n_in samples (and for enqueue_spectra calls of as many rows), after
+ *   which an enqueue neither allocates nor synchronises; un-reserved it grows on first use (REDIO_ERR_NOT_RESERVED while the stream
+ *   is being captured).
+ * enqueue: launches only, on the caller's stream; every argument is checked before anything is launched.  d_in and d_out are each
+ *   4-byte aligned (a real stream has no pair structure: a seam lands on any sample).  NULL or overlapping buffers -> REDIO_ERR_ARG;
+ *   fewer than W samples -> REDIO_OK, no launch.
+ * enqueue_spectra: the integration alone over nbatch packed rows of B cf32 (redio_fftr_enqueue's output; 8-byte aligned; window and
+ *   step do not apply): nbatch / K rows come out.
+ * set_split: 0 auto, 1 one wavefront (or thread group) per whole row, 2 one per segment and a fold pass over the partials: the bits
+ *   are the same in every mode. */
+typedef struct redio_pspec_real redio_pspec_real;
+int redio_pspec_real_create(redio_pspec_real **h, int nfft /* real points */, size_t integrate, size_t step, const float *window_host /* NULL or nfft */);
+int redio_pspec_real_destroy(redio_pspec_real *h);
+size_t redio_pspec_real_nrows(const redio_pspec_real *h, size_t n_in);
+size_t redio_pspec_real_nbins(const redio_pspec_real *h); /* nfft / 2 + 1; 0 for NULL */
+int redio_pspec_real_is_fused(const redio_pspec_real *h);
+int redio_pspec_real_reserve(redio_pspec_real *h, size_t n_in);
+int redio_pspec_real_enqueue(redio_pspec_real *h, const void *d_in_f32, size_t n_in, void *d_out_f32, void *stream);
+int redio_pspec_real_enqueue_spectra(redio_pspec_real *h, const void *d_spectra_c32, size_t nbatch, void *d_out_f32, void *stream);
+int redio_pspec_real_set_split(redio_pspec_real *h, int mode);
+
 /* ---- C2 chain: FIR (ntaps, decimate decim) -> nfft-point forward FFT of consecutive blocks ----
  * Fused single kernel for nfft = 1024 with (ntaps, decim) in {(127, 5), (127, 3), (127, 1), (63, 5), (63, 1)} on a
  * 16-byte aligned stream; other shapes run the FIR and FFT kernels back to back through a plan-owned
@@ -431,6 +471,9 @@ int redio_pfb_exchange_all(redio_comm *const *comms, int ndev, const void *const
  *             (whole rows of nfft).  The staging buffers hold fewer than W samples each side of a seam -- 8 MiB of history at
  *             nfft = integrate = 1024 -- so a long integration costs that much device memory per stream handle.  (A u8 stream,
  *             redio_pspec_stream_create_u8, carries the same samples as bytes: a quarter of that.)
+ *     pspec_real: the same on f32 samples (W and H count real samples), rows of nfft / 2 + 1 f32; d_new needs 4-byte alignment only --
+ *             messages may have any length, odd ones included -- and so does d_out.  Create reserves for the seam windows
+ *             (redio_pspec_real_reserve(plan, largest message + W) keeps longer bodies allocation-free).
  * enqueue() writes *nout (= redio_*_stream_nout(h, n_new), known before the call) output samples to d_out; the new
  * samples are read in place (only a seam of fewer than one window is staged through a plan-owned buffer).  It only
  * launches kernels and small device copies -- with one exception: a plan shape that runs as two kernels (redio_chain_is_fused() == 0,
@@ -491,6 +534,13 @@ int redio_pspec_stream_enqueue(redio_pspec_stream *h, const void *d_new, size_t 
  * Create reserves for the seam windows (redio_pspec_reserve_u8(plan, largest message's bytes + 2 W) keeps longer bodies allocation-free).
  * All other redio_pspec_stream_* calls apply unchanged. */
 int redio_pspec_stream_create_u8(redio_pspec_stream **h, redio_pspec *plan);
+typedef struct redio_pspec_real_stream redio_pspec_real_stream;
+int redio_pspec_real_stream_create(redio_pspec_real_stream **h, redio_pspec_real *plan);
+int redio_pspec_real_stream_destroy(redio_pspec_real_stream *h);
+int redio_pspec_real_stream_reset(redio_pspec_real_stream *h);
+size_t redio_pspec_real_stream_nout(const redio_pspec_real_stream *h, size_t n_new);
+size_t redio_pspec_real_stream_pending(const redio_pspec_real_stream *h);
+int redio_pspec_real_stream_enqueue(redio_pspec_real_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
 
 /* ---- A6: samplerate::resample's native side, src/samplerate/src/samplerate.rs:59-87 ----
  * nchan independent mono streams that share ratio and block lengths (the reference creates one

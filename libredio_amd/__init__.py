@@ -123,7 +123,7 @@ def lib():
     _sig(L.redio_fft_reserve, i, vp, sz)
     _sig(L.redio_pfb_reserve, i, vp, sz, i)
     _sig(L.redio_pfb_reserve_two_pass, i, vp, sz, i)
-    for n in ("fir", "chain", "pfb", "ovsave", "ovsave_real", "pspec"):
+    for n in ("fir", "chain", "pfb", "ovsave", "ovsave_real", "pspec", "pspec_real"):
         _sig(getattr(L, f"redio_{n}_stream_create"), i, C.POINTER(vp), vp)
         _sig(getattr(L, f"redio_{n}_stream_destroy"), i, vp)
         _sig(getattr(L, f"redio_{n}_stream_reset"), i, vp)
@@ -175,6 +175,15 @@ def lib():
     _sig(L.redio_pspec_set_split, i, vp, i)
     _sig(L.redio_pspec_enqueue_u8, i, vp, vp, sz, vp, vp)
     _sig(L.redio_pspec_reserve_u8, i, vp, sz)
+    _sig(L.redio_pspec_real_create, i, C.POINTER(vp), i, sz, sz, pf)
+    _sig(L.redio_pspec_real_destroy, i, vp)
+    _sig(L.redio_pspec_real_nrows, sz, vp, sz)
+    _sig(L.redio_pspec_real_nbins, sz, vp)
+    _sig(L.redio_pspec_real_is_fused, i, vp)
+    _sig(L.redio_pspec_real_reserve, i, vp, sz)
+    _sig(L.redio_pspec_real_enqueue, i, vp, vp, sz, vp, vp)
+    _sig(L.redio_pspec_real_enqueue_spectra, i, vp, vp, sz, vp, vp)
+    _sig(L.redio_pspec_real_set_split, i, vp, i)
     psz = C.POINTER(sz)
     _sig(L.redio_data_to_samples, i, vp, sz, vp, vp)
     _sig(L.redio_norm_c32, i, vp, sz, vp, vp)
@@ -269,4 +278,4 @@ def check(code, what="redio"):
 
 
 from . import bitfount, dsputils, kissfft, kpn_dev, plans, samplerate  # noqa: E402,F401
-from .plans import Chain, Channelizer, Comm, Fft, Fftr, Fir, Graph, OverlapSave, OverlapSaveReal, PowerSpectrum, Src, Stream, channelizer_all_to_all, current_stream, planes_to_rows, rows_to_planes, synth_f32, synth_iq  # noqa: E402,F401
+from .plans import Chain, Channelizer, Comm, Fft, Fftr, Fir, Graph, OverlapSave, OverlapSaveReal, PowerSpectrum, PowerSpectrumReal, Src, Stream, channelizer_all_to_all, current_stream, planes_to_rows, rows_to_planes, synth_f32, synth_iq  # noqa: E402,F401

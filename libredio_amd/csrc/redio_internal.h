@@ -125,6 +125,14 @@ hipError_t launch_pspec_rows_u8(const uint16_t *x, const float *win, float2 *row
 hipError_t launch_pspec_accum(const float2 *spec, float *dst, long q0, long nseg, long N, long K, long g_base, hipStream_t s);
 hipError_t launch_pspec_fold(const float *part, float *out, long nrows, long N, long S, hipStream_t s);
 
+// pspec_real_kernels.hip: the real-input integrated power spectrum.  launch_pspecr2k: 2048 real points per transform, one wavefront per
+// unit (a row of K transforms, or with `split` one segment of at most 16); x: 4-byte aligned; dst: 1025 f32 per unit; win: 2048 values
+// or null; tw / stw: the tables of the plan's redio_fftr.  launch_pspec_real_rows: the generic path's row gather (rows: ntr packed
+// rows of N f32); its accumulate and fold passes are launch_pspec_accum / launch_pspec_fold with a row of N / 2 + 1 bins.
+hipError_t launch_pspecr2k(const float *x, long step, long K, const float *win, const float2 *tw, const float2 *stw, float *dst, long nunits,
+                           bool split, hipStream_t s);
+hipError_t launch_pspec_real_rows(const float *x, const float *win, float *rows, long ntr, long N, long step, hipStream_t s);
+
 // overlap-save at nfft 1024 (one wave per block) and 4096: one kernel, no work buffers; at 4096 / 16384 tw_f / tw_i (4096) and
 // Tf / Ti (16384) are the plans' stage-ordered twiddle copies (redio_fft_twiddles_pass_dev)
 hipError_t launch_ovsave1k(const float2 *x, long hop, const float2 *tw_f, const float2 *tw_i, const float2 *Hc, float2 *out, long nblk,
@@ -182,13 +190,14 @@ inline int num_cus()
 } // namespace redio
 
 // plan shapes for the carried-history layer (stream_carry.hip); defined next to each plan struct
-struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real; struct redio_pspec;
+struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real; struct redio_pspec; struct redio_pspec_real;
 void redio_fir_shape(const redio_fir *h, size_t *ntaps, size_t *decim, unsigned *flags, int *device);
 void redio_chain_shape(const redio_chain *h, size_t *ntaps, size_t *decim, int *nfft, int *device);
 void redio_pfb_shape(const redio_pfb *h, int *nchan, int *taps_per_branch, int *device);
 void redio_ovsave_shape(const redio_ovsave *h, int *nfft, size_t *hop, int *device);
 void redio_ovsave_real_shape(const redio_ovsave_real *h, int *nfft, size_t *hop, int *device);
 void redio_pspec_shape(const redio_pspec *h, int *nfft, size_t *integrate, size_t *step, int *device);
+void redio_pspec_real_shape(const redio_pspec_real *h, int *nfft, size_t *integrate, size_t *step, int *device);
 // redio_ovsave_real_enqueue for the carried-history layer: d_in may be only 4-byte aligned (a message that started on an odd sample)
 int redio_ovsave_real_enqueue_any(redio_ovsave_real *h, const void *d_in, size_t n_in, void *d_out, void *stream);
 

@@ -9,6 +9,7 @@
 //     channelizer  W = nchan*taps_per_branch       H = nchan          unit = 1 row (nchan samples)
 //     overlap-save W = nfft                        H = hop            unit = hop output samples (cf32, or f32 for the real operator)
 //     power spectrum W = (integrate-1)*step + nfft H = integrate*step unit = 1 row (nfft f32 from cf32 samples, or from u8 I/Q byte pairs)
+//     real power spectrum  the same W and H in REAL samples  unit = 1 row (nfft/2 + 1 f32 from f32 samples)
 // so one layer serves them all.  The handle keeps the stream's unconsumed tail (fewer than W samples) on the device.
 // A call with n new samples
 //   1. appends the first min(n, W-1) new samples to the tail in a plan-owned staging buffer (one small copy),
@@ -54,7 +55,7 @@ hipError_t seam_copy(void *dst, const void *src, size_t bytes, hipStream_t st)
     SEAM_GO(uint8_t)
 #undef SEAM_GO
 }
-enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8 }; // _U8: the samples are interleaved u8 I/Q byte pairs
+enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8, K_PSPEC_REAL }; // _U8: the samples are interleaved u8 I/Q byte pairs
 struct Carry {
     int device = 0;
     Kind kind = K_FIR;
@@ -92,6 +93,7 @@ int run(const Carry &c, const void *d_in, size_t n_in, void *d_out, void *stream
     case K_PFB_U8: return redio_pfb_enqueue_u8((redio_pfb *)c.plan, d_in, 2 * n_in, d_out, 1, stream);
     case K_PSPEC: return redio_pspec_enqueue((redio_pspec *)c.plan, d_in, n_in, d_out, stream);
     case K_PSPEC_U8: return redio_pspec_enqueue_u8((redio_pspec *)c.plan, d_in, 2 * n_in, d_out, stream);
+    case K_PSPEC_REAL: return redio_pspec_real_enqueue((redio_pspec_real *)c.plan, d_in, n_in, d_out, stream); // takes 4-byte aligned input itself
     case K_OVSAVE_REAL: return redio_ovsave_real_enqueue_any((redio_ovsave_real *)c.plan, d_in, n_in, d_out, stream); // a unit may start on an odd sample
     }
     return REDIO_ERR_ARG;
@@ -137,6 +139,7 @@ int carry_enqueue(Carry *c, const void *d_new, size_t n, void *d_out, size_t *no
     if (n == 0) return REDIO_OK;
     if (!d_new) return REDIO_ERR_ARG;
     if (c->kind == K_PSPEC_U8 && ((uintptr_t)d_new & 1)) return REDIO_ERR_ARG; // a whole-sample boundary, refused before the seam copy
+    if (c->kind == K_PSPEC_REAL && ((uintptr_t)d_new & 3)) return REDIO_ERR_ARG; // likewise
     REDIO_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     const char *src = (const char *)d_new;
@@ -216,6 +219,7 @@ struct redio_pfb_stream { Carry *c; };
 struct redio_ovsave_stream { Carry *c; };
 struct redio_ovsave_real_stream { Carry *c; };
 struct redio_pspec_stream { Carry *c; };
+struct redio_pspec_real_stream { Carry *c; };
 
 #define RD_STREAM_API(NAME)                                                                                                     \
     extern "C" int redio_##NAME##_stream_destroy(redio_##NAME##_stream *h)                                                      \
@@ -243,6 +247,7 @@ RD_STREAM_API(pfb)
 RD_STREAM_API(ovsave)
 RD_STREAM_API(ovsave_real)
 RD_STREAM_API(pspec)
+RD_STREAM_API(pspec_real)
 
 template <typename Hd>
 static int make(Hd **h, Kind kind, void *plan, int dev, size_t W, size_t H, size_t in_elem, size_t unit_out, size_t out_elem)
@@ -362,4 +367,19 @@ extern "C" int redio_pspec_stream_create_u8(redio_pspec_stream **h, redio_pspec 
     const int rr = redio_pspec_reserve_u8(plan, 2 * (2 * W)); // seam windows; see redio_pspec_stream_create
     if (rr) return rr;
     return make(h, K_PSPEC_U8, plan, dev, W, K * step, 2, (size_t)nfft, 4);
+}
+// the real-input power spectrum: 4-byte samples, rows of nfft / 2 + 1 f32; a message may start and end on any sample
+extern "C" int redio_pspec_real_stream_create(redio_pspec_real_stream **h, redio_pspec_real *plan)
+{
+    if (!h) return REDIO_ERR_ARG;
+    *h = nullptr;
+    if (!plan) return REDIO_ERR_ARG;
+    int nfft, dev; size_t K, step;
+    redio_pspec_real_shape(plan, &nfft, &K, &step, &dev);
+    const size_t W = (K - 1) * step + (size_t)nfft;
+    // the plan's scratch, sized here for the seam windows (at most 2*W samples per head run); a longer body run grows it at enqueue
+    // time unless redio_pspec_real_reserve(plan, largest message + W) came first
+    const int rr = redio_pspec_real_reserve(plan, 2 * W);
+    if (rr) return rr;
+    return make(h, K_PSPEC_REAL, plan, dev, W, K * step, 4, (size_t)nfft / 2 + 1, 4);
 }

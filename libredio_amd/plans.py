@@ -262,15 +262,15 @@ class Chain:
 
 
 class Stream:
-    """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
+    """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec,pspec_real}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
     segmentation of the input gives the bits of one stateless call on the whole stream (the stateless plans keep the
-    reference's per-message semantics, dsputils.rs:30-32).  `plan` is a Fir, Chain, Channelizer, OverlapSave, OverlapSaveReal or PowerSpectrum
-    (complex64 in, float32 rows out)."""
+    reference's per-message semantics, dsputils.rs:30-32).  `plan` is a Fir, Chain, Channelizer, OverlapSave, OverlapSaveReal, PowerSpectrum
+    (complex64 in, float32 rows out) or PowerSpectrumReal (float32 in, float32 rows out)."""
 
     def __init__(self, plan, u8=False):
         """u8=True (Chain, Channelizer and PowerSpectrum): the stream arrives as the receiver's interleaved u8 I/Q bytes (uint8
         tensors, two bytes per sample; redio_{chain,pfb,pspec}_stream_create_u8)."""
-        kind = {Fir: "fir", Chain: "chain"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec"}[type(plan).__name__]
+        kind = {Fir: "fir", Chain: "chain"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec", "PowerSpectrumReal": "pspec_real"}[type(plan).__name__]
         assert not u8 or kind in ("chain", "pfb", "pspec")
         self._kind, self._plan, self._u8 = kind, plan, bool(u8)          # the plan must outlive the stream handle
         self._h = C.c_void_p()
@@ -293,7 +293,7 @@ class Stream:
         """Feed the next piece of the stream; returns the output samples that became computable (flat tensor; the
         chain's are whole spectra of nfft samples, the channelizer's whole rows of nchan samples)."""
         import torch
-        real = self._kind == "ovsave_real" or (self._kind == "fir" and not self._plan.complex_input)
+        real = self._kind in ("ovsave_real", "pspec_real") or (self._kind == "fir" and not self._plan.complex_input)
         want = torch.float32 if real else torch.complex64
         if self._u8:
             assert x.dtype == torch.uint8 and x.numel() % 2 == 0, "expected an even number of uint8 bytes"
@@ -767,4 +767,62 @@ class PowerSpectrum:
     def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
         if getattr(self, "_h", None):
             _safe_destroy("redio_pspec_destroy", self._h)
+            self._h = None
+
+
+class PowerSpectrumReal:
+    """redio_pspec_real_*: |X[k]|^2 of kiss_fftr rows (tools/kiss_fftr.c, the bits of Fftr) of nfft REAL samples that start every
+    `step` samples, optionally windowed, summed over `integrate` consecutive transforms in the blocked order of DESIGN.md 5.3c
+    (contract: DESIGN.md 5.3d): float32 samples in, rows of nbins = nfft/2 + 1 float32 out.  nfft = 2048 is one kernel (is_fused)."""
+
+    AUTO, ROWS, SEGMENTS = 0, 1, 2
+
+    def __init__(self, nfft=2048, integrate=1, step=None, window=None):
+        self.nfft, self.integrate = int(nfft), int(integrate)
+        self.step = self.nfft if step is None else int(step)
+        self.nbins = self.nfft // 2 + 1
+        p = None
+        if window is not None:
+            w, p = _taps(window)
+            assert len(w) == self.nfft, "a window of nfft values"
+        self._h = C.c_void_p()
+        check(lib().redio_pspec_real_create(C.byref(self._h), self.nfft, self.integrate, self.step, p), "pspec_real_create")
+        assert lib().redio_pspec_real_nbins(self._h) == self.nbins
+
+    def nrows(self, n_in):
+        return lib().redio_pspec_real_nrows(self._h, n_in)
+
+    @property
+    def is_fused(self):
+        return bool(lib().redio_pspec_real_is_fused(self._h))
+
+    def reserve(self, n_in):
+        check(lib().redio_pspec_real_reserve(self._h, n_in), "pspec_real_reserve")
+
+    def set_split(self, mode):
+        """AUTO / ROWS (one wavefront per whole row) / SEGMENTS (one per segment of 16 transforms and a fold pass): the same bits."""
+        check(lib().redio_pspec_real_set_split(self._h, int(mode)), "pspec_real_set_split")
+
+    def _run(self, fn, x, dtype, count, rows, out):
+        import torch
+        assert x.dtype == dtype, f"expected {dtype}"
+        if out is None:
+            out = torch.empty(rows * self.nbins, dtype=torch.float32, device=x.device)
+        assert out.dtype == torch.float32 and out.numel() >= rows * self.nbins
+        check(fn(self._h, _dev_ptr(x), count, _dev_ptr(out), current_stream()), "pspec_real_enqueue")
+        return out[: rows * self.nbins].view(rows, self.nbins)
+
+    def __call__(self, x, out=None):
+        import torch
+        return self._run(lib().redio_pspec_real_enqueue, x, torch.float32, x.numel(), self.nrows(x.numel()), out)
+
+    def spectra(self, X, out=None):
+        """the same integration over packed, already transformed rows of nbins bins (an Fftr's output): numel // nbins // integrate rows"""
+        import torch
+        nbatch = X.numel() // self.nbins
+        return self._run(lib().redio_pspec_real_enqueue_spectra, X, torch.complex64, nbatch, nbatch // self.integrate, out)
+
+    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
+        if getattr(self, "_h", None):
+            _safe_destroy("redio_pspec_real_destroy", self._h)
             self._h = None

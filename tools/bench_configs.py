@@ -1,5 +1,5 @@
 """Throughput of the non-headline configs of BASELINE.json on one MI355X (own measurements; bench.py
-stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8]..."""
+stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit]..."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, libredio_amd as R
@@ -169,6 +169,93 @@ if "pspecu8" in which:
               f"{n/ms_b/1e6:.1f} GS/s | u/a = {ms_u/ms_a:.3f}  u/b = {ms_u/ms_b:.3f}")
         del plan, out
     del raw, x, conv
+if "pspecreal" in which:
+    # the real-input integrated power spectrum of 2^28 real samples: (r) redio_pspec_real_enqueue against (t) redio_fftr at 2048 on the
+    # same samples, which writes every spectrum, (b) what a caller without this plan does -- redio_fftr into a spectra buffer (after a
+    # gather / window pass where the shape needs one: a window, or a step redio_fftr_enqueue_strided does not take), then
+    # PowerSpectrum(nfft // 2 + 1, K).spectra -- whose rows are compared with (r)'s bit for bit before anything is timed, and (c)
+    # PowerSpectrum(1024, K) on 2^28 cf32 samples (informational: time per sample, real against complex).  Timed alternately, twice
+    # each, in this one process; the smaller time of each is printed.  Algorithmic bytes per real sample of (r): 4 N / step + 4 B / (K step).
+    # The bar: r < b on every shape; the target at step == N on the fused size: r < t.
+    x = R.synth_f32(3, 0, n)
+    xc = R.synth_iq(2, 0, n)
+    fftr_t = R.Fftr(2048)
+    spec_t = torch.empty((n // 2048) * 1025, dtype=torch.complex64, device="cuda")
+    win2k = R.dsputils.lpf_corrected(2048, 0.1)
+    for nfft, k, step, w, mode, label in ((2048, 16, 2048, None, 0, "auto"), (2048, 1024, 2048, None, 1, "mode 1: a wave per row"),
+                                          (2048, 1024, 2048, None, 2, "mode 2: a wave per segment + fold"),
+                                          (2048, 16, 1024, win2k, 0, "auto, windowed, step 1024"), (2048, 16, 2047, None, 0, "auto, step 2047: 4-byte loads"),
+                                          (4096, 16, 4096, None, 0, "auto")):
+        nb = nfft // 2 + 1
+        plan = R.PowerSpectrumReal(nfft, k, step, w)
+        plan.set_split(mode)
+        plan.reserve(n)
+        rows = plan.nrows(n)
+        ntr = rows * k
+        out = torch.empty(rows * nb, dtype=torch.float32, device="cuda")
+        reps = 10 if plan.is_fused else 3
+        b = 4 * nfft / step + 4 * nb / (k * step)  # algorithmic bytes per real sample
+        # (b): the parent's route
+        fr = R.Fftr(nfft)
+        fr.reserve(ntr)
+        spec = torch.empty(ntr * nb, dtype=torch.complex64, device="cuda")
+        out_b = torch.empty_like(out)
+        packs = w is not None or step % 2 == 1
+        rowbuf = torch.empty((ntr, nfft), dtype=torch.float32, device="cuda") if packs else None
+        wd = torch.from_numpy(w).cuda() if w is not None else None
+        try:
+            old = R.PowerSpectrum(nb, k)
+            old.reserve(n)
+        except R.RedioError as e:
+            old = None
+            print(f"PSPEC-REAL {nfft}: leg (b) cannot be built, PowerSpectrum({nb}, {k}): {e}")
+        def route_b():
+            if packs:
+                frames = x.unfold(0, nfft, step)[:ntr]
+                if wd is not None: torch.mul(frames, wd, out=rowbuf)
+                else: rowbuf.copy_(frames)
+                fr(rowbuf.view(-1), out=spec)
+            else:
+                fr.strided(x, ntr, step, out=spec)
+            old.spectra(spec, out=out_b)
+        plan(x, out=out)
+        same = None
+        if old is not None:
+            route_b()
+            same = torch.equal(out.view(torch.int32), out_b.view(torch.int32))
+            assert same, "leg (b) and leg (r) differ"
+        cstep = 1024 * step // nfft if (1024 * step) % nfft == 0 else 1024  # the same overlap on the complex side
+        cplx = R.PowerSpectrum(1024, k, cstep, None if w is None else R.dsputils.lpf_corrected(1024, 0.1))
+        cplx.reserve(n)
+        out_c = torch.empty(cplx.nrows(n) * 1024, dtype=torch.float32, device="cuda")
+        ms_r = ms_t = ms_b = ms_c = 1e30
+        for _ in range(2):
+            ms_r = min(ms_r, timeit(lambda: plan(x, out=out), n=reps, warm=3))
+            ms_t = min(ms_t, timeit(lambda: fftr_t(x, out=spec_t), n=reps, warm=3))
+            if old is not None: ms_b = min(ms_b, timeit(route_b, n=3, warm=2))
+            ms_c = min(ms_c, timeit(lambda: cplx(xc, out=out_c), n=reps, warm=3))
+        print(f"PSPEC-REAL {nfft} K={k} step={step} ({label}; {'fused' if plan.is_fused else 'generic'}): {rows} rows  (r) {ms_r:.3f} ms  {n/ms_r/1e6:.1f} real GS/s  "
+              f"{b*n/ms_r/1e6:.0f} GB/s algorithmic ({b*n/ms_r/1e6/8000:.1%} of 8 TB/s at {b:.3f} B/sample) | (t) FFTR 2048 on the same samples: {ms_t:.3f} ms | "
+              f"(b) fftr + PowerSpectrum({nb}).spectra{' after a gather pass' if packs else ''}: {ms_b:.3f} ms, rows bit-equal: {same} | "
+              f"(c) PSPEC 1024 on as many cf32 samples: {ms_c:.3f} ms | r/t = {ms_r/ms_t:.3f}  r/b = {ms_r/ms_b:.3f}  r/c = {ms_r/ms_c:.3f}")
+        del plan, out, fr, spec, out_b, rowbuf, old, cplx, out_c
+    del x, xc, fftr_t, spec_t
+if "pspecrealsplit" in which:
+    # the table behind PSPEC_REAL_SPLIT_ROWS (pspec_real_core.h): 2^28 real samples, N = 2048, a wave per row against a wave per segment + fold
+    x = R.synth_f32(3, 0, n)
+    for k in (32, 64, 128, 256, 512):
+        plan = R.PowerSpectrumReal(2048, k)
+        plan.reserve(n)
+        rows = plan.nrows(n)
+        out = torch.empty(rows * 1025, dtype=torch.float32, device="cuda")
+        ms = [1e30, 1e30]
+        for _ in range(2):
+            for mode in (1, 2):
+                plan.set_split(mode)
+                ms[mode - 1] = min(ms[mode - 1], timeit(lambda: plan(x, out=out), n=10, warm=3))
+        print(f"PSPEC-REAL 2048 K={k} ({rows} rows): mode 1 {ms[0]:.3f} ms  mode 2 {ms[1]:.3f} ms")
+        del plan, out
+    del x
 if "fftall" in which:
     for nfft in (6, 9, 10, 12, 15, 20, 24, 25, 27, 30, 40, 45, 48, 60, 75, 80, 81, 90, 96, 100, 120, 125, 150, 160, 180, 192, 200, 225, 240, 243, 250, 300, 320, 360, 384, 400, 450, 480, 500, 600, 625, 640, 720, 729, 768, 800, 900, 960, 1000, 1200, 1280, 1440, 1536, 1600, 1800, 1920, 2000, 2187, 2400, 2560, 3072, 3125, 3200, 3600, 3840, 4000, 4800, 5120, 6144, 6400, 6561, 7680, 8000):
         x = R.synth_iq(2, 0, n)[: n // nfft * nfft]
