@@ -986,85 +986,92 @@ inline void overlap_save_real_stream(Receiver<View<float>> u, Sender<View<float>
                                               [&](const View<float> &d, float *o, size_t *got, void *st) { return redio_ovsave_real_stream_enqueue(s, d.data(), d.len, o, got, st); });
 }
 
+namespace detail {
+// what the six power-spectrum blocks differ in: the plan's functions, a message's element type and how many of them make a sample
+struct PspecCf32 {
+    using In = std::complex<float>; using Plan = redio_pspec; using Stream = redio_pspec_stream;
+    static constexpr size_t per_sample = 1;
+    static constexpr auto create = redio_pspec_create;
+    static constexpr auto destroy = redio_pspec_destroy;
+    static constexpr auto nrows = redio_pspec_nrows;
+    static constexpr auto enqueue = redio_pspec_enqueue;
+    static constexpr auto stream_create = redio_pspec_stream_create;
+    static constexpr auto stream_destroy = redio_pspec_stream_destroy;
+    static constexpr auto stream_nout = redio_pspec_stream_nout;
+    static constexpr auto stream_enqueue = redio_pspec_stream_enqueue;
+    static size_t bins(const Plan *, int nfft) { return (size_t)nfft; }
+};
+struct PspecU8 : PspecCf32 { // a message holds whole samples (an even byte count); the stream carries its history as bytes
+    using In = uint8_t;
+    static constexpr size_t per_sample = 2;
+    static constexpr auto enqueue = redio_pspec_enqueue_u8;
+    static constexpr auto stream_create = redio_pspec_stream_create_u8;
+};
+struct PspecReal {
+    using In = float; using Plan = redio_pspec_real; using Stream = redio_pspec_real_stream;
+    static constexpr size_t per_sample = 1;
+    static constexpr auto create = redio_pspec_real_create;
+    static constexpr auto destroy = redio_pspec_real_destroy;
+    static constexpr auto nrows = redio_pspec_real_nrows;
+    static constexpr auto enqueue = redio_pspec_real_enqueue;
+    static constexpr auto stream_create = redio_pspec_real_stream_create;
+    static constexpr auto stream_destroy = redio_pspec_real_stream_destroy;
+    static constexpr auto stream_nout = redio_pspec_real_stream_nout;
+    static constexpr auto stream_enqueue = redio_pspec_real_stream_enqueue;
+    static size_t bins(const Plan *h, int) { return redio_pspec_real_nbins(h); }
+};
+
+// per-message semantics: the rows that fit in each message, a trailing partial row dropped
+template <typename T>
+void pspec_block(Receiver<View<typename T::In>> &u, Sender<View<float>> &v, int nfft, size_t integrate, size_t step, const std::vector<float> &window)
+{
+    using In = typename T::In;
+    typename T::Plan *h = nullptr;
+    check(T::create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
+    struct G { typename T::Plan *h; ~G() { T::destroy(h); } } g{h};
+    run_block<In, float>(u, v, [&](const View<In> &d) { return T::nrows(h, d.len / T::per_sample) * T::bins(h, nfft); },
+                         [&](const View<In> &d, const View<float> &o, void *st) { return T::enqueue(h, d.data(), d.len, o.data(), st); });
+}
+
+// a STREAM: messages of any length give the rows of one call on the whole stream; a message that completes no row sends nothing
+template <typename T>
+void pspec_stream_block(Receiver<View<typename T::In>> &u, Sender<View<float>> &v, int nfft, size_t integrate, size_t step, const std::vector<float> &window)
+{
+    using In = typename T::In;
+    typename T::Plan *h = nullptr;
+    check(T::create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
+    typename T::Stream *s = nullptr;
+    const int rc = T::stream_create(&s, h);
+    struct G { typename T::Plan *h; typename T::Stream *s; ~G() { T::stream_destroy(s); T::destroy(h); } } g{h, s};
+    check(rc);
+    run_stream_block_of<In, float>(u, v, [&](size_t len) { return T::stream_nout(s, len / T::per_sample); },
+                                   [&](const View<In> &d, float *o, size_t *got, void *st) {
+                                       if (d.len % T::per_sample) return (int)REDIO_ERR_ARG;
+                                       return T::stream_enqueue(s, d.data(), d.len / T::per_sample, o, got, st);
+                                   });
+}
+} // namespace detail
+
 // the integrated power spectrum (redio_pspec_*: |X|^2 of nfft-point kissfft::fft blocks that start every `step` samples, summed over
 // `integrate` transforms; window: empty or nfft values): cf32 messages in, rows of nfft f32 out, per-message semantics -- the rows
 // that fit in each message, a trailing partial row dropped
-inline void power_spectrum(Receiver<View<std::complex<float>>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {})
-{
-    using cf = std::complex<float>;
-    redio_pspec *h = nullptr;
-    check(redio_pspec_create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
-    struct G { redio_pspec *h; ~G() { redio_pspec_destroy(h); } } g{h};
-    detail::run_block<cf, float>(u, v, [&](const View<cf> &d) { return redio_pspec_nrows(h, d.len) * (size_t)nfft; },
-                                 [&](const View<cf> &d, const View<float> &o, void *st) { return redio_pspec_enqueue(h, d.data(), d.len, o.data(), st); });
-}
-
+inline void power_spectrum(Receiver<View<std::complex<float>>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {}) { detail::pspec_block<detail::PspecCf32>(u, v, nfft, integrate, step, window); }
 // the same as a STREAM: messages of any length give the rows of one call on the whole stream; a message that completes no row sends nothing
-inline void power_spectrum_stream(Receiver<View<std::complex<float>>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {})
-{
-    using cf = std::complex<float>;
-    redio_pspec *h = nullptr;
-    check(redio_pspec_create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
-    redio_pspec_stream *s = nullptr;
-    const int rc = redio_pspec_stream_create(&s, h);
-    struct G { redio_pspec *h; redio_pspec_stream *s; ~G() { redio_pspec_stream_destroy(s); redio_pspec_destroy(h); } } g{h, s};
-    check(rc);
-    detail::run_stream_block_of<cf, float>(u, v, [&](size_t len) { return redio_pspec_stream_nout(s, len); },
-                                           [&](const View<cf> &d, float *o, size_t *got, void *st) { return redio_pspec_stream_enqueue(s, d.data(), d.len, o, got, st); });
-}
+inline void power_spectrum_stream(Receiver<View<std::complex<float>>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {}) { detail::pspec_stream_block<detail::PspecCf32>(u, v, nfft, integrate, step, window); }
 
 // the receiver's messages straight into the power spectrum: u8 I/Q bytes (rtlsdr::rtlSource, rtlsdr.rs:127-152) -> data_to_samples
 // (rtlsdr.rs:159-162) -> the block above, without the cf32 intermediate (redio_pspec_enqueue_u8: ONE kernel at nfft = 1024); a
 // message holds whole samples (an even byte count)
-inline void power_spectrum_u8(Receiver<View<uint8_t>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {})
-{
-    redio_pspec *h = nullptr;
-    check(redio_pspec_create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
-    struct G { redio_pspec *h; ~G() { redio_pspec_destroy(h); } } g{h};
-    detail::run_block<uint8_t, float>(u, v, [&](const View<uint8_t> &d) { return redio_pspec_nrows(h, d.len / 2) * (size_t)nfft; },
-                                      [&](const View<uint8_t> &d, const View<float> &o, void *st) { return redio_pspec_enqueue_u8(h, d.data(), d.len, o.data(), st); });
-}
-
+inline void power_spectrum_u8(Receiver<View<uint8_t>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {}) { detail::pspec_block<detail::PspecU8>(u, v, nfft, integrate, step, window); }
 // the same as a STREAM (redio_pspec_stream_create_u8: the history is carried as bytes)
-inline void power_spectrum_stream_u8(Receiver<View<uint8_t>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {})
-{
-    redio_pspec *h = nullptr;
-    check(redio_pspec_create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
-    redio_pspec_stream *s = nullptr;
-    const int rc = redio_pspec_stream_create_u8(&s, h);
-    struct G { redio_pspec *h; redio_pspec_stream *s; ~G() { redio_pspec_stream_destroy(s); redio_pspec_destroy(h); } } g{h, s};
-    check(rc);
-    detail::run_stream_block_of<uint8_t, float>(u, v, [&](size_t len) { return redio_pspec_stream_nout(s, len / 2); },
-                                                [&](const View<uint8_t> &d, float *o, size_t *got, void *st) {
-                                                    if (d.len & 1) return (int)REDIO_ERR_ARG;
-                                                    return redio_pspec_stream_enqueue(s, d.data(), d.len / 2, o, got, st);
-                                                });
-}
+inline void power_spectrum_stream_u8(Receiver<View<uint8_t>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {}) { detail::pspec_stream_block<detail::PspecU8>(u, v, nfft, integrate, step, window); }
 
 // the real-input integrated power spectrum (redio_pspec_real_*: |X|^2 of nfft-point kiss_fftr rows that start every `step` real
 // samples, summed over `integrate` transforms; window: empty or nfft values): f32 messages in, rows of nfft / 2 + 1 f32 out,
-// per-message semantics -- the rows that fit in each message, a trailing partial row dropped
-inline void power_spectrum_real(Receiver<View<float>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {})
-{
-    redio_pspec_real *h = nullptr;
-    check(redio_pspec_real_create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
-    struct G { redio_pspec_real *h; ~G() { redio_pspec_real_destroy(h); } } g{h};
-    detail::run_block<float, float>(u, v, [&](const View<float> &d) { return redio_pspec_real_nrows(h, d.len) * redio_pspec_real_nbins(h); },
-                                    [&](const View<float> &d, const View<float> &o, void *st) { return redio_pspec_real_enqueue(h, d.data(), d.len, o.data(), st); });
-}
-
+// per-message semantics
+inline void power_spectrum_real(Receiver<View<float>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {}) { detail::pspec_block<detail::PspecReal>(u, v, nfft, integrate, step, window); }
 // the same as a STREAM: messages of any length, odd ones included, give the rows of one call on the whole stream
-inline void power_spectrum_real_stream(Receiver<View<float>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {})
-{
-    redio_pspec_real *h = nullptr;
-    check(redio_pspec_real_create(&h, nfft, integrate, step, window.empty() ? nullptr : window.data()));
-    redio_pspec_real_stream *s = nullptr;
-    const int rc = redio_pspec_real_stream_create(&s, h);
-    struct G { redio_pspec_real *h; redio_pspec_real_stream *s; ~G() { redio_pspec_real_stream_destroy(s); redio_pspec_real_destroy(h); } } g{h, s};
-    check(rc);
-    detail::run_stream_block_of<float, float>(u, v, [&](size_t len) { return redio_pspec_real_stream_nout(s, len); },
-                                              [&](const View<float> &d, float *o, size_t *got, void *st) { return redio_pspec_real_stream_enqueue(s, d.data(), d.len, o, got, st); });
-}
+inline void power_spectrum_real_stream(Receiver<View<float>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {}) { detail::pspec_stream_block<detail::PspecReal>(u, v, nfft, integrate, step, window); }
 
 } // namespace dev
 } // namespace kpn

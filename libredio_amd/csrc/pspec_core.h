@@ -87,16 +87,19 @@ RD_HD void pspec1k_accum(const float2 (&v)[16], float (&seg)[16], bool first)
         for (int i = 0; i < 16; ++i) seg[i] = add_rn(seg[i], pspec_power(v[i]));
     }
 }
-RD_HD void pspec1k_fold(const float (&seg)[16], float (&row)[16], bool first)
+// a finished segment into the row accumulator, over the R registers a lane holds (16 here, 17 in the real plan's fused kernel)
+template <int R>
+RD_HD void pspec_fold_regs(const float (&seg)[R], float (&row)[R], bool first)
 {
     if (first) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) row[i] = seg[i];
+        for (int i = 0; i < R; ++i) row[i] = seg[i];
     } else {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) row[i] = add_rn(row[i], seg[i]);
+        for (int i = 0; i < R; ++i) row[i] = add_rn(row[i], seg[i]);
     }
 }
+RD_HD void pspec1k_fold(const float (&seg)[16], float (&row)[16], bool first) { pspec_fold_regs(seg, row, first); }
 // dst: the unit's 1024 f32 (a row of the output, or a segment's partial)
 template <typename OutPtr>
 RD_HD void pspec1k_store(const float (&row)[16], OutPtr dst, int lane)

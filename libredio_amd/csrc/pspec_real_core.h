@@ -95,16 +95,7 @@ RD_HD void pspecr2k_accum(const float (&p)[17], float (&seg)[17], bool first)
         for (int i = 0; i < 17; ++i) seg[i] = add_rn(seg[i], p[i]);
     }
 }
-RD_HD void pspecr2k_fold(const float (&seg)[17], float (&row)[17], bool first)
-{
-    if (first) {
-#pragma unroll
-        for (int i = 0; i < 17; ++i) row[i] = seg[i];
-    } else {
-#pragma unroll
-        for (int i = 0; i < 17; ++i) row[i] = add_rn(row[i], seg[i]);
-    }
-}
+RD_HD void pspecr2k_fold(const float (&seg)[17], float (&row)[17], bool first) { pspec_fold_regs(seg, row, first); }
 // dst: the unit's 1025 f32 (a row of the output, or a segment's partial; only 4-byte aligned): eight ascending and eight descending
 // wave-wide stores and lane 0's bin 512 -- every element once
 template <typename OutPtr>

@@ -7,7 +7,7 @@
 //                           spectra never leave the wave.  4 N / step bytes read and about 2 / K written per real sample.
 //   pspec_real_rows_kernel  every other even N: the row gather (window, overlap, 4-byte aligned streams) ahead of the plan's own
 //                           redio_fftr; the accumulate and fold passes are pspec_kernels.hip's with a row of N / 2 + 1 bins
-//                           (pspec_real_api.hip).  The fold also ends the fused kernel's segment mode.
+//                           (pspec_api.hip).  The fold also ends the fused kernel's segment mode.
 #include "redio_internal.h"
 #include "fft_wave.h"
 #include "pspec_real_core.h"

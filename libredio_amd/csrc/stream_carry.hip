@@ -62,6 +62,7 @@ struct Carry {
     void *plan = nullptr;                 // not owned: the plan must outlive the stream handle
     size_t W = 0, H = 0;                  // window and hop, in input samples
     size_t in_elem = 0;                   // bytes per input sample
+    uintptr_t align = 0;                  // mask a message's pointer is refused on (the power spectrum's u8 and real streams: a whole-sample boundary)
     size_t unit_out = 0, out_elem = 0;    // output samples per unit, bytes per output sample
     char *d_s[2] = {nullptr, nullptr};    // staging buffers, 2*W input samples each
     int cur = 0;
@@ -99,13 +100,13 @@ int run(const Carry &c, const void *d_in, size_t n_in, void *d_out, void *stream
     return REDIO_ERR_ARG;
 }
 
-int carry_create(Carry **out, Kind kind, void *plan, int device, size_t W, size_t H, size_t in_elem, size_t unit_out, size_t out_elem)
+int carry_create(Carry **out, Kind kind, void *plan, int device, size_t W, size_t H, size_t in_elem, size_t unit_out, size_t out_elem, uintptr_t align)
 {
     *out = nullptr;
     if (!plan || W == 0 || H == 0) return REDIO_ERR_ARG;
     Carry *c = new (std::nothrow) Carry();
     if (!c) return REDIO_ERR_NOMEM;
-    c->device = device; c->kind = kind; c->plan = plan; c->W = W; c->H = H; c->in_elem = in_elem; c->unit_out = unit_out; c->out_elem = out_elem;
+    c->device = device; c->kind = kind; c->plan = plan; c->W = W; c->H = H; c->in_elem = in_elem; c->unit_out = unit_out; c->out_elem = out_elem; c->align = align;
     hipError_t e = hipSetDevice(device);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMalloc((void **)&c->d_s[i], 2 * W * in_elem);
     if (e != hipSuccess) {
@@ -138,8 +139,7 @@ int carry_enqueue(Carry *c, const void *d_new, size_t n, void *d_out, size_t *no
     if (!guard.ok()) return REDIO_ERR_ARG; // another thread is inside this stream: its counters are not ours to move
     if (n == 0) return REDIO_OK;
     if (!d_new) return REDIO_ERR_ARG;
-    if (c->kind == K_PSPEC_U8 && ((uintptr_t)d_new & 1)) return REDIO_ERR_ARG; // a whole-sample boundary, refused before the seam copy
-    if (c->kind == K_PSPEC_REAL && ((uintptr_t)d_new & 3)) return REDIO_ERR_ARG; // likewise
+    if ((uintptr_t)d_new & c->align) return REDIO_ERR_ARG; // a whole-sample boundary, refused before the seam copy
     REDIO_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     const char *src = (const char *)d_new;
@@ -250,10 +250,10 @@ RD_STREAM_API(pspec)
 RD_STREAM_API(pspec_real)
 
 template <typename Hd>
-static int make(Hd **h, Kind kind, void *plan, int dev, size_t W, size_t H, size_t in_elem, size_t unit_out, size_t out_elem)
+static int make(Hd **h, Kind kind, void *plan, int dev, size_t W, size_t H, size_t in_elem, size_t unit_out, size_t out_elem, uintptr_t align = 0)
 {
     Carry *c = nullptr;
-    const int rc = carry_create(&c, kind, plan, dev, W, H, in_elem, unit_out, out_elem);
+    const int rc = carry_create(&c, kind, plan, dev, W, H, in_elem, unit_out, out_elem, align);
     if (rc) return rc;
     Hd *p = new (std::nothrow) Hd();
     if (!p) { carry_destroy(c); return REDIO_ERR_NOMEM; }
@@ -341,45 +341,33 @@ extern "C" int redio_ovsave_real_stream_create(redio_ovsave_real_stream **h, red
     if (rr) return rr;
     return make(h, K_OVSAVE_REAL, plan, dev, (size_t)nfft, hop, 4, hop, 4);
 }
+// The power spectrum's three streams: W and H in input samples of in_elem bytes (cf32; u8 I/Q byte pairs, carried as bytes; f32 for the
+// real plan, where a message may start and end on any sample), rows of `bins` f32 out.  The plan's scratch is sized here for the seam
+// windows (at most 2*W samples per head run, which `reserve` takes in its own entry's units: reserve_per_sample of them per sample);
+// a longer body run grows it at enqueue time unless the plan's reserve for the largest message + W came first.
+template <typename Hd, typename Plan>
+static int make_pspec(Hd **h, Plan *plan, Kind kind, void (*shape)(const Plan *, int *, size_t *, size_t *, int *), int (*reserve)(Plan *, size_t),
+                      size_t reserve_per_sample, size_t in_elem, uintptr_t align, bool half_bins)
+{
+    if (!h) return REDIO_ERR_ARG;
+    *h = nullptr;
+    if (!plan) return REDIO_ERR_ARG;
+    int nfft, dev; size_t K, step;
+    shape(plan, &nfft, &K, &step, &dev);
+    const size_t W = (K - 1) * step + (size_t)nfft;
+    const int rr = reserve(plan, reserve_per_sample * 2 * W);
+    if (rr) return rr;
+    return make(h, kind, plan, dev, W, K * step, in_elem, half_bins ? (size_t)nfft / 2 + 1 : (size_t)nfft, 4, align);
+}
 extern "C" int redio_pspec_stream_create(redio_pspec_stream **h, redio_pspec *plan)
 {
-    if (!h) return REDIO_ERR_ARG;
-    *h = nullptr;
-    if (!plan) return REDIO_ERR_ARG;
-    int nfft, dev; size_t K, step;
-    redio_pspec_shape(plan, &nfft, &K, &step, &dev);
-    const size_t W = (K - 1) * step + (size_t)nfft;
-    // the plan's scratch, sized here for the seam windows (at most 2*W samples per head run); a longer body run grows it at enqueue
-    // time unless redio_pspec_reserve(plan, largest message + W) came first
-    const int rr = redio_pspec_reserve(plan, 2 * W);
-    if (rr) return rr;
-    return make(h, K_PSPEC, plan, dev, W, K * step, 8, (size_t)nfft, 4);
+    return make_pspec(h, plan, K_PSPEC, redio_pspec_shape, redio_pspec_reserve, 1, 8, 0, false);
 }
-// the same stream fed with the receiver's u8 I/Q bytes: the history is carried as bytes and every window runs redio_pspec_enqueue_u8
 extern "C" int redio_pspec_stream_create_u8(redio_pspec_stream **h, redio_pspec *plan)
 {
-    if (!h) return REDIO_ERR_ARG;
-    *h = nullptr;
-    if (!plan) return REDIO_ERR_ARG;
-    int nfft, dev; size_t K, step;
-    redio_pspec_shape(plan, &nfft, &K, &step, &dev);
-    const size_t W = (K - 1) * step + (size_t)nfft;
-    const int rr = redio_pspec_reserve_u8(plan, 2 * (2 * W)); // seam windows; see redio_pspec_stream_create
-    if (rr) return rr;
-    return make(h, K_PSPEC_U8, plan, dev, W, K * step, 2, (size_t)nfft, 4);
+    return make_pspec(h, plan, K_PSPEC_U8, redio_pspec_shape, redio_pspec_reserve_u8, 2, 2, 1, false);
 }
-// the real-input power spectrum: 4-byte samples, rows of nfft / 2 + 1 f32; a message may start and end on any sample
 extern "C" int redio_pspec_real_stream_create(redio_pspec_real_stream **h, redio_pspec_real *plan)
 {
-    if (!h) return REDIO_ERR_ARG;
-    *h = nullptr;
-    if (!plan) return REDIO_ERR_ARG;
-    int nfft, dev; size_t K, step;
-    redio_pspec_real_shape(plan, &nfft, &K, &step, &dev);
-    const size_t W = (K - 1) * step + (size_t)nfft;
-    // the plan's scratch, sized here for the seam windows (at most 2*W samples per head run); a longer body run grows it at enqueue
-    // time unless redio_pspec_real_reserve(plan, largest message + W) came first
-    const int rr = redio_pspec_real_reserve(plan, 2 * W);
-    if (rr) return rr;
-    return make(h, K_PSPEC_REAL, plan, dev, W, K * step, 4, (size_t)nfft / 2 + 1, 4);
+    return make_pspec(h, plan, K_PSPEC_REAL, redio_pspec_real_shape, redio_pspec_real_reserve, 1, 4, 3, true);
 }

@@ -701,128 +701,91 @@ class OverlapSaveReal:
             self._h = None
 
 
-class PowerSpectrum:
+class _PowerSpectrumBase:
+    """what PowerSpectrum and PowerSpectrumReal share: a subclass gives its C symbols' prefix, its input dtype and its bins per row"""
+
+    AUTO, ROWS, SEGMENTS = 0, 1, 2
+    _prefix = _in_dtype = None
+
+    def _fn(self, name):
+        return getattr(lib(), f"redio_{self._prefix}_{name}")
+
+    def __init__(self, bins, nfft, integrate, step, window):
+        self.nfft, self.integrate, self._bins = int(nfft), int(integrate), int(bins)
+        self.step = self.nfft if step is None else int(step)
+        p = None
+        if window is not None:
+            w, p = _taps(window)
+            assert len(w) == self.nfft, "a window of nfft values"
+        self._h = C.c_void_p()
+        check(self._fn("create")(C.byref(self._h), self.nfft, self.integrate, self.step, p), f"{self._prefix}_create")
+
+    def nrows(self, n_in):
+        return self._fn("nrows")(self._h, n_in)
+
+    @property
+    def is_fused(self):
+        return bool(self._fn("is_fused")(self._h))
+
+    def reserve(self, n_in):
+        check(self._fn("reserve")(self._h, n_in), f"{self._prefix}_reserve")
+
+    def set_split(self, mode):
+        """AUTO / ROWS (one wavefront per whole row) / SEGMENTS (one per segment of 16 transforms and a fold pass): the same bits."""
+        check(self._fn("set_split")(self._h, int(mode)), f"{self._prefix}_set_split")
+
+    def _run(self, name, x, dtype, count, rows, out):
+        import torch
+        assert x.dtype == getattr(torch, dtype), f"expected torch.{dtype}"
+        if out is None:
+            out = torch.empty(rows * self._bins, dtype=torch.float32, device=x.device)
+        assert out.dtype == torch.float32 and out.numel() >= rows * self._bins
+        check(self._fn(name)(self._h, _dev_ptr(x), count, _dev_ptr(out), current_stream()), f"{self._prefix}_{name}")
+        return out[: rows * self._bins].view(rows, self._bins)
+
+    def __call__(self, x, out=None):
+        return self._run("enqueue", x, self._in_dtype, x.numel(), self.nrows(x.numel()), out)
+
+    def spectra(self, X, out=None):
+        """the same integration over packed, already transformed rows of that many bins (a Chain's or an Fftr's output): numel // bins //
+        integrate rows"""
+        nbatch = X.numel() // self._bins
+        return self._run("enqueue_spectra", X, "complex64", nbatch, nbatch // self.integrate, out)
+
+    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
+        if getattr(self, "_h", None):
+            _safe_destroy(f"redio_{self._prefix}_destroy", self._h)
+            self._h = None
+
+
+class PowerSpectrum(_PowerSpectrumBase):
     """redio_pspec_*: |X[k]|^2 of kissfft::fft blocks (kissfft.rs:18-31) of nfft samples that start every `step` samples, optionally
     windowed, summed over `integrate` consecutive transforms in the blocked order of DESIGN.md 5.3c: complex64 samples in, rows of
     nfft float32 out.  nfft = 1024 is one kernel (is_fused)."""
 
-    AUTO, ROWS, SEGMENTS = 0, 1, 2
+    _prefix, _in_dtype = "pspec", "complex64"
 
     def __init__(self, nfft=1024, integrate=1, step=None, window=None):
-        self.nfft, self.integrate = int(nfft), int(integrate)
-        self.step = self.nfft if step is None else int(step)
-        p = None
-        if window is not None:
-            w, p = _taps(window)
-            assert len(w) == self.nfft, "a window of nfft values"
-        self._h = C.c_void_p()
-        check(lib().redio_pspec_create(C.byref(self._h), self.nfft, self.integrate, self.step, p), "pspec_create")
-
-    def nrows(self, n_in):
-        return lib().redio_pspec_nrows(self._h, n_in)
-
-    @property
-    def is_fused(self):
-        return bool(lib().redio_pspec_is_fused(self._h))
-
-    def reserve(self, n_in):
-        check(lib().redio_pspec_reserve(self._h, n_in), "pspec_reserve")
-
-    def set_split(self, mode):
-        """AUTO / ROWS (one wavefront per whole row) / SEGMENTS (one per segment of 16 transforms and a fold pass): the same bits."""
-        check(lib().redio_pspec_set_split(self._h, int(mode)), "pspec_set_split")
-
-    def _run(self, fn, x, count, rows, out):
-        import torch
-        assert x.dtype == torch.complex64
-        if out is None:
-            out = torch.empty(rows * self.nfft, dtype=torch.float32, device=x.device)
-        assert out.dtype == torch.float32 and out.numel() >= rows * self.nfft
-        check(fn(self._h, _dev_ptr(x), count, _dev_ptr(out), current_stream()), "pspec_enqueue")
-        return out[: rows * self.nfft].view(rows, self.nfft)
-
-    def __call__(self, x, out=None):
-        return self._run(lib().redio_pspec_enqueue, x, x.numel(), self.nrows(x.numel()), out)
+        super().__init__(nfft, nfft, integrate, step, window)
 
     def u8(self, raw, out=None):
         """the receiver's interleaved u8 I/Q bytes in (uint8 tensor, even numel): the rows of data_to_samples + __call__, bit for
         bit, without the cf32 intermediate (redio_pspec_enqueue_u8)"""
-        import torch
-        assert raw.dtype == torch.uint8 and raw.numel() % 2 == 0, "expected an even number of uint8 bytes"
-        rows = self.nrows(raw.numel() // 2)
-        if out is None:
-            out = torch.empty(rows * self.nfft, dtype=torch.float32, device=raw.device)
-        assert out.dtype == torch.float32 and out.numel() >= rows * self.nfft
-        check(lib().redio_pspec_enqueue_u8(self._h, _dev_ptr(raw), raw.numel(), _dev_ptr(out), current_stream()), "pspec_enqueue_u8")
-        return out[: rows * self.nfft].view(rows, self.nfft)
+        assert raw.numel() % 2 == 0, "expected an even number of uint8 bytes"
+        return self._run("enqueue_u8", raw, "uint8", raw.numel(), self.nrows(raw.numel() // 2), out)
 
     def reserve_u8(self, nbytes):
         check(lib().redio_pspec_reserve_u8(self._h, nbytes), "pspec_reserve_u8")
 
-    def spectra(self, X, out=None):
-        """the same integration over packed, already transformed rows of nfft bins (a Chain's output): numel // nfft // integrate rows"""
-        nbatch = X.numel() // self.nfft
-        return self._run(lib().redio_pspec_enqueue_spectra, X, nbatch, nbatch // self.integrate, out)
 
-    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
-        if getattr(self, "_h", None):
-            _safe_destroy("redio_pspec_destroy", self._h)
-            self._h = None
-
-
-class PowerSpectrumReal:
+class PowerSpectrumReal(_PowerSpectrumBase):
     """redio_pspec_real_*: |X[k]|^2 of kiss_fftr rows (tools/kiss_fftr.c, the bits of Fftr) of nfft REAL samples that start every
     `step` samples, optionally windowed, summed over `integrate` consecutive transforms in the blocked order of DESIGN.md 5.3c
     (contract: DESIGN.md 5.3d): float32 samples in, rows of nbins = nfft/2 + 1 float32 out.  nfft = 2048 is one kernel (is_fused)."""
 
-    AUTO, ROWS, SEGMENTS = 0, 1, 2
+    _prefix, _in_dtype = "pspec_real", "float32"
 
     def __init__(self, nfft=2048, integrate=1, step=None, window=None):
-        self.nfft, self.integrate = int(nfft), int(integrate)
-        self.step = self.nfft if step is None else int(step)
-        self.nbins = self.nfft // 2 + 1
-        p = None
-        if window is not None:
-            w, p = _taps(window)
-            assert len(w) == self.nfft, "a window of nfft values"
-        self._h = C.c_void_p()
-        check(lib().redio_pspec_real_create(C.byref(self._h), self.nfft, self.integrate, self.step, p), "pspec_real_create")
+        self.nbins = int(nfft) // 2 + 1
+        super().__init__(self.nbins, nfft, integrate, step, window)
         assert lib().redio_pspec_real_nbins(self._h) == self.nbins
-
-    def nrows(self, n_in):
-        return lib().redio_pspec_real_nrows(self._h, n_in)
-
-    @property
-    def is_fused(self):
-        return bool(lib().redio_pspec_real_is_fused(self._h))
-
-    def reserve(self, n_in):
-        check(lib().redio_pspec_real_reserve(self._h, n_in), "pspec_real_reserve")
-
-    def set_split(self, mode):
-        """AUTO / ROWS (one wavefront per whole row) / SEGMENTS (one per segment of 16 transforms and a fold pass): the same bits."""
-        check(lib().redio_pspec_real_set_split(self._h, int(mode)), "pspec_real_set_split")
-
-    def _run(self, fn, x, dtype, count, rows, out):
-        import torch
-        assert x.dtype == dtype, f"expected {dtype}"
-        if out is None:
-            out = torch.empty(rows * self.nbins, dtype=torch.float32, device=x.device)
-        assert out.dtype == torch.float32 and out.numel() >= rows * self.nbins
-        check(fn(self._h, _dev_ptr(x), count, _dev_ptr(out), current_stream()), "pspec_real_enqueue")
-        return out[: rows * self.nbins].view(rows, self.nbins)
-
-    def __call__(self, x, out=None):
-        import torch
-        return self._run(lib().redio_pspec_real_enqueue, x, torch.float32, x.numel(), self.nrows(x.numel()), out)
-
-    def spectra(self, X, out=None):
-        """the same integration over packed, already transformed rows of nbins bins (an Fftr's output): numel // nbins // integrate rows"""
-        import torch
-        nbatch = X.numel() // self.nbins
-        return self._run(lib().redio_pspec_real_enqueue_spectra, X, torch.complex64, nbatch, nbatch // self.integrate, out)
-
-    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
-        if getattr(self, "_h", None):
-            _safe_destroy("redio_pspec_real_destroy", self._h)
-            self._h = None

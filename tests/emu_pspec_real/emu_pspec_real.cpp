@@ -109,7 +109,7 @@ extern "C" void emu_pspec_real_rows(const float *x, const float *win, long ntr, 
 }
 
 // pspec_accum_kernel's threads over every segment of nrows rows of K packed spectra of B = N / 2 + 1 bins (part: B f32 per segment),
-// then pspec_fold_kernel's threads (out: B f32 per row), as pspec_real_api.hip launches them; stores_part / stores_out: writes per element
+// then pspec_fold_kernel's threads (out: B f32 per row), as pspec_api.hip launches them; stores_part / stores_out: writes per element
 extern "C" void emu_pspec_real_generic(const float2 *spec, long B, long K, long nrows, float *part, float *out, int *stores_part, int *stores_out)
 {
     const long S = pspec_nseg(K);

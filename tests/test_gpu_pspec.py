@@ -106,6 +106,28 @@ def test_spectra_of_the_chain(gpu, redio, oracle):
     assert np.array_equal(bits(short), bits(ref.spectra(X, N, 3))) and short.shape == (11, N)
 
 
+def test_scratch_regrows_between_calls_on_one_plan(gpu, redio, oracle):
+    """N = 96, K = 17 (two segments, the second of one transform), step 48, windowed, one plan: a 1-row call, the integration of 2 rows
+    of spectra, a 9-row call that regrows the row scratch and the partials, 11 rows of spectra that regrow the partials once more, and
+    the 1-row call again on scratch that is now larger than it needs"""
+    N, K, step = 96, 17, 48
+    w = window_of(oracle, N, True)
+    W, H = ref.shape(N, K, step)
+    x = oracle.synth_iq(SEED + 8, 0, W + 8 * H)
+    want = ref.power_spectrum(x, N, K, step, w)
+    X = oracle.fft(oracle.synth_iq(SEED + 9, 0, 11 * K * N), N)
+    want_spectra = ref.spectra(X, N, K)
+    assert want.shape == (9, N) and want_spectra.shape == (11, N)
+    plan = redio.PowerSpectrum(N, K, step, w)
+    assert not plan.is_fused
+    xd, Xd = gpu.from_numpy(x).cuda(), gpu.from_numpy(X).cuda()
+    for rows, spectra_rows in ((1, 2), (9, 11), (1, None)):
+        assert np.array_equal(bits(run(gpu, plan, xd[: W + (rows - 1) * H])), bits(want[:rows])), rows
+        if spectra_rows:
+            got = plan.spectra(Xd[: spectra_rows * K * N]).cpu().numpy()
+            assert np.array_equal(bits(got), bits(want_spectra[:spectra_rows])), spectra_rows
+
+
 @pytest.mark.parametrize("N,K,step,mode", [(1024, 17, 512, 1), (1024, 17, 512, 2), (1000, 5, 1000, 0), (64, 33, 64, 0)])
 def test_reserve_then_capture_and_replay(gpu, redio, oracle, N, K, step, mode):
     w = window_of(oracle, N, True)

@@ -88,6 +88,22 @@ def test_generic_bit_exact(gpu, redio, oracle, N, K, step, windowed):
     assert np.array_equal(bits(run(plan, buf[1:])), bits(want)), "offset"
 
 
+def test_scratch_regrows_between_calls_on_one_plan(gpu, redio, oracle):
+    """N = 96, K = 17 (two segments, the second of one transform), step 48, windowed, one plan: a 1-row call, a 9-row call that regrows
+    the row scratch, the spectrum scratch, the transform's own and the partials, and the 1-row call again"""
+    N, K, step = 96, 17, 48
+    w = window_of(oracle, N, True)
+    W, H = ref.shape(N, K, step)
+    x = oracle.synth_f32(SEED + 8, 0, W + 8 * H)
+    want = ref.power_spectrum(x, N, K, step, w)
+    assert want.shape == (9, N // 2 + 1)
+    plan = redio.PowerSpectrumReal(N, K, step, w)
+    assert not plan.is_fused
+    xd = gpu.from_numpy(x).cuda()
+    for rows in (1, 9, 1):
+        assert np.array_equal(bits(run(plan, xd[: W + (rows - 1) * H])), bits(want[:rows])), rows
+
+
 def test_generic_across_the_chunk_loop(gpu, redio, oracle):
     """N = 4096, K = 17: a pass through the spectrum scratch takes (64 MiB) / (2049 * 8 * 16) = 255 segments, so the first seam falls
     between the two segments of row 127.  The first row, the rows either side of the seam and the last against the restatement

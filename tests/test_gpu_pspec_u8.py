@@ -118,6 +118,33 @@ def test_generic_bit_exact(gpu, redio, oracle, N, K, step, windowed):
     assert np.array_equal(bits(plan.u8(rd[: 2 * W]).cpu().numpy()), bits(want[:1]))
 
 
+@pytest.mark.parametrize("N", [96, 2048])
+def test_scratch_regrows_between_calls_on_one_plan(gpu, redio, oracle, N):
+    """K = 17 (two segments, the second of one transform), step N / 2, windowed, one plan, at a size that gathers and transforms in
+    place (96) and at one whose transform reads the bytes itself (2048): a 1-row call, the integration of 2 rows of spectra, a 9-row
+    call that regrows the row scratch and the partials, the cf32 entry on the same samples, 11 rows of spectra that regrow the
+    partials once more, and the 1-row call again"""
+    from libredio_amd import bitfount
+    K, step = 17, N // 2
+    w = window_of(oracle, N, True)
+    W, H = ref.shape(N, K, step)
+    raw = random_bytes(SEED + 8 + N, 2 * (W + 8 * H))
+    want = checker(oracle, raw, N, K, step, w)
+    X = oracle.fft(oracle.synth_iq(SEED + 9, 0, 11 * K * N), N)
+    want_spectra = ref.spectra(X, N, K)
+    assert want.shape == (9, N) and want_spectra.shape == (11, N)
+    plan = redio.PowerSpectrum(N, K, step, w)
+    assert not plan.is_fused
+    rd, Xd = gpu.from_numpy(raw).cuda(), gpu.from_numpy(X).cuda()
+    for rows, spectra_rows in ((1, 2), (9, 11), (1, None)):
+        nbytes = 2 * (W + (rows - 1) * H)
+        assert np.array_equal(bits(plan.u8(rd[:nbytes]).cpu().numpy()), bits(want[:rows])), rows
+        if spectra_rows:
+            assert np.array_equal(bits(plan(bitfount.data_to_samples(rd[:nbytes])).cpu().numpy()), bits(want[:rows])), rows
+            got = plan.spectra(Xd[: spectra_rows * K * N]).cpu().numpy()
+            assert np.array_equal(bits(got), bits(want_spectra[:spectra_rows])), spectra_rows
+
+
 def test_generic_across_the_chunk_loop(gpu, redio, oracle):
     """N = 4096, K = 17: 2100 transforms (17 MB of bytes) are 123 rows of two segments; a pass through the scratch takes 128 segments
     = 64 rows.  The first row, the rows either side of the seam and the last against the checker on their own windows."""
