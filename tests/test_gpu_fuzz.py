@@ -1,5 +1,7 @@
 """A short, seeded run of the randomised differential tool (tests/fuzz_parity.py): FIR, FFT, chain, overlap-save,
-channelizer and resampler against the oracle on random shapes, lengths, alignments and message cuts."""
+channelizer and resampler against the oracle on random shapes, lengths, alignments and message cuts.  The real-input transform, overlap-save
+on real streams, the power spectrum (cf32, u8 and real entries) and their streams are the other tool's, tests/fuzz_spectra.py, run by
+tests/test_gpu_fuzz_spectra.py."""
 import os
 import subprocess
 import sys

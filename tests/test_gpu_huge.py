@@ -4,6 +4,7 @@ Every kernel here was written with 64-bit unit indices and 32-bit offsets inside
 32-bit product crept in.  One cf32 stream of 2^32 + a ragged tail samples (34 GB) is generated on the device by the closed-form hash
  and pushed through each operator; the oracle recomputes, from nothing but its own input window, the outputs next to every
 boundary that matters: the start, byte offset 2^32 (sample 2^29), element 2^31, element 2^32, the end.  Bit-exact, as everywhere.
+The real-input and spectrum plans read narrower views of the same memory as f32 samples and as u8 I/Q bytes (second half of this file).
 Skipped when the device has less than 120 GB free."""
 import numpy as np
 import pytest
@@ -193,3 +194,135 @@ def test_resampler_past_2_32(gpu, redio, oracle, big):
         err, want, wused = oracle.Resampler(1).process(w, ratio, int(ratio * n + 1.0))
         assert err == 0 and wused == n
         assert same_bits(out[c].cpu().numpy(), want), c
+
+
+# ---- the real-input and spectrum plans --------------------------------------------------------------------------------------------------
+# The same stream seen three ways: cf32 samples, and -- narrower views of its first bytes -- NV f32 samples and NV u8 I/Q byte pairs,
+# so that element 2^32 of either view and byte offset 2^33 of the u8 one lie inside.  Every check recomputes the rows next to a mark
+# from its own window of the hash, through the restatements of tests/ (pspec_ref, pspec_real_ref, fftr_ref, ovsave_real_ref).
+NV = N
+
+
+def f32_view(gpu, big):
+    return gpu.view_as_real(big).reshape(-1)[:NV]
+
+
+def u8_view(gpu, big):
+    return gpu.view_as_real(big).reshape(-1).view(gpu.uint8)[: 2 * NV]
+
+
+def host_f32(oracle, lo, cnt):
+    """f32 words [lo, lo + cnt) of the stream"""
+    c0 = lo // 2
+    return oracle.synth_iq(SEED, c0, (lo + cnt + 1) // 2 - c0).view(np.float32)[lo - 2 * c0: lo - 2 * c0 + cnt]
+
+
+def host_u8(oracle, lo, cnt):
+    """the bytes of u8 I/Q samples [lo, lo + cnt) of the stream"""
+    b0, b1 = 2 * lo, 2 * (lo + cnt)
+    c0 = b0 // 8
+    return oracle.synth_iq(SEED, c0, (b1 + 7) // 8 - c0).view(np.uint8)[b0 - 8 * c0: b1 - 8 * c0]
+
+
+def check_rows(out, rows, W, H, want_of, more=()):
+    """rows of `out` next to every mark (and the rows `more` names) against want_of(first sample, sample count)"""
+    for b in sorted(set(marks(rows, H)) | {q for q in more if 0 <= q < rows}):
+        lo = max(0, min(b - 1, rows - 3))
+        cnt = min(3, rows - lo)
+        assert same_bits(out[lo:lo + cnt].cpu().numpy(), want_of(lo * H, (cnt - 1) * H + W)), b
+
+
+@pytest.mark.parametrize("nfft,k,step,windowed,mode", [(1024, 16, 1024, False, 1), (1024, 16, 1024, False, 2), (1024, 17, 1024, False, 2), (4096, 4, 4096, False, 0), (1024, 4, 512, True, 0)])
+def test_pspec_past_2_32(gpu, redio, oracle, big, nfft, k, step, windowed, mode):
+    """redio_pspec_enqueue: the fused kernel over 262 148 rows (1 GiB out) in both launch modes (at K = 16 a row is one segment, so
+    both launch a wave per row; K = 17 in mode 2 is the wave per segment with its 2 GiB of partials and the fold pass), the generic
+    path's chunk loop 2048 times over at 4096 points, and the fused kernel on overlapping windowed rows (2^21 of them)"""
+    import pspec_ref
+    w = oracle.lpf_corrected(nfft, 0.1) if windowed else None
+    W, H = pspec_ref.shape(nfft, k, step)
+    plan = redio.PowerSpectrum(nfft, k, step, w)
+    plan.set_split(mode)
+    rows = plan.nrows(N)
+    assert rows == (N - W) // H + 1 and plan.is_fused == (nfft == 1024)
+    out = plan(big)
+    assert tuple(out.shape) == (rows, nfft)
+    check_rows(out, rows, W, H, lambda lo, cnt: pspec_ref.power_spectrum(oracle.synth_iq(SEED, lo, cnt), nfft, k, step, w))
+    del out
+
+
+@pytest.mark.parametrize("nfft,k", [(1024, 16), (2048, 4), (1000, 4)])
+def test_pspec_u8_past_2_32(gpu, redio, oracle, big, nfft, k):
+    """redio_pspec_enqueue_u8 on 2^33 bytes and more: the fused kernel, the transform that converts at its own load (2048) and the
+    converting row gather (1000), whose 32-bit indices inside a chunk hold only because a chunk is small: there the rows either side of
+    the chunk seams next to every mark are compared as well"""
+    import pspec_ref
+    raw = u8_view(gpu, big)
+    assert raw.numel() == 2 * NV > 1 << 33
+    W, H = pspec_ref.shape(nfft, k, nfft)
+    plan = redio.PowerSpectrum(nfft, k)
+    rows = plan.nrows(NV)
+    assert rows == (NV - W) // H + 1
+    out = plan.u8(raw)
+    assert tuple(out.shape) == (rows, nfft)
+    chunk = max(1, (64 << 20) // (nfft * 8 * pspec_ref.SEG))   # rows per pass of the generic path (one segment per row at this K)
+    seams = [q for b in marks(rows, H) for q in (b // chunk * chunk, (b // chunk + 1) * chunk)] if nfft != 1024 else []
+    check_rows(out, rows, W, H, lambda lo, cnt: pspec_ref.power_spectrum(oracle.data_to_samples(host_u8(oracle, lo, cnt)), nfft, k), seams)
+    del out
+
+
+@pytest.mark.parametrize("nfft,k,mode", [(2048, 16, 1), (2048, 16, 2), (2048, 17, 2), (4096, 4, 0)])
+def test_pspec_real_past_2_32(gpu, redio, oracle, big, nfft, k, mode):
+    """redio_pspec_real_enqueue on 2^32 f32 samples and more: the fused kernel in both launch modes (one segment per row at K = 16;
+    K = 17 in mode 2 runs a wave per segment and the fold pass) and the generic path, whose transform reads the caller's buffer row by
+    row through the chunk loop"""
+    import pspec_real_ref
+    x = f32_view(gpu, big)
+    W, H = pspec_real_ref.shape(nfft, k, nfft)
+    plan = redio.PowerSpectrumReal(nfft, k)
+    plan.set_split(mode)
+    rows = plan.nrows(NV)
+    assert rows == (NV - W) // H + 1 and plan.is_fused == (nfft == 2048)
+    out = plan(x)
+    assert tuple(out.shape) == (rows, nfft // 2 + 1)
+    check_rows(out, rows, W, H, lambda lo, cnt: pspec_real_ref.power_spectrum(host_f32(oracle, lo, cnt), nfft, k))
+    del out
+
+
+@pytest.mark.parametrize("nfft", [2048, 1000])
+def test_fftr_past_2_32(gpu, redio, oracle, big, nfft):
+    """kiss_fftr over consecutive frames of 2^32 f32 samples (fused at 2048, the complex plan and the split pass at 1000): more than
+    2^31 bins come out, and kiss_fftri then takes five rows of them that lie across element 2^31 of that buffer"""
+    import fftr_ref
+    x = f32_view(gpu, big)
+    nb, nbins = NV // nfft, nfft // 2 + 1
+    assert nb * nbins > 1 << 31
+    plan = redio.Fftr(nfft)
+    assert plan.is_fused == (nfft == 2048)
+    out = plan(x[: nb * nfft]).view(nb, nbins)
+    check_rows(out, nb, nfft, nfft, lambda lo, cnt: fftr_ref.fftr_rows(host_f32(oracle, lo, cnt), nfft))
+    r0 = (1 << 31) // nbins - 2
+    assert r0 * nbins < 1 << 31 < (r0 + 5) * nbins
+    back = redio.Fftr(nfft, inverse=True)(out[r0:r0 + 5].reshape(-1)).view(5, nfft)
+    want = fftr_ref.fftri_rows(fftr_ref.fftr_rows(host_f32(oracle, r0 * nfft, 5 * nfft), nfft), nfft)
+    assert same_bits(back.cpu().numpy(), want)
+    del out, back
+
+
+@pytest.mark.parametrize("nfft,ntaps", [(2048, 127), (4096, 1025)])
+def test_ovsave_real_past_2_32(gpu, redio, oracle, big, nfft, ntaps):
+    """redio_ovsave_real_enqueue on 2^32 f32 samples and more: the fused kernel, and the generic path through its chunk loop"""
+    import ovsave_real_ref
+    x = f32_view(gpu, big)
+    h = oracle.lpf_corrected(ntaps, 0.08)
+    plan = redio.OverlapSaveReal(h, nfft)
+    hop = nfft - ntaps + 1
+    nout = plan.nout(NV)
+    assert nout == ((NV - nfft) // hop + 1) * hop > 1 << 32 and plan.is_fused == (nfft == 2048)
+    out = plan(x)
+    assert out.numel() == nout
+    for p in marks(nout):
+        o0 = max(0, min(p - 700, nout - 1400))
+        b0, b1 = o0 // hop, (o0 + 1399) // hop
+        want = ovsave_real_ref.overlap_save_real(host_f32(oracle, b0 * hop, (b1 - b0) * hop + nfft), h, nfft)
+        assert same_bits(out[o0:o0 + 1400].cpu().numpy(), want[o0 - b0 * hop: o0 - b0 * hop + 1400]), (nfft, p)
+    del out

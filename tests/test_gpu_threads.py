@@ -53,3 +53,85 @@ def test_concurrent_plans_on_their_own_streams(gpu, redio, oracle):
     for t in threads:
         t.join(300)
     assert not errors, errors
+
+
+def test_concurrent_real_input_and_spectrum_plans(gpu, redio, oracle):
+    """the plan families with plan-owned scratch that grows on first use (redio_pspec_*, its u8 entry, redio_pspec_real_*, the generic
+    redio_fftr_* and redio_ovsave_real_*): eight threads, each with plans of its own on a stream of its own, messages whose length
+    changes from call to call so that scratch regrows while the other threads are inside the library; every result bit for bit the
+    restatement's"""
+    import fftr_ref
+    import ovsave_real_ref
+    import pspec_real_ref
+    import pspec_ref
+    errors = []
+    rows_of = [1, 3, 2, 5, 1, 4, 6, 2, 7, 3, 1, 8]   # per iteration: up and down, the largest last
+
+    def worker(kind, seed):
+        try:
+            s = gpu.cuda.Stream()
+            with gpu.cuda.stream(s):
+                if kind == "pspec_fused":
+                    N, K, step = 1024, 17, 512
+                    w = oracle.lpf_corrected(N, 0.1)
+                    plan = redio.PowerSpectrum(N, K, step, w)
+                elif kind == "pspec_generic":   # K = 17: segment partials and row scratch
+                    N, K, step = 96, 17, 48
+                    w = oracle.lpf_corrected(N, 0.1)
+                    plan = redio.PowerSpectrum(N, K, step, w)
+                elif kind == "pspec_u8":
+                    N, K, step, w = 64, 33, 64, None
+                    plan = redio.PowerSpectrum(N, K, step)
+                elif kind == "pspec_real4":     # un-windowed at step = N from a 4-byte base: the row gather instead of the caller's buffer
+                    N, K, step, w = 1000, 17, 1000, None
+                    plan = redio.PowerSpectrumReal(N, K, step)
+                elif kind == "fftr":
+                    N = 1000
+                    plan = redio.Fftr(N)
+                else:
+                    N, taps = 1000, oracle.synth_f32(seed, 0, 101)
+                    plan = redio.OverlapSaveReal(taps, N)
+                for it, rows in enumerate(rows_of):
+                    if kind == "pspec_fused":
+                        rows = 1 + rows % 3
+                    if kind.startswith("pspec"):
+                        W, H = pspec_ref.shape(N, K, step)
+                        n = W + (rows - 1) * H + 7 * it
+                    if kind in ("pspec_fused", "pspec_generic"):
+                        x = oracle.synth_iq(seed + it, 0, n)
+                        got = plan(gpu.from_numpy(x).cuda()).cpu().numpy()
+                        want = pspec_ref.power_spectrum(x, N, K, step, w)
+                    elif kind == "pspec_u8":
+                        raw = np.random.default_rng(seed + it).integers(0, 256, 2 * n, dtype=np.uint8)
+                        buf = gpu.zeros(raw.size + 16, dtype=gpu.uint8, device="cuda")
+                        buf[2: 2 + raw.size].copy_(gpu.from_numpy(raw))
+                        got = plan.u8(buf[2: 2 + raw.size]).cpu().numpy()
+                        want = pspec_ref.power_spectrum(oracle.data_to_samples(raw), N, K, step)
+                    elif kind == "pspec_real4":
+                        x = oracle.synth_f32(seed + it, 0, n)
+                        buf = gpu.zeros(n + 4, dtype=gpu.float32, device="cuda")
+                        buf[1: 1 + n].copy_(gpu.from_numpy(x))
+                        assert buf[1:].data_ptr() % 8 == 4
+                        got = plan(buf[1: 1 + n]).cpu().numpy()
+                        want = pspec_real_ref.power_spectrum(x, N, K, step)
+                    elif kind == "fftr":
+                        x = oracle.synth_f32(seed + it, 0, 2 * rows * N)
+                        got = plan(gpu.from_numpy(x).cuda()).cpu().numpy().reshape(-1, N // 2 + 1)
+                        want = fftr_ref.fftr_rows(x, N)
+                    else:
+                        x = oracle.synth_f32(seed + it, 0, N + (rows - 1) * plan.hop + 13 * it)
+                        got = plan(gpu.from_numpy(x).cuda()).cpu().numpy()
+                        want = ovsave_real_ref.overlap_save_real(x, taps, N)
+                    if not (got.shape == want.shape and np.array_equal(np.ascontiguousarray(got).view(np.uint32), np.ascontiguousarray(want).view(np.uint32))):
+                        errors.append((kind, it))
+        except Exception as e:  # noqa: BLE001
+            errors.append((kind, repr(e)))
+
+    kinds = ["pspec_fused", "pspec_generic", "pspec_u8", "pspec_real4", "fftr", "ovsave_real", "pspec_generic", "pspec_u8"]
+    threads = [threading.Thread(target=worker, args=(k, 1000 * (i + 1))) for i, k in enumerate(kinds)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(300)
+    assert not any(t.is_alive() for t in threads), "a thread did not finish"
+    assert not errors, errors

@@ -1,0 +1,170 @@
+"""The generator of tests/fuzz_spectra.py, and the four restatements it compares the device with, checked without a GPU.
+
+Generator coverage: the dry mode (`fuzz_spectra.py --draw 2000 SEED`, the seed of tests/test_gpu_fuzz_spectra.py) is run as the
+command it is, in a process that must import neither torch nor the product library, and every route combination the driver of
+pspec_api.hip, the stream layer and the real-input plans distinguish has to turn up in at least 1 % of the cases.
+
+Restatements against float64: the counterpart of test_oracle_random.py for fftr_ref, ovsave_real_ref, pspec_ref and pspec_real_ref, on
+the generator's own first 300 shapes, unspiced.  The bounds are the project's: 2e-6 for transforms and spectra (SURVEY.md 8c,
+test_pspec_cpu.py, test_fftr_cpu.py) and 2e-6 sum|taps| sqrt(log2 N) + 1e-7 for overlap-save (test_ovsave_real_cpu.py), each times
+max(1, p / 8) with p the largest prime factor of the complex transform's size, the rule of test_oracle_random.py.
+Worst distances over those 300 cases, as values and as fractions of their bounds (measure: max|got - exact| / max(exact) for the
+spectra, relative L2 for the transforms, the largest absolute error for overlap-save):
+    pspec        3.6e-07, 0.18 of its bound        pspec_real   3.2e-07, 0.16
+    pspec_u8     4.2e-07, 0.21                     fftr         1.5e-07, 0.07
+    ovsave_real  8.5e-08, 0.08                     streams      3.0e-07, 0.15"""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import fftr_ref
+import fuzz_spectra as fz
+import ovsave_real_ref
+import pspec_real_ref
+import pspec_ref
+
+SEED = 11          # tests/test_gpu_fuzz_spectra.py runs the tool with this seed
+DRAWN, LEAST = 2000, 20
+TOOL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fuzz_spectra.py")
+# the dry mode as a command, in an interpreter that afterwards reports whether torch or the product library were imported
+DRY = ("import runpy, sys\n"
+       "sys.argv = [sys.argv[1]] + sys.argv[2:]\n"
+       "try:\n    runpy.run_path(sys.argv[0], run_name='__main__')\nexcept SystemExit as e:\n    assert not e.code, e.code\n"
+       "sys.exit(3 if 'torch' in sys.modules or 'libredio_amd' in sys.modules else 0)\n")
+
+
+@pytest.fixture(scope="module")
+def drawn():
+    out = subprocess.run([sys.executable, "-c", DRY, TOOL, "--draw", str(DRAWN), str(SEED)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, (out.returncode, out.stderr[-2000:])
+    cases = [json.loads(line) for line in out.stdout.splitlines()]
+    assert len(cases) == DRAWN
+    return cases
+
+
+def plan_key(c):
+    return json.dumps({k: c[k] for k in ("family", "N", "inverse", "ntaps", "taps", "tseed", "K", "step", "window", "wseed") if k in c}, sort_keys=True)
+
+
+def test_the_dry_mode_draws_what_a_run_draws(drawn):
+    """the same cases from the generator in this process: an opening round of every family first, then families at random"""
+    gen = fz.Gen(SEED)
+    again = [gen.draw(f) for _, f in zip(range(DRAWN), fz.sequence(gen, None))]
+    assert json.loads(json.dumps(again)) == drawn
+    opening = [c["family"] for c in drawn[: fz.OPENING * len(fz.FAMILIES)]]
+    assert opening == [f for f in fz.FAMILIES for _ in range(fz.OPENING)]
+
+
+def test_every_route_combination_is_drawn_often_enough(drawn):
+    by = {f: [c for c in drawn if c["family"] == f] for f in fz.FAMILIES}
+    r = lambda c: c["route"]
+    cond = {}
+    for f in fz.FAMILIES:
+        cond[f"{f} present"] = by[f]
+    for f in ("fftr", "ovsave_real", "pspec", "pspec_u8", "pspec_real"):
+        cond[f"{f} fused"] = [c for c in by[f] if r(c)["fused"]]
+        cond[f"{f} generic"] = [c for c in by[f] if not r(c)["fused"]]
+    for f in ("pspec", "pspec_u8", "pspec_real"):
+        cond[f"{f} packs"] = [c for c in by[f] if r(c)["packs"]]
+        cond[f"{f} does not pack"] = [c for c in by[f] if not r(c)["packs"]]
+        cond[f"{f} K <= 16"] = [c for c in by[f] if c["K"] <= 16]
+        for mode in (1, 2):
+            cond[f"{f} K > 16 in mode {mode}"] = [c for c in by[f] if c["K"] > 16 and r(c)["segments2"] and c["mode"] == mode]
+        cond[f"{f} step > N"] = [c for c in by[f] if c["step"] > c["N"] and r(c)["H>W"]]
+        cond[f"{f} stream with H > W"] = [c for c in by["streams"] if c["kind"] == f and r(c)["H>W"]]
+    cond["pspec_real odd step"] = [c for c in by["pspec_real"] if r(c)["odd_step"]]
+    cond["pspec_real 4-byte base"] = [c for c in by["pspec_real"] if r(c)["base"] == 4]
+    cond["pspec_u8 at 2048 or 4096"] = [c for c in by["pspec_u8"] if r(c)["fft_u8"] in (2048, 4096)]
+    cond["pspec_u8 base not a multiple of 8"] = [c for c in by["pspec_u8"] if r(c)["base"] % 8]
+    cond["ovsave_real even ntaps"] = [c for c in by["ovsave_real"] if r(c)["ntaps_even"]]
+    cond["fftr strided forward with overlap"] = [c for c in by["fftr"] if r(c)["strided"] and not c["inverse"] and r(c)["overlap"] and c["in_stride"] < c["N"]]
+    cond["refusal expected"] = [c for c in drawn if r(c).get("refusal")]
+    seen, again = {}, []
+    for c in drawn:
+        if c["family"] != "streams":
+            k = plan_key(c)
+            if any(rows != c["rows"] for rows in seen.get(k, ())):
+                again.append(c)
+            seen.setdefault(k, set()).add(c["rows"])
+    cond["a plan shape again with another row count"] = again
+    # the streams' cuts: a zero-length piece, one shorter than a window, one longer than two, odd lengths, an end inside a skipped gap
+    pst = [c for c in by["streams"] if c["kind"] != "ovsave_real"]
+    for name in ("zero_piece", "short_piece", "long_piece", "odd_piece", "ends_in_gap", "reset"):
+        cond[f"streams {name}"] = [c for c in by["streams"] if r(c)[name]]
+    counts = {k: len(v) for k, v in cond.items()}
+    print(counts)
+    short = {k: n for k, n in counts.items() if n < LEAST}
+    assert not short, short
+    assert 4 * len([c for c in pst if r(c)["H>W"]]) >= len(pst)       # a quarter of the power-spectrum streams skip
+    assert 2 * len(cond["streams reset"]) >= 0.8 * len(by["streams"])  # about half reset and run again
+    sizes = {r(c)["staging"] for c in drawn if r(c).get("staging")}
+    assert sizes >= {65536, 8194, 16388, 131072}, sizes
+    # every case respects the bound that keeps the restatement fast, the large sizes' one or two transforms excepted
+    for c in drawn:
+        real = c["family"] in ("pspec_real", "fftr", "ovsave_real") or c.get("kind") in ("pspec_real", "ovsave_real")
+        ntr = {"fftr": c["rows"], "ovsave_real": 2 * c["rows"]}.get(c["family"], c["rows"] * c.get("K", 1))
+        if c["family"] == "streams":
+            continue
+        if r(c).get("staging"):
+            assert ntr <= 2, c
+        else:
+            assert ntr * (c["N"] // 2 if real else c["N"]) <= fz.POINTS, c
+
+
+def exact_rows(x, N, K, step, window, real):
+    """float64: the sum over K transforms of |fft|^2 (|rfft|^2) of the windowed rows"""
+    nt = pspec_ref.nrows(len(x), N, K, step) * K
+    rows = np.stack([x[t * step: t * step + N] for t in range(nt)]).astype(np.float64 if real else np.complex128)
+    if window is not None:
+        rows = rows * window.astype(np.float64)
+    P = np.abs(np.fft.rfft(rows, axis=1) if real else np.fft.fft(rows, axis=1)) ** 2
+    return P.reshape(-1, K, P.shape[1]).sum(axis=1)
+
+
+def test_restatements_against_float64_on_the_generators_shapes(oracle):
+    gen = fz.Gen(SEED)
+    worst = {}
+
+    def note(fam, err, tol, c):
+        w = worst.setdefault(fam, [0.0, 0.0])
+        if err / tol > w[0]:
+            w[:] = [err / tol, err]
+        assert err <= tol, (fam, err, tol, c)
+
+    for _, fam in zip(range(300), fz.sequence(gen, None)):
+        c = gen.draw(fam)
+        kind = c.get("kind", fam)
+        x = fz.case_input(oracle, c, spiced=False)
+        N = c["N"]
+        rough = max(1.0, fz.largest_prime_factor(max(N if kind in ("pspec", "pspec_u8") else N // 2, 1)) / 8.0)
+        if kind == "fftr":
+            nin = N // 2 + 1 if c["inverse"] else N
+            rows = np.stack([x[b * c["in_stride"]: b * c["in_stride"] + nin] for b in range(c["rows"])])
+            if c["inverse"]:
+                got, want = fftr_ref.fftri_rows(rows, N), np.fft.irfft(rows.astype(np.complex128), n=N, axis=1) * N
+            else:
+                got, want = fftr_ref.fftr_rows(rows, N), np.fft.rfft(rows.astype(np.float64), axis=1)
+            note(fam, np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-30), 2e-6 * rough, c)
+        elif kind == "ovsave_real":
+            taps = fz.taps_of(oracle, c)
+            got = ovsave_real_ref.overlap_save_real(x, taps, N)
+            if len(got):
+                want = np.correlate(x.astype(np.float64), taps.astype(np.float64), "valid")[: len(got)]
+                tol = (2e-6 * float(np.abs(taps).sum()) * np.sqrt(np.log2(N)) + 1e-7) * rough
+                note(fam, float(np.abs(got - want).max()), tol, c)
+        else:
+            real = kind == "pspec_real"
+            xs = fz.samples_of(oracle, x) if kind == "pspec_u8" else x
+            w = fz.window_of(oracle, c)
+            got = (pspec_real_ref if real else pspec_ref).power_spectrum(xs, N, c["K"], c["step"], w)
+            if len(got):
+                want = exact_rows(xs, N, c["K"], c["step"], w, real)
+                assert got.shape == want.shape
+                note(fam, float(np.abs(got - want).max() / want.max()), 2e-6 * rough, c)
+    for fam, (frac, err) in sorted(worst.items()):
+        print(f"{fam:12s} worst distance {err:.2e}, {frac:.2f} of its bound")
+    assert set(worst) == set(fz.FAMILIES)
