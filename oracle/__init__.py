@@ -356,8 +356,12 @@ class Rle:
 
 
 def dle(runs, s_rate):
-    """kpn::dle, kpn.rs:32-38: (x, ct) -> (x, ct as f32 / s_rate as f32)."""
-    return [(x, np.float32(np.float32(ct) / np.float32(s_rate))) for x, ct in runs]
+    """kpn::dle, kpn.rs:32-38: (x, ct) -> (x, ct as f32 / s_rate as f32).  Both are u64 -> f32 casts with ONE rounding: the cast of a
+    uint64 array, not np.float32(int), which goes through double and rounds twice above 2^53."""
+    def as_f32(v):
+        return np.array(v, np.uint64).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return [(x, np.float32(as_f32(ct) / as_f32(s_rate))) for x, ct in runs]
 
 
 def rld(runs):
