@@ -1073,5 +1073,62 @@ inline void power_spectrum_real(Receiver<View<float>> u, Sender<View<float>> v, 
 // the same as a STREAM: messages of any length, odd ones included, give the rows of one call on the whole stream
 inline void power_spectrum_real_stream(Receiver<View<float>> u, Sender<View<float>> v, int nfft, size_t integrate, size_t step, std::vector<float> window = {}) { detail::pspec_stream_block<detail::PspecReal>(u, v, nfft, integrate, step, window); }
 
+namespace detail {
+// the polyphase spectrometer's four blocks: cf32 or u8 I/Q messages in (per_sample elements make a sample), rows of nchan f32 out
+struct PfbSpecCf32 {
+    using In = std::complex<float>;
+    static constexpr size_t per_sample = 1;
+    static constexpr auto enqueue = redio_pfb_pspec_enqueue;
+    static constexpr auto stream_create = redio_pfb_pspec_stream_create;
+};
+struct PfbSpecU8 {
+    using In = uint8_t;
+    static constexpr size_t per_sample = 2;
+    static constexpr auto enqueue = redio_pfb_pspec_enqueue_u8;
+    static constexpr auto stream_create = redio_pfb_pspec_stream_create_u8;
+};
+template <typename T>
+void pfb_pspec_block(Receiver<View<typename T::In>> &u, Sender<View<float>> &v, const std::vector<float> &proto, int nchan, int taps_per_branch, size_t integrate, unsigned flags)
+{
+    using In = typename T::In;
+    if (proto.size() != (size_t)nchan * (size_t)taps_per_branch) check(REDIO_ERR_ARG);
+    redio_pfb_pspec *h = nullptr;
+    check(redio_pfb_pspec_create(&h, proto.data(), nchan, taps_per_branch, integrate, flags));
+    struct G { redio_pfb_pspec *h; ~G() { redio_pfb_pspec_destroy(h); } } g{h};
+    run_block<In, float>(u, v, [&](const View<In> &d) { return redio_pfb_pspec_nrows(h, d.len / T::per_sample) * (size_t)nchan; },
+                         [&](const View<In> &d, const View<float> &o, void *st) { return T::enqueue(h, d.data(), d.len, o.data(), st); });
+}
+template <typename T>
+void pfb_pspec_stream_block(Receiver<View<typename T::In>> &u, Sender<View<float>> &v, const std::vector<float> &proto, int nchan, int taps_per_branch, size_t integrate,
+                            unsigned flags)
+{
+    using In = typename T::In;
+    if (proto.size() != (size_t)nchan * (size_t)taps_per_branch) check(REDIO_ERR_ARG);
+    redio_pfb_pspec *h = nullptr;
+    check(redio_pfb_pspec_create(&h, proto.data(), nchan, taps_per_branch, integrate, flags));
+    redio_pfb_pspec_stream *s = nullptr;
+    const int rc = T::stream_create(&s, h);
+    struct G { redio_pfb_pspec *h; redio_pfb_pspec_stream *s; ~G() { redio_pfb_pspec_stream_destroy(s); redio_pfb_pspec_destroy(h); } } g{h, s};
+    check(rc);
+    run_stream_block_of<In, float>(u, v, [&](size_t len) { return redio_pfb_pspec_stream_nout(s, len / T::per_sample); },
+                                   [&](const View<In> &d, float *o, size_t *got, void *st) {
+                                       if (d.len % T::per_sample) return (int)REDIO_ERR_ARG;
+                                       return redio_pfb_pspec_stream_enqueue(s, d.data(), d.len / T::per_sample, o, got, st);
+                                   });
+}
+} // namespace detail
+
+// the polyphase spectrometer (redio_pfb_pspec_*: |row[c]|^2 of the nchan-channel polyphase channelizer's rows, summed over `integrate`
+// rows; proto: nchan * taps_per_branch prototype taps; flags: REDIO_FIR_FUSED or 0): cf32 messages in, rows of nchan f32 out,
+// per-message semantics -- the rows that fit in each message, a trailing partial row dropped
+inline void polyphase_spectrum(Receiver<View<std::complex<float>>> u, Sender<View<float>> v, std::vector<float> proto, int nchan, int taps_per_branch, size_t integrate, unsigned flags = REDIO_FIR_FUSED) { detail::pfb_pspec_block<detail::PfbSpecCf32>(u, v, proto, nchan, taps_per_branch, integrate, flags); }
+// the same as a STREAM: messages of any length give the rows of one call on the whole stream; a message that completes no row sends nothing
+inline void polyphase_spectrum_stream(Receiver<View<std::complex<float>>> u, Sender<View<float>> v, std::vector<float> proto, int nchan, int taps_per_branch, size_t integrate, unsigned flags = REDIO_FIR_FUSED) { detail::pfb_pspec_stream_block<detail::PfbSpecCf32>(u, v, proto, nchan, taps_per_branch, integrate, flags); }
+// the receiver's messages straight into the spectrometer: u8 I/Q bytes (rtlsdr.rs:127-162), without the cf32 intermediate
+// (redio_pfb_pspec_enqueue_u8: ONE kernel at 64 channels x 4 / 8 / 16 taps per branch); a message holds whole samples
+inline void polyphase_spectrum_u8(Receiver<View<uint8_t>> u, Sender<View<float>> v, std::vector<float> proto, int nchan, int taps_per_branch, size_t integrate, unsigned flags = REDIO_FIR_FUSED) { detail::pfb_pspec_block<detail::PfbSpecU8>(u, v, proto, nchan, taps_per_branch, integrate, flags); }
+// the same as a STREAM (redio_pfb_pspec_stream_create_u8: the history is carried as bytes)
+inline void polyphase_spectrum_stream_u8(Receiver<View<uint8_t>> u, Sender<View<float>> v, std::vector<float> proto, int nchan, int taps_per_branch, size_t integrate, unsigned flags = REDIO_FIR_FUSED) { detail::pfb_pspec_stream_block<detail::PfbSpecU8>(u, v, proto, nchan, taps_per_branch, integrate, flags); }
+
 } // namespace dev
 } // namespace kpn

@@ -426,6 +426,41 @@ int redio_pfb_reserve(redio_pfb *h, size_t n_in, int ngroups);
  * shape without a fused 64-channel kernel, so that an output that is not 16-byte aligned never allocates (e.g. inside a capture) */
 int redio_pfb_reserve_two_pass(redio_pfb *h, size_t n_in, int ngroups);
 
+/* ---- the polyphase spectrometer: |row[c]|^2 of the channelizer's rows summed over K rows (a NEW composition) ----
+ * What a waterfall, a detector or a radiometer puts behind a channelizer.  M = nchan, P = taps_per_branch, K = integrate >= 1:
+ *     channelizer row t is exactly redio_pfb_enqueue's row t (ngroups = 1): the same branch fold, with or without REDIO_FIR_FUSED,
+ *     and the same nchan-point kissfft transform;
+ *     p_t[c] = row_t[c].re * row_t[c].re + row_t[c].im * row_t[c].im, every multiply and add rounded on its own;
+ *     output row r integrates channelizer rows [r K, r K + K) in the order of the power spectrum above: segments of
+ *     REDIO_PSPEC_SEG rows counted from r K, a left fold in ascending t inside each, a left fold over them in ascending s.
+ * The order does not depend on launch geometry.  With T = n_in / M a call gives nrows = (T - P + 1) / K rows (0 when T < P + K - 1;
+ * a trailing partial row is dropped) of M f32 in natural channel order, packed.  In samples: window W = (K - 1 + P) M, hop H = K M.
+ * Bit for bit that is redio_pfb_enqueue followed by redio_pspec_enqueue_spectra of a (nfft = M, integrate = K) plan, for every shape
+ * redio_pfb_create accepts -- that composition is the definition -- without the channel rows ever reaching memory on the fused
+ * shapes.  No dB, no fftshift, no normalisation: those are the caller's.
+ * create: NULL h, integrate == 0 -> REDIO_ERR_ARG; a shape redio_pfb_create refuses -> its error.  flags: as redio_pfb_create.
+ * nchan = 64 with taps_per_branch in {4, 8, 16} is ONE kernel (redio_pfb_pspec_is_fused() == 1), from cf32 and from bytes: 8 (or 2)
+ *   bytes read and 4 / K written per sample, no scratch beyond the segment partials.  Every other shape runs the plan's own
+ *   redio_pfb into plan-owned row scratch in chunks of whole segments with at most 64 MiB of rows, and an accumulate pass per chunk.
+ * reserve(h, n_in) / reserve_u8(h, nbytes) size all of the scratch, the inner channelizer's included, for calls of up to that many
+ *   samples / bytes, after which an enqueue neither allocates nor synchronises; un-reserved it grows on first use
+ *   (REDIO_ERR_NOT_RESERVED while the stream is being captured).
+ * enqueue / enqueue_u8 (interleaved u8 I/Q bytes, rtlsdr.rs:159-162: bit for bit redio_data_to_samples + enqueue): launches only, on
+ *   the caller's stream; every argument is checked before anything is launched.  NULL or overlapping buffers, d_in not 8-byte,
+ *   d_bytes not 2-byte or d_out not 4-byte aligned, odd nbytes -> REDIO_ERR_ARG; fewer than W samples -> REDIO_OK, no launch.
+ * set_split: 0 auto, 1 a wavefront owns whole output rows, 2 a wavefront owns a run of whole segments and a fold pass finishes: the
+ *   bits are the same in every mode. */
+typedef struct redio_pfb_pspec redio_pfb_pspec;
+int redio_pfb_pspec_create(redio_pfb_pspec **h, const float *proto_taps_host, int nchan, int taps_per_branch, size_t integrate, unsigned flags);
+int redio_pfb_pspec_destroy(redio_pfb_pspec *h);
+size_t redio_pfb_pspec_nrows(const redio_pfb_pspec *h, size_t n_in);
+int redio_pfb_pspec_is_fused(const redio_pfb_pspec *h);
+int redio_pfb_pspec_reserve(redio_pfb_pspec *h, size_t n_in);
+int redio_pfb_pspec_enqueue(redio_pfb_pspec *h, const void *d_in_c32, size_t n_in, void *d_out_f32, void *stream);
+int redio_pfb_pspec_enqueue_u8(redio_pfb_pspec *h, const void *d_bytes, size_t nbytes, void *d_out_f32, void *stream);
+int redio_pfb_pspec_reserve_u8(redio_pfb_pspec *h, size_t nbytes);
+int redio_pfb_pspec_set_split(redio_pfb_pspec *h, int mode);
+
 /* ---- the channelizer's one exchange step over RCCL / xGMI (the only collective on the path) ----
  * Time-sharded channelizer: every rank runs redio_pfb_enqueue(..., ngroups = G) on its own slice of the stream and
  * holds d_grouped = [G groups][its rows][chans_per_rank cf32]; the exchange sends group q to rank q
@@ -541,6 +576,19 @@ int redio_pspec_real_stream_reset(redio_pspec_real_stream *h);
 size_t redio_pspec_real_stream_nout(const redio_pspec_real_stream *h, size_t n_new);
 size_t redio_pspec_real_stream_pending(const redio_pspec_real_stream *h);
 int redio_pspec_real_stream_enqueue(redio_pspec_real_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
+/* the polyphase spectrometer as a stream: row r from the W = (integrate - 1 + taps_per_branch) nchan samples that start at
+ * r * integrate * nchan; *nout counts f32 words (whole rows of nchan).  create_u8: d_new points to interleaved u8 I/Q bytes (2-byte
+ * aligned: an odd address is REDIO_ERR_ARG before anything is launched), n_new still counts SAMPLES, the history is carried as bytes.
+ * Create reserves for the seam windows (redio_pfb_pspec_reserve / _reserve_u8 for the largest message + W keeps longer bodies
+ * allocation-free on the shapes that are not fused). */
+typedef struct redio_pfb_pspec_stream redio_pfb_pspec_stream;
+int redio_pfb_pspec_stream_create(redio_pfb_pspec_stream **h, redio_pfb_pspec *plan);
+int redio_pfb_pspec_stream_create_u8(redio_pfb_pspec_stream **h, redio_pfb_pspec *plan);
+int redio_pfb_pspec_stream_destroy(redio_pfb_pspec_stream *h);
+int redio_pfb_pspec_stream_reset(redio_pfb_pspec_stream *h);
+size_t redio_pfb_pspec_stream_nout(const redio_pfb_pspec_stream *h, size_t n_new);
+size_t redio_pfb_pspec_stream_pending(const redio_pfb_pspec_stream *h);
+int redio_pfb_pspec_stream_enqueue(redio_pfb_pspec_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
 
 /* ---- A6: samplerate::resample's native side, src/samplerate/src/samplerate.rs:59-87 ----
  * nchan independent mono streams that share ratio and block lengths (the reference creates one

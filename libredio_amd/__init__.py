@@ -123,14 +123,14 @@ def lib():
     _sig(L.redio_fft_reserve, i, vp, sz)
     _sig(L.redio_pfb_reserve, i, vp, sz, i)
     _sig(L.redio_pfb_reserve_two_pass, i, vp, sz, i)
-    for n in ("fir", "chain", "pfb", "ovsave", "ovsave_real", "pspec", "pspec_real"):
+    for n in ("fir", "chain", "pfb", "ovsave", "ovsave_real", "pspec", "pspec_real", "pfb_pspec"):
         _sig(getattr(L, f"redio_{n}_stream_create"), i, C.POINTER(vp), vp)
         _sig(getattr(L, f"redio_{n}_stream_destroy"), i, vp)
         _sig(getattr(L, f"redio_{n}_stream_reset"), i, vp)
         _sig(getattr(L, f"redio_{n}_stream_nout"), sz, vp, sz)
         _sig(getattr(L, f"redio_{n}_stream_pending"), sz, vp)
         _sig(getattr(L, f"redio_{n}_stream_enqueue"), i, vp, vp, sz, vp, C.POINTER(sz), vp)
-    for n in ("chain", "pfb", "pspec"):
+    for n in ("chain", "pfb", "pspec", "pfb_pspec"):
         _sig(getattr(L, f"redio_{n}_stream_create_u8"), i, C.POINTER(vp), vp)
     _sig(L.redio_chain_enqueue, i, vp, vp, sz, vp, vp)
     _sig(L.redio_chain_enqueue_u8, i, vp, vp, sz, vp, vp)
@@ -184,6 +184,15 @@ def lib():
     _sig(L.redio_pspec_real_enqueue, i, vp, vp, sz, vp, vp)
     _sig(L.redio_pspec_real_enqueue_spectra, i, vp, vp, sz, vp, vp)
     _sig(L.redio_pspec_real_set_split, i, vp, i)
+    _sig(L.redio_pfb_pspec_create, i, C.POINTER(vp), pf, i, i, sz, u)
+    _sig(L.redio_pfb_pspec_destroy, i, vp)
+    _sig(L.redio_pfb_pspec_nrows, sz, vp, sz)
+    _sig(L.redio_pfb_pspec_is_fused, i, vp)
+    _sig(L.redio_pfb_pspec_reserve, i, vp, sz)
+    _sig(L.redio_pfb_pspec_reserve_u8, i, vp, sz)
+    _sig(L.redio_pfb_pspec_enqueue, i, vp, vp, sz, vp, vp)
+    _sig(L.redio_pfb_pspec_enqueue_u8, i, vp, vp, sz, vp, vp)
+    _sig(L.redio_pfb_pspec_set_split, i, vp, i)
     psz = C.POINTER(sz)
     _sig(L.redio_data_to_samples, i, vp, sz, vp, vp)
     _sig(L.redio_norm_c32, i, vp, sz, vp, vp)
@@ -278,4 +287,4 @@ def check(code, what="redio"):
 
 
 from . import bitfount, dsputils, kissfft, kpn_dev, plans, samplerate  # noqa: E402,F401
-from .plans import Chain, Channelizer, Comm, Fft, Fftr, Fir, Graph, OverlapSave, OverlapSaveReal, PowerSpectrum, PowerSpectrumReal, Src, Stream, channelizer_all_to_all, current_stream, planes_to_rows, rows_to_planes, synth_f32, synth_iq  # noqa: E402,F401
+from .plans import Chain, Channelizer, Comm, Fft, Fftr, Fir, Graph, OverlapSave, OverlapSaveReal, PolyphaseSpectrum, PowerSpectrum, PowerSpectrumReal, Src, Stream, channelizer_all_to_all, current_stream, planes_to_rows, rows_to_planes, synth_f32, synth_iq  # noqa: E402,F401

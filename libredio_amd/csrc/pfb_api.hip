@@ -179,6 +179,11 @@ void redio_pfb_shape(const redio_pfb *h, int *nchan, int *taps_per_branch, int *
 {
     *nchan = h->nchan; *taps_per_branch = h->taps_per_branch; *device = h->device;
 }
+// what the polyphase spectrometer's fused kernel (pfb_pspec_kernels.hip) takes from the channelizer it owns
+void redio_pfb_tables(const redio_pfb *h, const float **d_taps, const float2 **d_tw, unsigned *flags, int *fused_kernel)
+{
+    *d_taps = h->d_h; *d_tw = h->d_tw; *flags = h->flags; *fused_kernel = h->fused_kernel ? 1 : 0;
+}
 
 extern "C" int redio_pfb_enqueue(redio_pfb *h, const void *d_in, size_t n_in, void *d_out, int ngroups, void *stream)
 {

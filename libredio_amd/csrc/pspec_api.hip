@@ -1,11 +1,14 @@
 // pspec_api.hip -- C ABI of the integrated power spectrum (include/redio.h, redio_pspec_* and redio_pspec_real_*): |X[k]|^2 summed over
 // K consecutive transforms of N = nfft samples that start every `step` samples, optionally windowed (the periodogram; with a window
 // and step < N, Welch's method).  The integration is new: the reference has no such block.  Summation order (pspec_core.h): segments
-// of REDIO_PSPEC_SEG transforms, a left fold inside each, a left fold over them.  Two plans, one driver (enqueue<Entry> below):
+// of REDIO_PSPEC_SEG transforms, a left fold inside each, a left fold over them.  Three plans, one driver (enqueue<Entry> below):
 //   redio_pspec        X = the kissfft::fft block (src/kissfft/src/kissfft.rs:18-31) of N cf32 samples, B = N bins per row; fused at
 //                      N = 1024 (pspec_kernels.hip).  Algorithmic bytes per input sample: 8 N / step read + 4 / K written.
 //   redio_pspec_real   X = kiss_fftr (tools/kiss_fftr.c, the bits of redio_fftr_*) of N REAL samples, B = N / 2 + 1 bins per row; fused
 //                      at N = 2048 (pspec_real_kernels.hip).  Per real sample: 4 N / step read + 4 B / (K step) written.
+//   redio_pfb_pspec    X = row t of the polyphase channelizer (redio_pfb_*, ngroups = 1) of M = nchan channels, B = M; a transform starts
+//                      every M samples and reads P M of them; fused at 64 channels x 4 / 8 / 16 taps per branch (pfb_pspec_kernels.hip).
+//                      Per input sample: 8 (cf32) or 2 (u8 I/Q) bytes read + 4 / K written.  Contract: DESIGN.md 5.6b.
 //   fused N      one kernel: the spectra stay in the wave's registers; one more fold pass when a wave takes a segment instead of a
 //                whole row
 //   other N      [row gather with window ->] the plan's own transform -> accumulate -> fold, through plan-owned scratch, in chunks of
@@ -17,6 +20,7 @@
 #include "../../include/redio.h"
 #include "redio_internal.h"
 #include "pspec_real_core.h"
+#include "pfb_pspec_core.h"
 #include <new>
 #include <type_traits>
 
@@ -27,7 +31,7 @@ static_assert(PSPEC_SEG == REDIO_PSPEC_SEG, "the header's constant is the kernel
 namespace {
 // what both plans hold, and everything below that does not depend on the sample type works on
 struct Pspec {
-    int device, nfft;
+    int device, nfft;      // nfft: the samples one transform reads (redio_pfb_pspec: nchan * taps_per_branch)
     size_t B;              // bins per row: N, or N / 2 + 1 for the real plan
     size_t K, step, S;     // S = ceil(K / 16) segments per row
     bool fused;            // the plan's one-kernel size
@@ -200,6 +204,15 @@ struct redio_pspec_real {
     size_t fftr_cap;       // rows per call the plan's redio_fftr has been reserved for
 };
 
+struct redio_pfb_pspec {
+    Pspec c;               // nfft = M P samples per transform, B = M bins, step = M
+    int M, P;
+    redio_pfb *pfb;        // the channelizer: taps, table, and on the generic path the rows themselves
+    void *d_rows;          // generic path: rows_cap channelizer rows of M cf32
+    size_t rows_cap;
+    size_t pfb_cap, pfb_cap_u8; // rows per pass the channelizer's own scratch has been reserved for, from cf32 and from bytes
+};
+
 namespace {
 // cf32 samples in (redio_pspec_enqueue) and u8 I/Q byte pairs in (redio_pspec_enqueue_u8: one 16-bit word per sample, a sample-aligned
 // pointer as the cf32 entry asks for 8).  U8 gathers rows and transforms them in place on every plan that has no launch_fft_u8.
@@ -281,6 +294,41 @@ struct Real {
         float *rows = (float *)h->d_rows;
         REDIO_TRY(launch_pspec_real_rows(x + g0 * c.step, c.d_win, rows, (long)ntr, N, (long)c.step, (hipStream_t)stream));
         return redio_fftr_enqueue(h->fftr, rows, out, ntr, stream);
+    }
+};
+
+// the polyphase spectrometer: cf32 samples in (redio_pfb_pspec_enqueue) or u8 I/Q byte pairs (redio_pfb_pspec_enqueue_u8).  A
+// "transform" is one channelizer row; a pass of ntr rows reads (ntr + P - 1) M samples.
+template <bool U8>
+struct Polyphase {
+    redio_pfb_pspec *h;
+    static constexpr bool transforms = true;
+    static constexpr uintptr_t align = U8 ? 1 : 7;
+    using Sample = std::conditional_t<U8, uint16_t, float2>;
+    size_t in_bytes(size_t n_in) const { return n_in * sizeof(Sample); }
+    size_t pass_in(size_t pass) const { return (pass + (size_t)h->P - 1) * (size_t)h->M; }
+    size_t &cap() const { return U8 ? h->pfb_cap_u8 : h->pfb_cap; }
+    bool short_rows(size_t pass) const { return pass * (size_t)h->M > h->rows_cap || pass > cap(); }
+    int reserve(size_t pass) const
+    {
+        if (pass > cap()) {
+            if (int rc = U8 ? redio_pfb_reserve_u8(h->pfb, 2 * pass_in(pass), 1) : redio_pfb_reserve(h->pfb, pass_in(pass), 1)) return rc;
+            cap() = pass;
+        }
+        return scratch_grow(&h->d_rows, &h->rows_cap, pass * (size_t)h->M, sizeof(float2));
+    }
+    hipError_t launch_fused(const void *d_in, float *dst, long nunits, bool split, hipStream_t st) const
+    {
+        const float *taps; const float2 *tw; unsigned flags; int fk;
+        redio_pfb_tables(h->pfb, &taps, &tw, &flags, &fk);
+        return launch_pfbspec64(d_in, U8, taps, tw, dst, nunits, (long)h->c.K, h->P, split, (flags & REDIO_FIR_FUSED) != 0, st);
+    }
+    int spectra(const void *d_in, size_t g0, size_t ntr, void *stream, const float2 *&spec) const
+    {
+        const Sample *x = (const Sample *)d_in + g0 * (size_t)h->M;
+        spec = (const float2 *)h->d_rows;
+        if constexpr (U8) return redio_pfb_enqueue_u8(h->pfb, x, 2 * pass_in(ntr), h->d_rows, 1, stream);
+        else return redio_pfb_enqueue(h->pfb, x, pass_in(ntr), h->d_rows, 1, stream);
     }
 };
 } // namespace
@@ -390,4 +438,57 @@ extern "C" int redio_pspec_enqueue_spectra(redio_pspec *h, const void *d_spectra
 extern "C" int redio_pspec_real_enqueue_spectra(redio_pspec_real *h, const void *d_spectra, size_t nbatch, void *d_out, void *stream)
 {
     return h ? enqueue_spectra(h->c, d_spectra, nbatch, d_out, stream) : REDIO_ERR_ARG;
+}
+
+// ---- the polyphase spectrometer (include/redio.h, redio_pfb_pspec_*) ----
+extern "C" int redio_pfb_pspec_create(redio_pfb_pspec **h, const float *proto, int nchan, int taps_per_branch, size_t integrate, unsigned flags)
+{
+    if (!h) return REDIO_ERR_ARG;
+    *h = nullptr;
+    if (integrate == 0) return REDIO_ERR_ARG;
+    redio_pfb *pfb = nullptr;
+    if (int rc = redio_pfb_create(&pfb, proto, nchan, taps_per_branch, flags)) return rc; // its own refusals
+    redio_pfb_pspec *p = new (std::nothrow) redio_pfb_pspec();
+    if (!p) { redio_pfb_destroy(pfb); return REDIO_ERR_NOMEM; }
+    p->pfb = pfb; p->M = nchan; p->P = taps_per_branch;
+    const float *taps; const float2 *tw; unsigned fl; int fused;
+    redio_pfb_tables(pfb, &taps, &tw, &fl, &fused);
+    // auto mode: a wave per run of whole rows once those runs give PFBSPEC_SPLIT_WAVES waves
+    const long split_rows = PFBSPEC_SPLIT_WAVES * pfbspec_units_per_wave(1, (long)integrate, false);
+    if (int rc = pspec_init(p->c, nchan * taps_per_branch, (size_t)nchan, integrate, (size_t)nchan, fused != 0, split_rows, nullptr)) {
+        redio_pfb_pspec_destroy(p);
+        return rc;
+    }
+    *h = p;
+    return REDIO_OK;
+}
+extern "C" int redio_pfb_pspec_destroy(redio_pfb_pspec *h)
+{
+    if (!h) return REDIO_OK;
+    redio_pfb_destroy(h->pfb);
+    pspec_free(h->c);
+    redio_free(h->d_rows);
+    delete h;
+    return REDIO_OK;
+}
+void redio_pfb_pspec_shape(const redio_pfb_pspec *h, int *window, size_t *K, size_t *step, int *device) { *window = h->c.nfft; *K = h->c.K; *step = h->c.step; *device = h->c.device; }
+extern "C" size_t redio_pfb_pspec_nrows(const redio_pfb_pspec *h, size_t n_in) { return h ? nrows_of(h->c, n_in) : 0; }
+extern "C" int redio_pfb_pspec_is_fused(const redio_pfb_pspec *h) { return h && h->c.fused ? 1 : 0; }
+extern "C" int redio_pfb_pspec_set_split(redio_pfb_pspec *h, int mode) { return h ? set_split(h->c, mode) : REDIO_ERR_ARG; }
+extern "C" int redio_pfb_pspec_reserve(redio_pfb_pspec *h, size_t n_in)
+{
+    return h ? reserve(h->c, Polyphase<false>{h}, nrows_of(h->c, n_in)) : REDIO_ERR_ARG;
+}
+extern "C" int redio_pfb_pspec_reserve_u8(redio_pfb_pspec *h, size_t nbytes)
+{
+    return h ? reserve(h->c, Polyphase<true>{h}, nrows_of(h->c, nbytes / 2)) : REDIO_ERR_ARG;
+}
+extern "C" int redio_pfb_pspec_enqueue(redio_pfb_pspec *h, const void *d_in, size_t n_in, void *d_out, void *stream)
+{
+    return h ? enqueue(h->c, Polyphase<false>{h}, d_in, n_in, nrows_of(h->c, n_in), d_out, stream) : REDIO_ERR_ARG;
+}
+extern "C" int redio_pfb_pspec_enqueue_u8(redio_pfb_pspec *h, const void *d_bytes, size_t nbytes, void *d_out, void *stream)
+{
+    if (!h || (nbytes & 1)) return REDIO_ERR_ARG;
+    return enqueue(h->c, Polyphase<true>{h}, d_bytes, nbytes / 2, nrows_of(h->c, nbytes / 2), d_out, stream);
 }

@@ -125,6 +125,12 @@ hipError_t launch_pspec_rows_u8(const uint16_t *x, const float *win, float2 *row
 hipError_t launch_pspec_accum(const float2 *spec, float *dst, long q0, long nseg, long N, long K, long g_base, hipStream_t s);
 hipError_t launch_pspec_fold(const float *part, float *out, long nrows, long N, long S, hipStream_t s);
 
+// pfb_pspec_kernels.hip: the fused 64-channel polyphase spectrometer (taps_per_branch 4, 8 or 16).  x: cf32 samples, or with in_u8 one
+// 16-bit word per sample (2-byte aligned); nunits: output rows of K channelizer rows each, or with `split` their segments (every segment
+// of a whole number of rows); dst: 64 f32 per unit; h, tw64: the channelizer's branch taps and 64-point table.
+hipError_t launch_pfbspec64(const void *x, bool in_u8, const float *h, const float2 *tw64, float *dst, long nunits, long K, int taps_per_branch,
+                            bool split, bool fused, hipStream_t s);
+
 // pspec_real_kernels.hip: the real-input integrated power spectrum.  launch_pspecr2k: 2048 real points per transform, one wavefront per
 // unit (a row of K transforms, or with `split` one segment of at most 16); x: 4-byte aligned; dst: 1025 f32 per unit; win: 2048 values
 // or null; tw / stw: the tables of the plan's redio_fftr.  launch_pspec_real_rows: the generic path's row gather (rows: ntr packed
@@ -190,7 +196,7 @@ inline int num_cus()
 } // namespace redio
 
 // plan shapes for the carried-history layer (stream_carry.hip); defined next to each plan struct
-struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real; struct redio_pspec; struct redio_pspec_real;
+struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real; struct redio_pspec; struct redio_pspec_real; struct redio_pfb_pspec;
 void redio_fir_shape(const redio_fir *h, size_t *ntaps, size_t *decim, unsigned *flags, int *device);
 void redio_chain_shape(const redio_chain *h, size_t *ntaps, size_t *decim, int *nfft, int *device);
 void redio_pfb_shape(const redio_pfb *h, int *nchan, int *taps_per_branch, int *device);
@@ -198,6 +204,8 @@ void redio_ovsave_shape(const redio_ovsave *h, int *nfft, size_t *hop, int *devi
 void redio_ovsave_real_shape(const redio_ovsave_real *h, int *nfft, size_t *hop, int *device);
 void redio_pspec_shape(const redio_pspec *h, int *nfft, size_t *integrate, size_t *step, int *device);
 void redio_pspec_real_shape(const redio_pspec_real *h, int *nfft, size_t *integrate, size_t *step, int *device);
+void redio_pfb_pspec_shape(const redio_pfb_pspec *h, int *window, size_t *integrate, size_t *step, int *device); // window = nchan * taps_per_branch samples, step = nchan
+void redio_pfb_tables(const redio_pfb *h, const float **d_taps, const float2 **d_tw, unsigned *flags, int *fused_kernel); // pfb_api.hip
 // redio_ovsave_real_enqueue for the carried-history layer: d_in may be only 4-byte aligned (a message that started on an odd sample)
 int redio_ovsave_real_enqueue_any(redio_ovsave_real *h, const void *d_in, size_t n_in, void *d_out, void *stream);
 

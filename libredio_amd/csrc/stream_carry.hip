@@ -10,6 +10,7 @@
 //     overlap-save W = nfft                        H = hop            unit = hop output samples (cf32, or f32 for the real operator)
 //     power spectrum W = (integrate-1)*step + nfft H = integrate*step unit = 1 row (nfft f32 from cf32 samples, or from u8 I/Q byte pairs)
 //     real power spectrum  the same W and H in REAL samples  unit = 1 row (nfft/2 + 1 f32 from f32 samples)
+//     polyphase spectrum  W = (integrate-1+taps_per_branch)*nchan  H = integrate*nchan  unit = 1 row (nchan f32 from cf32 samples or u8 I/Q byte pairs)
 // so one layer serves them all.  The handle keeps the stream's unconsumed tail (fewer than W samples) on the device.
 // A call with n new samples
 //   1. appends the first min(n, W-1) new samples to the tail in a plan-owned staging buffer (one small copy),
@@ -55,7 +56,7 @@ hipError_t seam_copy(void *dst, const void *src, size_t bytes, hipStream_t st)
     SEAM_GO(uint8_t)
 #undef SEAM_GO
 }
-enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8, K_PSPEC_REAL }; // _U8: the samples are interleaved u8 I/Q byte pairs
+enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8, K_PSPEC_REAL, K_PFB_PSPEC, K_PFB_PSPEC_U8 }; // _U8: the samples are interleaved u8 I/Q byte pairs
 struct Carry {
     int device = 0;
     Kind kind = K_FIR;
@@ -95,6 +96,8 @@ int run(const Carry &c, const void *d_in, size_t n_in, void *d_out, void *stream
     case K_PSPEC: return redio_pspec_enqueue((redio_pspec *)c.plan, d_in, n_in, d_out, stream);
     case K_PSPEC_U8: return redio_pspec_enqueue_u8((redio_pspec *)c.plan, d_in, 2 * n_in, d_out, stream);
     case K_PSPEC_REAL: return redio_pspec_real_enqueue((redio_pspec_real *)c.plan, d_in, n_in, d_out, stream); // takes 4-byte aligned input itself
+    case K_PFB_PSPEC: return redio_pfb_pspec_enqueue((redio_pfb_pspec *)c.plan, d_in, n_in, d_out, stream);
+    case K_PFB_PSPEC_U8: return redio_pfb_pspec_enqueue_u8((redio_pfb_pspec *)c.plan, d_in, 2 * n_in, d_out, stream);
     case K_OVSAVE_REAL: return redio_ovsave_real_enqueue_any((redio_ovsave_real *)c.plan, d_in, n_in, d_out, stream); // a unit may start on an odd sample
     }
     return REDIO_ERR_ARG;
@@ -220,6 +223,7 @@ struct redio_ovsave_stream { Carry *c; };
 struct redio_ovsave_real_stream { Carry *c; };
 struct redio_pspec_stream { Carry *c; };
 struct redio_pspec_real_stream { Carry *c; };
+struct redio_pfb_pspec_stream { Carry *c; };
 
 #define RD_STREAM_API(NAME)                                                                                                     \
     extern "C" int redio_##NAME##_stream_destroy(redio_##NAME##_stream *h)                                                      \
@@ -248,6 +252,7 @@ RD_STREAM_API(ovsave)
 RD_STREAM_API(ovsave_real)
 RD_STREAM_API(pspec)
 RD_STREAM_API(pspec_real)
+RD_STREAM_API(pfb_pspec)
 
 template <typename Hd>
 static int make(Hd **h, Kind kind, void *plan, int dev, size_t W, size_t H, size_t in_elem, size_t unit_out, size_t out_elem, uintptr_t align = 0)
@@ -345,9 +350,10 @@ extern "C" int redio_ovsave_real_stream_create(redio_ovsave_real_stream **h, red
 // real plan, where a message may start and end on any sample), rows of `bins` f32 out.  The plan's scratch is sized here for the seam
 // windows (at most 2*W samples per head run, which `reserve` takes in its own entry's units: reserve_per_sample of them per sample);
 // a longer body run grows it at enqueue time unless the plan's reserve for the largest message + W came first.
+// bins: f32 per output row; 0: as many as the transform has points, -1: half of them and one (the real plan)
 template <typename Hd, typename Plan>
 static int make_pspec(Hd **h, Plan *plan, Kind kind, void (*shape)(const Plan *, int *, size_t *, size_t *, int *), int (*reserve)(Plan *, size_t),
-                      size_t reserve_per_sample, size_t in_elem, uintptr_t align, bool half_bins)
+                      size_t reserve_per_sample, size_t in_elem, uintptr_t align, long bins)
 {
     if (!h) return REDIO_ERR_ARG;
     *h = nullptr;
@@ -357,17 +363,39 @@ static int make_pspec(Hd **h, Plan *plan, Kind kind, void (*shape)(const Plan *,
     const size_t W = (K - 1) * step + (size_t)nfft;
     const int rr = reserve(plan, reserve_per_sample * 2 * W);
     if (rr) return rr;
-    return make(h, kind, plan, dev, W, K * step, in_elem, half_bins ? (size_t)nfft / 2 + 1 : (size_t)nfft, 4, align);
+    return make(h, kind, plan, dev, W, K * step, in_elem, bins < 0 ? (size_t)nfft / 2 + 1 : bins ? (size_t)bins : (size_t)nfft, 4, align);
 }
 extern "C" int redio_pspec_stream_create(redio_pspec_stream **h, redio_pspec *plan)
 {
-    return make_pspec(h, plan, K_PSPEC, redio_pspec_shape, redio_pspec_reserve, 1, 8, 0, false);
+    return make_pspec(h, plan, K_PSPEC, redio_pspec_shape, redio_pspec_reserve, 1, 8, 0, 0);
 }
 extern "C" int redio_pspec_stream_create_u8(redio_pspec_stream **h, redio_pspec *plan)
 {
-    return make_pspec(h, plan, K_PSPEC_U8, redio_pspec_shape, redio_pspec_reserve_u8, 2, 2, 1, false);
+    return make_pspec(h, plan, K_PSPEC_U8, redio_pspec_shape, redio_pspec_reserve_u8, 2, 2, 1, 0);
 }
 extern "C" int redio_pspec_real_stream_create(redio_pspec_real_stream **h, redio_pspec_real *plan)
 {
-    return make_pspec(h, plan, K_PSPEC_REAL, redio_pspec_real_shape, redio_pspec_real_reserve, 1, 4, 3, true);
+    return make_pspec(h, plan, K_PSPEC_REAL, redio_pspec_real_shape, redio_pspec_real_reserve, 1, 4, 3, -1);
+}
+// the polyphase spectrometer's two streams: the shape reports the nchan * taps_per_branch samples a channelizer row reads as the
+// transform's points and nchan as the step, so W and H come out as above; a row of the output holds `step` = nchan f32
+static long pfb_pspec_bins(const redio_pfb_pspec *plan)
+{
+    int window, dev; size_t K, step;
+    redio_pfb_pspec_shape(plan, &window, &K, &step, &dev);
+    return (long)step;
+}
+extern "C" int redio_pfb_pspec_stream_create(redio_pfb_pspec_stream **h, redio_pfb_pspec *plan)
+{
+    if (!h) return REDIO_ERR_ARG;
+    *h = nullptr;
+    if (!plan) return REDIO_ERR_ARG;
+    return make_pspec(h, plan, K_PFB_PSPEC, redio_pfb_pspec_shape, redio_pfb_pspec_reserve, 1, 8, 0, pfb_pspec_bins(plan));
+}
+extern "C" int redio_pfb_pspec_stream_create_u8(redio_pfb_pspec_stream **h, redio_pfb_pspec *plan)
+{
+    if (!h) return REDIO_ERR_ARG;
+    *h = nullptr;
+    if (!plan) return REDIO_ERR_ARG;
+    return make_pspec(h, plan, K_PFB_PSPEC_U8, redio_pfb_pspec_shape, redio_pfb_pspec_reserve_u8, 2, 2, 1, pfb_pspec_bins(plan));
 }

@@ -262,16 +262,17 @@ class Chain:
 
 
 class Stream:
-    """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec,pspec_real}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
+    """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec,pspec_real,pfb_pspec}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
     segmentation of the input gives the bits of one stateless call on the whole stream (the stateless plans keep the
     reference's per-message semantics, dsputils.rs:30-32).  `plan` is a Fir, Chain, Channelizer, OverlapSave, OverlapSaveReal, PowerSpectrum
-    (complex64 in, float32 rows out) or PowerSpectrumReal (float32 in, float32 rows out)."""
+    (complex64 in, float32 rows out), PowerSpectrumReal (float32 in, float32 rows out) or PolyphaseSpectrum (complex64 in, float32 rows
+    of nchan out)."""
 
     def __init__(self, plan, u8=False):
-        """u8=True (Chain, Channelizer and PowerSpectrum): the stream arrives as the receiver's interleaved u8 I/Q bytes (uint8
-        tensors, two bytes per sample; redio_{chain,pfb,pspec}_stream_create_u8)."""
-        kind = {Fir: "fir", Chain: "chain"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec", "PowerSpectrumReal": "pspec_real"}[type(plan).__name__]
-        assert not u8 or kind in ("chain", "pfb", "pspec")
+        """u8=True (Chain, Channelizer, PowerSpectrum and PolyphaseSpectrum): the stream arrives as the receiver's interleaved u8 I/Q
+        bytes (uint8 tensors, two bytes per sample; redio_{chain,pfb,pspec,pfb_pspec}_stream_create_u8)."""
+        kind = {Fir: "fir", Chain: "chain"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec", "PowerSpectrumReal": "pspec_real", "PolyphaseSpectrum": "pfb_pspec"}[type(plan).__name__]
+        assert not u8 or kind in ("chain", "pfb", "pspec", "pfb_pspec")
         self._kind, self._plan, self._u8 = kind, plan, bool(u8)          # the plan must outlive the stream handle
         self._h = C.c_void_p()
         check(getattr(lib(), f"redio_{kind}_stream_create" + ("_u8" if u8 else ""))(C.byref(self._h), plan._h), f"{kind}_stream_create")
@@ -303,7 +304,7 @@ class Stream:
             nsamp = x.numel()
         n = self.nout(nsamp)
         if out is None:
-            out = torch.empty(max(n, 1), dtype=torch.float32 if self._kind == "pspec" else want, device=x.device)
+            out = torch.empty(max(n, 1), dtype=torch.float32 if self._kind in ("pspec", "pfb_pspec") else want, device=x.device)
         assert out.numel() >= n
         got = C.c_size_t(0)
         check(self._f("enqueue")(self._h, _dev_ptr(x) if x.numel() else None, nsamp, _dev_ptr(out), C.byref(got), current_stream()),
@@ -789,3 +790,64 @@ class PowerSpectrumReal(_PowerSpectrumBase):
         self.nbins = int(nfft) // 2 + 1
         super().__init__(self.nbins, nfft, integrate, step, window)
         assert lib().redio_pspec_real_nbins(self._h) == self.nbins
+
+
+class PolyphaseSpectrum:
+    """redio_pfb_pspec_*: the polyphase spectrometer -- |row[c]|^2 of a Channelizer's rows (ngroups = 1) summed over `integrate`
+    consecutive rows in the blocked order of DESIGN.md 5.3c (contract: DESIGN.md 5.6b), bit for bit Channelizer followed by
+    PowerSpectrum(nchan, integrate).spectra: complex64 samples (or, from_bytes, the receiver's u8 I/Q bytes) in, rows of nchan
+    float32 out.  64 channels with 4 / 8 / 16 taps per branch are one kernel (is_fused): the channel rows never reach memory."""
+
+    AUTO, ROWS, SEGMENTS = 0, 1, 2
+
+    def __init__(self, proto, nchan=64, taps_per_branch=16, integrate=1, fused=True):
+        t, p = _taps(proto)
+        assert len(t) == nchan * taps_per_branch
+        self.nchan, self.taps_per_branch, self.integrate = int(nchan), int(taps_per_branch), int(integrate)
+        self._h = C.c_void_p()
+        check(lib().redio_pfb_pspec_create(C.byref(self._h), p, self.nchan, self.taps_per_branch, self.integrate,
+                                           REDIO_FIR_FUSED if fused else 0), "pfb_pspec_create")
+
+    def nrows(self, n_in):
+        return lib().redio_pfb_pspec_nrows(self._h, n_in)
+
+    @property
+    def is_fused(self):
+        return bool(lib().redio_pfb_pspec_is_fused(self._h))
+
+    def reserve(self, n_in, u8=False):
+        """all plan scratch (the inner channelizer's included) for calls of up to n_in samples, so that a call never allocates, e.g.
+        inside a Graph; u8: for from_bytes calls of as many samples (redio_pfb_pspec_reserve_u8 of twice as many bytes)"""
+        if u8:
+            check(lib().redio_pfb_pspec_reserve_u8(self._h, 2 * int(n_in)), "pfb_pspec_reserve_u8")
+        else:
+            check(lib().redio_pfb_pspec_reserve(self._h, int(n_in)), "pfb_pspec_reserve")
+
+    def set_split(self, mode):
+        """AUTO / ROWS (a wavefront owns whole output rows) / SEGMENTS (a run of whole 16-row segments, and a fold pass): the same bits."""
+        check(lib().redio_pfb_pspec_set_split(self._h, int(mode)), "pfb_pspec_set_split")
+
+    def _run(self, fn, x, count, nsamp, out):
+        import torch
+        rows = self.nrows(nsamp)
+        if out is None:
+            out = torch.empty(rows * self.nchan, dtype=torch.float32, device=x.device)
+        assert out.dtype == torch.float32 and out.numel() >= rows * self.nchan
+        check(getattr(lib(), fn)(self._h, _dev_ptr(x), count, _dev_ptr(out), current_stream()), fn)
+        return out[: rows * self.nchan].view(rows, self.nchan)
+
+    def __call__(self, x, out=None):
+        import torch
+        assert x.dtype == torch.complex64
+        return self._run("redio_pfb_pspec_enqueue", x, x.numel(), x.numel(), out)
+
+    def from_bytes(self, raw, out=None):
+        """redio_pfb_pspec_enqueue_u8: the rows of bitfount.data_to_samples(raw) followed by this plan, bit for bit"""
+        import torch
+        assert raw.dtype == torch.uint8 and raw.numel() % 2 == 0
+        return self._run("redio_pfb_pspec_enqueue_u8", raw, raw.numel(), raw.numel() // 2, out)
+
+    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
+        if getattr(self, "_h", None):
+            _safe_destroy("redio_pfb_pspec_destroy", self._h)
+            self._h = None

@@ -1,5 +1,5 @@
 """Throughput of the non-headline configs of BASELINE.json on one MI355X (own measurements; bench.py
-stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit]..."""
+stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit]..."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, libredio_amd as R
@@ -254,6 +254,68 @@ if "pspecrealsplit" in which:
                 plan.set_split(mode)
                 ms[mode - 1] = min(ms[mode - 1], timeit(lambda: plan(x, out=out), n=10, warm=3))
         print(f"PSPEC-REAL 2048 K={k} ({rows} rows): mode 1 {ms[0]:.3f} ms  mode 2 {ms[1]:.3f} ms")
+        del plan, out
+    del x
+if "pfbpspec" in which:
+    # the polyphase spectrometer of 2^28 samples resident in HBM: (n) redio_pfb_pspec_enqueue[_u8] against (a) redio_pfb_enqueue[_u8]
+    # alone on the same samples, which writes every channel row, and (b) what a caller without this plan does -- the channelizer into a
+    # row buffer as large as the input, then PowerSpectrum(nchan, K).spectra -- whose rows are compared with (n)'s bit for bit before
+    # anything is timed.  Timed alternately, twice each, in this one process; the smaller time of each is printed.  Algorithmic bytes
+    # per sample of (n): 8 (cf32) or 2 (u8) + 4 / K; of (b): 8 or 2 read + 8 written + 8 read + 4 / K.
+    # The bar: n < b on every shape; the target on the fused cf32 shapes: n < a.
+    xc = R.synth_iq(0x5EED0004, 0, n)
+    xb = torch.randint(0, 256, (2 * n,), dtype=torch.uint8, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))
+    for M, P, k, u8 in ((64, 16, 16, False), (64, 16, 1024, False), (64, 4, 16, False), (64, 16, 16, True), (64, 16, 1024, True), (64, 4, 16, True),
+                        (256, 8, 16, False)):
+        h = R.dsputils.lpf_corrected(M * P, 0.45 / M)
+        plan = R.PolyphaseSpectrum(h, M, P, k)
+        plan.reserve(n, u8=u8)
+        x = xb if u8 else xc
+        rows = plan.nrows(n)
+        out = torch.empty(rows * M, dtype=torch.float32, device="cuda")
+        chan = R.Channelizer(h, M, P)
+        if u8: R.check(R.lib().redio_pfb_reserve_u8(chan._h, 2 * n, 1), "pfb_reserve_u8")
+        else: chan.reserve(n)
+        crows = torch.empty((chan.nrows(n), M), dtype=torch.complex64, device="cuda")
+        old = R.PowerSpectrum(M, k)
+        old.reserve(rows * k * M)
+        out_b = torch.empty_like(out)
+        run_n = (lambda: plan.from_bytes(x, out=out)) if u8 else (lambda: plan(x, out=out))
+        run_a = (lambda: chan.from_bytes(x, out=crows)) if u8 else (lambda: chan(x, out=crows))
+        def route_b():
+            run_a()
+            old.spectra(crows.view(-1)[: rows * k * M], out=out_b)
+        run_n(); route_b()
+        same = torch.equal(out.view(torch.int32), out_b.view(torch.int32))
+        assert same, "leg (b) and leg (n) differ"
+        reps = 10 if plan.is_fused else 3
+        ms_n = ms_a = ms_b = 1e30
+        for _ in range(2):
+            ms_n = min(ms_n, timeit(run_n, n=reps, warm=3))
+            ms_a = min(ms_a, timeit(run_a, n=reps, warm=3))
+            ms_b = min(ms_b, timeit(route_b, n=3, warm=2))
+        b = (2 if u8 else 8) + 4 / k
+        print(f"PFB-PSPEC {M}x{P} K={k} from {'u8' if u8 else 'cf32'} ({'fused' if plan.is_fused else 'generic'}): {rows} rows  (n) {ms_n:.3f} ms  {n/ms_n/1e6:.1f} GS/s  "
+              f"{b*n/ms_n/1e6:.0f} GB/s algorithmic ({b*n/ms_n/1e6/8000:.1%} of 8 TB/s at {b:.3f} B/sample) | (a) channelizer alone: {ms_a:.3f} ms | "
+              f"(b) channelizer + PowerSpectrum({M}, {k}).spectra: {ms_b:.3f} ms, rows bit-equal: {same} | n/a = {ms_n/ms_a:.3f}  n/b = {ms_n/ms_b:.3f}", flush=True)
+        del plan, out, chan, crows, old, out_b
+    del xc, xb
+if "pfbpspecsplit" in which:
+    # the table behind PFBSPEC_SPLIT_WAVES (pfb_pspec_core.h): 2^28 cf32 samples, 64 x 16, a wave per run of whole rows against a wave per
+    # run of whole segments + fold.  Waves of mode 1: one per output row from K = 64 up (2 rows per wave at K = 32)
+    x = R.synth_iq(0x5EED0004, 0, n)
+    h = R.dsputils.lpf_corrected(1024, 0.45 / 64)
+    for k in (32, 64, 128, 256, 512, 1024, 2048, 4096):
+        plan = R.PolyphaseSpectrum(h, 64, 16, k)
+        plan.reserve(n)
+        rows = plan.nrows(n)
+        out = torch.empty(rows * 64, dtype=torch.float32, device="cuda")
+        ms = [1e30, 1e30]
+        for _ in range(2):
+            for mode in (1, 2):
+                plan.set_split(mode)
+                ms[mode - 1] = min(ms[mode - 1], timeit(lambda: plan(x, out=out), n=10, warm=3))
+        print(f"PFB-PSPEC 64x16 K={k} ({rows} rows, {min(rows, 2048) if k >= 64 else -(-rows // max(2, -(-rows // 2048)))} waves in mode 1): mode 1 {ms[0]:.3f} ms  mode 2 {ms[1]:.3f} ms", flush=True)
         del plan, out
     del x
 if "fftall" in which:
