@@ -37,9 +37,17 @@ __device__ __forceinline__ void static_for4(F &&f)
 // RES: the FIR runs with the taps resident in scalar registers (fir_lane_v_res).  PRECONDITION of RES: the taps are bit-palindromic
 // (taps[i] and taps[K-1-i] the same 32-bit pattern); the host decides that once per plan (taps_bit_palindromic) and every launcher
 // below takes the answer.  !RES: any taps (fir_lane_v, staged per chunk through the scalar cache).
+// SCH: the block schedule of the transforming forms with one sub-tile of loads in flight (chain_v4_sched below picks it):
+//   0  the sub-tile loop: a step's place in its block is a run-time fact (the register shift, the (j & 3) test), the transform's
+//      middle-stage twiddles are global loads behind the stream request;
+//   1  a loop over whole blocks of four steps whose place S is a compile-time fact: the FIR's results go straight to a[4 S ...], and the
+//      loop issues no global load but the stream (middle-stage twiddles from the LDS table PF2 uses, tw[0] resident);
+//   2  1, and the transform of block b runs UNDER the FIR of block b + 1's first sub-tile, piece by piece between that window's read
+//      chunks (fft1kn_wave_piece through the FIR's per-chunk hook), its exchanges in halves behind the image -- which stays intact, so
+//      the halo is never held in registers across a transform.  A run's last block has no next FIR and transforms as in 1.
 // One body for the single-message kernels, the list kernel and their any-taps twins; `wave` is the wavefront's index within its
 // message (the workgroup index of a single-message launch).
-template <int K, int D, bool FUSED, int WPS, int CH, bool FIR_ONLY, bool TWP, bool IN_U8, bool PF2, bool RES>
+template <int K, int D, bool FUSED, int WPS, int CH, bool FIR_ONLY, bool TWP, bool IN_U8, bool PF2, bool RES, int SCH>
 __device__ __forceinline__ void chain_v4_body(const float2 *__restrict__ x, const float *__restrict__ taps,
                                               const float2 *__restrict__ tw, float2 *__restrict__ out,
                                               long nblocks, long blocks_per_wave, long wave, unsigned long long *dbg, long dbg_cap)
@@ -124,8 +132,11 @@ __device__ __forceinline__ void chain_v4_body(const float2 *__restrict__ x, cons
     // PF2: the 60 twiddles of the transform's middle stages (Fft1knTw12: 15 per lane, 4 distinct sets by lane >> 4) sit in LDS behind the
     // image for the life of the wave, so the transform issues NO global load: its twiddle loads would queue behind the sub-tile request
     // (loads return in order) and make the transform wait for it
-    constexpr int T12_OFF = G::lds_elems(SUB_OUT) > FFT1KN_LDS ? G::lds_elems(SUB_OUT) : FFT1KN_LDS;
-    if constexpr (PF2 && !FIR_ONLY) {
+    static_assert(SCH == 0 || (!PF2 && !FIR_ONLY && TWP && WPS == 2), "the block schedules: the transforming product forms");
+    constexpr int EXH_OFF = G::lds_elems(SUB_OUT) > FFT1KN_LDS ? G::lds_elems(SUB_OUT) : FFT1KN_LDS; // SCH 2: the half exchanges, behind image and one-piece exchange
+    constexpr int T12_OFF = EXH_OFF + (SCH == 2 ? FFT1KN_HALF_LDS : 0);
+    static_assert(SCH == 0 || (T12_OFF + 60) * sizeof(float2) <= 160 * 1024 / 8 - 480, "within the request of chain_v4_lds at two waves per SIMD");
+    if constexpr ((PF2 || SCH != 0) && !FIR_ONLY) {
         if (lane < 60) {
             const int k4 = lane / 15, i = lane % 15;
             const int idx = i < 3 ? 64 * k4 * (i + 1) : 16 * (k4 + 4 * ((i - 3) / 3)) * ((i - 3) % 3 + 1);
@@ -193,7 +204,94 @@ __device__ __forceinline__ void chain_v4_body(const float2 *__restrict__ x, cons
         }
         wave_lds_fence();
     };
-    if constexpr (PF2) {
+    // SCH 1, 2: tw[0] (the first stage's unit twiddle) in two registers and the middle-stage twiddles from the LDS table, so that a block's
+    // transform issues no global load
+    [[maybe_unused]] float2 one = make_float2(0.f, 0.f);
+    if constexpr (SCH != 0) {
+        one = tw[0];
+        asm volatile("" : "+v"(one.x), "+v"(one.y));
+    }
+    [[maybe_unused]] auto t12_lds = [&](Fft1knTw12 &t12, int ln) {
+        const float2 *T = ex + T12_OFF + 15 * (ln >> 4);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) t12.a[i] = T[i];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) t12.b[i] = T[3 + i];
+    };
+    // SCH 1, 2: one sub-tile at place S of its block.  more: another sub-tile follows in this run (S < 3: always); xform: the block
+    // completed by this step (S == 3) is transformed here, the image its scratch and the halo held meanwhile; hook: fir_core.h
+    [[maybe_unused]] auto sstep = [&](long j, auto place, bool more_, bool xform_, auto &&hook) {
+        constexpr int S = decltype(place)::value;
+        const bool more = S < 3 || more_, xform = S == 3 && xform_;
+        if (more) fetch_to(pre, j + 1);
+        float2 acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = make_float2(0.f, 0.f);
+        int lf = lane; // opaque per sub-tile: keeps LDS address arithmetic out of the loop's live set
+        asm volatile("" : "+v"(lf));
+        if constexpr (RES) fir_lane_v_res<K, D, R, FUSED, CH>(xs4, lf, rtaps, acc, hook);
+        else fir_lane_v<K, D, R, FUSED, CH>(xs4, lf, taps, acc, hook);
+#pragma unroll
+        for (int r = 0; r < R; ++r) a[4 * S + r] = acc[r];
+        wave_lds_fence(); // window reads done
+        v4f_t halo = v4f_t{0.f, 0.f, 0.f, 0.f};
+        if (more && lf < HALO_V) halo = xs4[G::lds_index(SUB_NEW + 2 * lf) / 2];
+        if (xform) {
+            wave_lds_fence();
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            Fft1knTw12 t12;
+            t12_lds(t12, ln);
+            const float2 one1[1] = {one};
+            fft1kn_wave_tw<false>(a, ex, one1, t12, t34, out + (b0 + (j >> 2)) * 1024, ln);
+            wave_lds_fence();
+        }
+        if (more) {
+            if (lf < HALO_V) xs4[G::lds_index(2 * lf) / 2] = halo;
+            park_from(pre);
+        }
+        wave_lds_fence();
+    };
+    using S0 = std::integral_constant<int, 0>;
+    using S1 = std::integral_constant<int, 1>;
+    using S2 = std::integral_constant<int, 2>;
+    using S3 = std::integral_constant<int, 3>;
+    if constexpr (SCH == 1) {
+        const long nb = b1 - b0;
+#pragma unroll 1
+        for (long blk = 0; blk < nb; ++blk) {
+            sstep(4 * blk, S0{}, true, false, FirNoHook{});
+            sstep(4 * blk + 1, S1{}, true, false, FirNoHook{});
+            sstep(4 * blk + 2, S2{}, true, false, FirNoHook{});
+            sstep(4 * blk + 3, S3{}, blk + 1 < nb, true, FirNoHook{});
+        }
+    } else if constexpr (SCH == 2) {
+        constexpr int NCH = fir_num_chunks<K, D, R, CH>();
+        const long nb = b1 - b0;
+        sstep(0, S0{}, true, false, FirNoHook{});
+#pragma unroll 1
+        for (long blk = 0;; ++blk) {
+            sstep(4 * blk + 1, S1{}, true, false, FirNoHook{});
+            sstep(4 * blk + 2, S2{}, true, false, FirNoHook{});
+            const bool more = blk + 1 < nb;
+            sstep(4 * blk + 3, S3{}, more, !more, FirNoHook{}); // the run's last block: transformed there
+            if (!more) break;
+            // block blk under the first FIR of block blk + 1
+            float2 ap[16], u[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) ap[i] = a[i];
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            Fft1knTw12 t12;
+            float2 *dst = out + (b0 + blk) * 1024;
+            auto piece = [&](auto C) {
+                fft1kn_wave_piece<decltype(C)::value, false>(ap, u, ex + EXH_OFF, one, ex + T12_OFF + 15 * (ln >> 4), t12, t34, dst, ln);
+            };
+            sstep(4 * blk + 4, S0{}, true, false, piece);
+            if constexpr (NCH < FFT1KN_PIECES) // a window of fewer chunks than the transform has pieces: the rest behind it
+                static_for4<FFT1KN_PIECES - NCH>([&](auto I) { piece(std::integral_constant<int, NCH + I.value>{}); });
+        }
+    } else if constexpr (PF2) {
         fetch_to(pre, 1);
         using two = std::integral_constant<int, 2>;
 #pragma unroll 1
@@ -219,6 +317,16 @@ __device__ __forceinline__ void chain_v4_body(const float2 *__restrict__ x, cons
     }
 }
 
+// The block schedule (chain_v4_body, SCH) of a kernel's template parameters: one rule for the single-message kernels, the list
+// kernels and the any-taps twins.  The transforming product forms run schedule 1 (round 8: - 1.1 % on the headline kernel, every run
+// beyond the parent's range); schedule 2 measured no better than 1 (profiles/r08_chain_block_schedule.txt) and is built only as
+// chain_v4_sched2_kernel of the measurement build.
+template <int WPS, bool FIR_ONLY, bool TWP, bool PF2, bool RES>
+constexpr int chain_v4_sched()
+{
+    return (WPS == 2 && !FIR_ONLY && TWP && !PF2) ? 1 : 0;
+}
+
 // PRECONDITION: bit-palindromic taps (chain_v4_body, RES).  The template parameters, and so the name a profiler prints, are those of
 // the kernel before the resident-taps form.
 template <int K, int D, bool FUSED, int WPS, int CH, bool FIR_ONLY = false, bool TWP = false, bool IN_U8 = false, bool PF2 = false>
@@ -226,7 +334,7 @@ __global__ __launch_bounds__(64, WPS) void chain_v4_kernel(const float2 *__restr
                                                            const float2 *__restrict__ tw, float2 *__restrict__ out,
                                                            long nblocks, long blocks_per_wave, unsigned long long *dbg, long dbg_cap)
 {
-    chain_v4_body<K, D, FUSED, WPS, CH, FIR_ONLY, TWP, IN_U8, PF2, true>(x, taps, tw, out, nblocks, blocks_per_wave, (long)blockIdx.x, dbg, dbg_cap);
+    chain_v4_body<K, D, FUSED, WPS, CH, FIR_ONLY, TWP, IN_U8, PF2, true, chain_v4_sched<WPS, FIR_ONLY, TWP, PF2, true>()>(x, taps, tw, out, nblocks, blocks_per_wave, (long)blockIdx.x, dbg, dbg_cap);
 }
 // any taps: the plans whose taps are not bit-palindromic
 template <int K, int D, bool FUSED, int WPS, int CH, bool FIR_ONLY = false, bool TWP = false, bool IN_U8 = false, bool PF2 = false>
@@ -234,8 +342,20 @@ __global__ __launch_bounds__(64, WPS) void chain_v4_anytaps_kernel(const float2 
                                                                    const float2 *__restrict__ tw, float2 *__restrict__ out,
                                                                    long nblocks, long blocks_per_wave, unsigned long long *dbg, long dbg_cap)
 {
-    chain_v4_body<K, D, FUSED, WPS, CH, FIR_ONLY, TWP, IN_U8, PF2, false>(x, taps, tw, out, nblocks, blocks_per_wave, (long)blockIdx.x, dbg, dbg_cap);
+    chain_v4_body<K, D, FUSED, WPS, CH, FIR_ONLY, TWP, IN_U8, PF2, false, chain_v4_sched<WPS, FIR_ONLY, TWP, PF2, false>()>(x, taps, tw, out, nblocks, blocks_per_wave, (long)blockIdx.x, dbg, dbg_cap);
 }
+
+#ifdef REDIO_MEASURE
+// schedule 2 (the transform of block b under the first FIR of block b + 1) on the headline shape, resident taps: A/B against the product
+// form in one process, tools/chain_sched_ab.py
+template <int K, int D, bool FUSED>
+__global__ __launch_bounds__(64, 2) void chain_v4_sched2_kernel(const float2 *__restrict__ x, const float *__restrict__ taps,
+                                                                const float2 *__restrict__ tw, float2 *__restrict__ out,
+                                                                long nblocks, long blocks_per_wave, unsigned long long *dbg, long dbg_cap)
+{
+    chain_v4_body<K, D, FUSED, 2, 8, false, true, false, false, true, 2>(x, taps, tw, out, nblocks, blocks_per_wave, (long)blockIdx.x, dbg, dbg_cap);
+}
+#endif
 
 // A list of independent cf32 messages in ONE launch (redio_chain_enqueue_list): message i owns the waves [wave0[i], wave0[i + 1]).
 // The list travels by value in the kernel arguments: no descriptor buffer, nothing to upload or recycle, and a captured launch carries
@@ -260,7 +380,7 @@ __device__ __forceinline__ void chain_v4_list_body(const ChainList &list, const 
     for (int i = 1; i < list.count; ++i) m = w >= list.wave0[i] ? i : m;
     m = __builtin_amdgcn_readfirstlane(m);
     // wave index within the message: b0 < nblocks, the host gives message i ceil(nblocks_i / bpw) waves
-    chain_v4_body<K, D, FUSED, 2, 8, false, true, false, false, RES>(list.x[m], taps, tw, list.out[m], list.nblocks[m], blocks_per_wave,
+    chain_v4_body<K, D, FUSED, 2, 8, false, true, false, false, RES, chain_v4_sched<2, false, true, false, RES>()>(list.x[m], taps, tw, list.out[m], list.nblocks[m], blocks_per_wave,
                                                                      (long)(w - list.wave0[m]), nullptr, 0);
 }
 
@@ -343,6 +463,14 @@ hipError_t launch_chain_v4(const float2 *x, const float *taps, bool pal, const f
     if (measure_env("REDIO_CHAIN_WPS3")) return launch_v4_t<127, 5, 3, 8, false, false>(x, taps, pal, tw, out, nblocks, fused, s, dbg, dbg_cap);
     // two sub-tiles of loads in flight (round 6): A/B against the product form in one process, tools/chain_pf2_ab.py
     if (measure_env("REDIO_CHAIN_PF2")) return launch_v4_t<127, 5, 2, 8, false, true, false, true>(x, taps, pal, tw, out, nblocks, fused, s, dbg, dbg_cap);
+    // the transform under the next FIR (round 8): the product form's geometry and LDS request
+    if (pal && measure_env("REDIO_CHAIN_SCHED2")) {
+        const long bpw = chain_v4_blocks_per_wave(nblocks, 2);
+        const dim3 grid((unsigned)((nblocks + bpw - 1) / bpw));
+        if (fused) hipLaunchKernelGGL((chain_v4_sched2_kernel<127, 5, true>), grid, dim3(64), (chain_v4_lds<127, 5, 2>()), s, x, taps, tw, out, nblocks, bpw, dbg, dbg_cap);
+        else hipLaunchKernelGGL((chain_v4_sched2_kernel<127, 5, false>), grid, dim3(64), (chain_v4_lds<127, 5, 2>()), s, x, taps, tw, out, nblocks, bpw, dbg, dbg_cap);
+        return hipGetLastError();
+    }
 #endif
     return launch_v4_t<127, 5, 2, 8, false, true>(x, taps, pal, tw, out, nblocks, fused, s, dbg, dbg_cap); // last-stage twiddles resident
 }

@@ -348,6 +348,31 @@ RD_HD int fft1kn_x2_store(int lane, int k2, int k3)
 }
 // lane l2 = k4 + 4 k3 + 16 k2 reads element f = d1 + 4 d0
 RD_HD int fft1kn_x2_load(int lane, int f) { return ((f >> 2) + 4 * (f & 3)) * FFT1KN_ROW2 + lane; }
+// The two exchanges in two HALVES each, for a caller whose LDS cannot hold a whole image beside what else is live (the chain
+// kernel transforms block b under the FIR of block b + 1, whose window image stays where it is).  A half is stored, fenced, read,
+// fenced, and the second half then reuses the same FFT1KN_HALF_LDS float2.  The split keeps every READ at full width (a masked
+// read would need its lanes' registers merged), the stores of a half come from half of the lanes:
+//   X1: by COLUMN (the writer's lane): half h holds columns 32 h .. 32 h + 31, stored by lanes 32 h .. 32 h + 31 (all 16 values each)
+//       and read by every lane for e = 8 h .. 8 h + 7.  Row stride 36 = 68 - 32: the same banks as the one-piece image.
+//   X2: by ROW: half h holds rows 8 h .. 8 h + 7, stored by the lanes whose row that is ((lane & 2) == 2 h, all 16 values each) and
+//       read by every lane for the f whose row lies there ((f & 2) == 2 h).  Row stride 66 as in the one-piece image.
+// With one-piece index i = row * ROW + col: X1 half = col >> 5 and half index = row * 36 + (col & 31); X2 half = row >> 3 and half
+// index = (row & 7) * 66 + col (fft1kn_x1_half_of / fft1kn_x2_half_of; tests/emu_sched enumerates both).
+constexpr int FFT1KN_HROW1 = 36;
+constexpr int FFT1KN_HALF_LDS = 16 * FFT1KN_HROW1; // float2 per wave: 576 >= 8 * FFT1KN_ROW2
+RD_HD int fft1kn_x1_half_of(int i, int *half) { *half = (i % FFT1KN_ROW1) >> 5; return (i / FFT1KN_ROW1) * FFT1KN_HROW1 + ((i % FFT1KN_ROW1) & 31); }
+RD_HD int fft1kn_x2_half_of(int i, int *half) { *half = (i / FFT1KN_ROW2) >> 3; return ((i / FFT1KN_ROW2) & 7) * FFT1KN_ROW2 + i % FFT1KN_ROW2; }
+RD_HD int fft1kn_x1h_store_half(int lane) { return lane >> 5; }
+RD_HD int fft1kn_x1h_store(int lane, int k4, int d0) { return (4 * k4 + d0) * FFT1KN_HROW1 + (lane & 31); }
+RD_HD int fft1kn_x1h_load_half(int e) { return e >> 3; }
+RD_HD int fft1kn_x1h_load(int lane, int e) { return (4 * (lane >> 4) + ((lane >> 2) & 3)) * FFT1KN_HROW1 + (lane & 3) + 4 * (e & 7); }
+RD_HD int fft1kn_x2h_store_half(int lane) { return (lane >> 1) & 1; }
+RD_HD int fft1kn_x2h_store(int lane, int k2, int k3)
+{
+    return ((((lane >> 2) & 3) + 4 * (lane & 3)) & 7) * FFT1KN_ROW2 + (lane >> 4) + 4 * k3 + 16 * k2;
+}
+RD_HD int fft1kn_x2h_load_half(int f) { return (f >> 1) & 1; }
+RD_HD int fft1kn_x2h_load(int lane, int f) { return (((f >> 2) + 4 * (f & 3)) & 7) * FFT1KN_ROW2 + lane; }
 // w[d1 + 4 d0] -> w[k1 + 4 k0] = X[lane + 64 k1 + 256 k0]
 template <bool INV>
 RD_HD void fft1kn_pass34(float2 (&w)[16], const Fft1knTw34 &t)

@@ -74,6 +74,22 @@ __device__ __forceinline__ void fft1k_wave(SrcPtr src, float2 *dst, float2 *ex,
 
 namespace redio {
 
+// a[k1 + 4 k0] = X[ln + 64 k1 + 256 k0] to the block's spectrum: 512 contiguous bytes per wave instruction
+__device__ __forceinline__ void fft1kn_store_spectrum(const float2 (&a)[16], float2 *dst, int ln)
+{
+#pragma unroll
+    for (int k0 = 0; k0 < 4; ++k0)
+#pragma unroll
+#if defined(REDIO_EXP_CHAIN_NT) && (REDIO_EXP_CHAIN_NT & 2) // the fused chain writes its spectra once (chain_v4.hip sets this before including the header)
+        for (int k1 = 0; k1 < 4; ++k1) {
+            typedef float nt_v2f __attribute__((ext_vector_type(2)));
+            __builtin_nontemporal_store(nt_v2f{a[k1 + 4 * k0].x, a[k1 + 4 * k0].y}, reinterpret_cast<nt_v2f *>(dst + ln + 64 * k1 + 256 * k0));
+        }
+#else
+        for (int k1 = 0; k1 < 4; ++k1) dst[ln + 64 * k1 + 256 * k0] = a[k1 + 4 * k0];
+#endif
+}
+
 // The "native" 1024-point forward transform of fft_core.h by the calling wavefront: a[4 s + r] holds
 // y[256 s + 4 lane + r] on entry (the FIR's own register layout), ex is FFT1KN_LDS float2 of LDS owned
 // by this wave, dst the block's spectrum in global memory (natural order).
@@ -100,17 +116,76 @@ __device__ __forceinline__ void fft1kn_wave_tw(float2 (&a)[16], float2 *ex, cons
     for (int f = 0; f < 16; ++f) a[f] = ex[fft1kn_x2_load(ln, f)];
     wave_lds_fence();
     fft1kn_pass34<INV>(a, t34);
+    fft1kn_store_spectrum(a, dst, ln);
+}
+
+// fft1kn_wave_tw in the EIGHT pieces a caller can issue between other work (the chain kernel: between the window-read chunks of the
+// next block's first FIR), with each exchange in two halves (fft_core.h: fft1kn_x1h_*, fft1kn_x2h_*) so that it needs FFT1KN_HALF_LDS
+// float2 at exh instead of FFT1KN_LDS.  a: the block on entry (the layout of fft1kn_wave_tw), scratch afterwards; u: scratch (a half's
+// reads land while the other half's operands are still to be stored, so the passes alternate between the two arrays); one = tw[0];
+// T12: this lane's 15 middle-stage twiddles in LDS, Fft1knTw12 order (read in piece 2, used in piece 3: t12 lives in between).
+// Pieces 0 ... 7 in order give the bits of fft1kn_wave_tw: the same butterflies on the same values.
+constexpr int FFT1KN_PIECES = 8;
+template <int P, bool INV>
+__device__ __forceinline__ void fft1kn_wave_piece(float2 (&a)[16], float2 (&u)[16], float2 *exh, float2 one, const float2 *T12, Fft1knTw12 &t12,
+                                                  const Fft1knTw34 &t34, float2 *dst, int ln)
+{
+    if constexpr (P == 0) {
+        const float2 one1[1] = {one};
+        fft1kn_stage0<INV>(a, one1);
+        if (fft1kn_x1h_store_half(ln) == 0) {
 #pragma unroll
-    for (int k0 = 0; k0 < 4; ++k0)
+            for (int k4 = 0; k4 < 4; ++k4)
 #pragma unroll
-#if defined(REDIO_EXP_CHAIN_NT) && (REDIO_EXP_CHAIN_NT & 2) // the fused chain writes its spectra once (chain_v4.hip sets this before including the header)
-        for (int k1 = 0; k1 < 4; ++k1) {
-            typedef float nt_v2f __attribute__((ext_vector_type(2)));
-            __builtin_nontemporal_store(nt_v2f{a[k1 + 4 * k0].x, a[k1 + 4 * k0].y}, reinterpret_cast<nt_v2f *>(dst + ln + 64 * k1 + 256 * k0));
+                for (int d0 = 0; d0 < 4; ++d0) exh[fft1kn_x1h_store(ln, k4, d0)] = a[4 * k4 + d0];
         }
-#else
-        for (int k1 = 0; k1 < 4; ++k1) dst[ln + 64 * k1 + 256 * k0] = a[k1 + 4 * k0];
-#endif
+    } else if constexpr (P == 1 || P == 2) {
+        constexpr int h = P - 1;
+        wave_lds_fence();
+#pragma unroll
+        for (int e = 8 * h; e < 8 * h + 8; ++e) u[e] = exh[fft1kn_x1h_load(ln, e)];
+        wave_lds_fence();
+        if constexpr (h == 0) {
+            if (fft1kn_x1h_store_half(ln) == 1) {
+#pragma unroll
+                for (int k4 = 0; k4 < 4; ++k4)
+#pragma unroll
+                    for (int d0 = 0; d0 < 4; ++d0) exh[fft1kn_x1h_store(ln, k4, d0)] = a[4 * k4 + d0];
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) t12.a[i] = T12[i];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) t12.b[i] = T12[3 + i];
+        }
+    } else if constexpr (P == 3) {
+        fft1kn_pass12<INV>(u, t12);
+        if (fft1kn_x2h_store_half(ln) == 0) {
+#pragma unroll
+            for (int k3 = 0; k3 < 4; ++k3)
+#pragma unroll
+                for (int k2 = 0; k2 < 4; ++k2) exh[fft1kn_x2h_store(ln, k2, k3)] = u[k2 + 4 * k3];
+        }
+    } else if constexpr (P == 4 || P == 5) {
+        constexpr int h = P - 4;
+        wave_lds_fence();
+#pragma unroll
+        for (int f = 0; f < 16; ++f)
+            if (fft1kn_x2h_load_half(f) == h) a[f] = exh[fft1kn_x2h_load(ln, f)];
+        wave_lds_fence();
+        if constexpr (h == 0) {
+            if (fft1kn_x2h_store_half(ln) == 1) {
+#pragma unroll
+                for (int k3 = 0; k3 < 4; ++k3)
+#pragma unroll
+                    for (int k2 = 0; k2 < 4; ++k2) exh[fft1kn_x2h_store(ln, k2, k3)] = u[k2 + 4 * k3];
+            }
+        }
+    } else if constexpr (P == 6) {
+        fft1kn_pass34<INV>(a, t34);
+    } else if constexpr (P == 7) {
+        fft1kn_store_spectrum(a, dst, ln);
+    }
 }
 
 // the same with the 30 lane-dependent twiddles loaded here (callers that transform many blocks load them

@@ -95,9 +95,19 @@ struct FirChunkTaps {
     RD_HD static constexpr int lo(int c) { return 2 * CH * c - (R - 1) * D; }
 };
 
-template <int c, int K, int D, int R, bool FUSED, int CH, typename Q, typename Lds4Ptr, typename TapPtr>
+// A caller's own work issued between the chunks of a window (the chain kernel: the previous block's transform, piece by piece):
+// hook(integral_constant<int, c>) runs once per chunk c = 0 ... fir_num_chunks - 1, after the next chunk's reads are requested and
+// before this chunk's multiply-adds, inside the chunk's scheduling region.  FirNoHook: nothing.
+struct FirNoHook {
+    template <typename C>
+    RD_HD void operator()(C) const {}
+};
+template <int K, int D, int R, int CH>
+RD_HD constexpr int fir_num_chunks() { return ((FirGeomV<K, D, R>::SPAN + 1) / 2 + CH - 1) / CH; }
+
+template <int c, int K, int D, int R, bool FUSED, int CH, typename Q, typename Lds4Ptr, typename TapPtr, typename Hook>
 RD_HD void fir_chunks_v(Lds4Ptr xs4, int base4, TapPtr h, Q (&q)[2][CH],
-                        float (&hb)[2][FirChunkTaps<K, D, R, CH>::NT], float2 (&acc)[R])
+                        float (&hb)[2][FirChunkTaps<K, D, R, CH>::NT], float2 (&acc)[R], Hook &hook)
 {
     using G = FirGeomV<K, D, R>;
     using T = FirChunkTaps<K, D, R, CH>;
@@ -119,6 +129,7 @@ RD_HD void fir_chunks_v(Lds4Ptr xs4, int base4, TapPtr h, Q (&q)[2][CH],
             constexpr int j = T::lo(c + 1) + J.value;
             if constexpr (c + 1 < NCH && j >= 0 && j < K) hb[(c + 1) & 1][J.value] = h[j];
         });
+        hook(std::integral_constant<int, c>{});
         fir_static_for<CH>([&](auto I) {
             constexpr int m = 2 * (c * CH + I.value);
             if constexpr (m < G::SPAN) {
@@ -140,12 +151,12 @@ RD_HD void fir_chunks_v(Lds4Ptr xs4, int base4, TapPtr h, Q (&q)[2][CH],
 #pragma unroll
         for (int r = 0; r < R; ++r) RD_PIN_F2(acc[r]);
         RD_SCHED_BARRIER();
-        fir_chunks_v<c + 1, K, D, R, FUSED, CH>(xs4, base4, h, q, hb, acc);
+        fir_chunks_v<c + 1, K, D, R, FUSED, CH>(xs4, base4, h, q, hb, acc, hook);
     }
 }
 
-template <int K, int D, int R, bool FUSED, int CH = 8 /* 16-byte reads per chunk */, typename Lds4Ptr, typename TapPtr>
-RD_HD void fir_lane_v(Lds4Ptr xs4, int lane_slot, TapPtr h, float2 (&acc)[R])
+template <int K, int D, int R, bool FUSED, int CH = 8 /* 16-byte reads per chunk */, typename Lds4Ptr, typename TapPtr, typename Hook>
+RD_HD void fir_lane_v(Lds4Ptr xs4, int lane_slot, TapPtr h, float2 (&acc)[R], Hook &&hook)
 {
     using G = FirGeomV<K, D, R>;
     using Q = typename std::remove_cv<typename std::remove_reference<decltype(xs4[0])>::type>::type;
@@ -163,7 +174,12 @@ RD_HD void fir_lane_v(Lds4Ptr xs4, int lane_slot, TapPtr h, float2 (&acc)[R])
         constexpr int i = I.value;
         if constexpr (i < NRD) q[0][i] = xs4[base4 + G::lds_index(2 * i) / 2];
     });
-    fir_chunks_v<0, K, D, R, FUSED, CH>(xs4, base4, h, q, hb, acc);
+    fir_chunks_v<0, K, D, R, FUSED, CH>(xs4, base4, h, q, hb, acc, hook);
+}
+template <int K, int D, int R, bool FUSED, int CH = 8, typename Lds4Ptr, typename TapPtr>
+RD_HD void fir_lane_v(Lds4Ptr xs4, int lane_slot, TapPtr h, float2 (&acc)[R])
+{
+    fir_lane_v<K, D, R, FUSED, CH>(xs4, lane_slot, h, acc, FirNoHook{});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -331,8 +347,8 @@ RD_HD void fir_read_res(float2 x0, float2 x1, const FirTapsResident<K> &t, float
 }
 #endif
 
-template <int c, int K, int D, int R, bool FUSED, int CH, typename Q, typename Lds4Ptr>
-RD_HD void fir_chunks_res(Lds4Ptr xs4, int base4, const FirTapsResident<K> &t, Q (&q)[2][CH], fir_acc_t (&acc)[R])
+template <int c, int K, int D, int R, bool FUSED, int CH, typename Q, typename Lds4Ptr, typename Hook>
+RD_HD void fir_chunks_res(Lds4Ptr xs4, int base4, const FirTapsResident<K> &t, Q (&q)[2][CH], fir_acc_t (&acc)[R], Hook &hook)
 {
     using G = FirGeomV<K, D, R>;
     constexpr int NRD = (G::SPAN + 1) / 2; // 16-byte reads in a window
@@ -349,6 +365,7 @@ RD_HD void fir_chunks_res(Lds4Ptr xs4, int base4, const FirTapsResident<K> &t, Q
 #endif
             if constexpr (i < NRD) q[(c + 1) & 1][I.value] = xs4[base4 + G::lds_index(2 * i) / 2];
         });
+        hook(std::integral_constant<int, c>{});
         fir_static_for<CH>([&](auto I) {
             constexpr int m = 2 * (c * CH + I.value);
             if constexpr (m < G::SPAN) {
@@ -362,14 +379,14 @@ RD_HD void fir_chunks_res(Lds4Ptr xs4, int base4, const FirTapsResident<K> &t, Q
             }
         });
         RD_SCHED_BARRIER();
-        fir_chunks_res<c + 1, K, D, R, FUSED, CH>(xs4, base4, t, q, acc);
+        fir_chunks_res<c + 1, K, D, R, FUSED, CH>(xs4, base4, t, q, acc, hook);
     }
 }
 
 // fir_lane_v with resident palindromic taps (PRECONDITION: the taps t was loaded from are bit-palindromic); xs4 on the device is a
 // view of 16-byte vectors of four floats
-template <int K, int D, int R, bool FUSED, int CH = 8, typename Lds4Ptr>
-RD_HD void fir_lane_v_res(Lds4Ptr xs4, int lane_slot, const FirTapsResident<K> &t, float2 (&acc)[R])
+template <int K, int D, int R, bool FUSED, int CH = 8, typename Lds4Ptr, typename Hook>
+RD_HD void fir_lane_v_res(Lds4Ptr xs4, int lane_slot, const FirTapsResident<K> &t, float2 (&acc)[R], Hook &&hook)
 {
     using G = FirGeomV<K, D, R>;
     using Q = typename std::remove_cv<typename std::remove_reference<decltype(xs4[0])>::type>::type;
@@ -389,7 +406,7 @@ RD_HD void fir_lane_v_res(Lds4Ptr xs4, int lane_slot, const FirTapsResident<K> &
 #else
     for (int r = 0; r < R; ++r) a[r] = acc[r];
 #endif
-    fir_chunks_res<0, K, D, R, FUSED, CH>(xs4, base4, t, q, a);
+    fir_chunks_res<0, K, D, R, FUSED, CH>(xs4, base4, t, q, a, hook);
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("s_nop 0"); // the last packed result, one wait state ahead of the compiler's first reader
 #pragma unroll
@@ -397,6 +414,11 @@ RD_HD void fir_lane_v_res(Lds4Ptr xs4, int lane_slot, const FirTapsResident<K> &
 #else
     for (int r = 0; r < R; ++r) acc[r] = a[r];
 #endif
+}
+template <int K, int D, int R, bool FUSED, int CH = 8, typename Lds4Ptr>
+RD_HD void fir_lane_v_res(Lds4Ptr xs4, int lane_slot, const FirTapsResident<K> &t, float2 (&acc)[R])
+{
+    fir_lane_v_res<K, D, R, FUSED, CH>(xs4, lane_slot, t, acc, FirNoHook{});
 }
 
 } // namespace redio
