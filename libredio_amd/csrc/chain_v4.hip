@@ -8,6 +8,15 @@
 #ifndef REDIO_EXP_CHAIN_NT
 #define REDIO_EXP_CHAIN_NT 3 // bit 0: non-temporal stream loads, bit 1: non-temporal spectrum stores (fft_wave.h)
 #endif
+// The seam between two sub-tiles and the wave's prologue (round 12, profiles/r12_chain_seam.txt), one bit per item so that the
+// measurement build can time each on its own (tools/chain_seam_ab.sh); a bit that is clear builds the parent's code for that item:
+//   bit 0  lane-constant LDS addresses (window base, halo slots, park slots, the transform's exchange rows) computed once per wave
+//   bit 1  stream loads and output stores through buffer descriptors of the wave's own run: scalar base, one constant lane offset
+//   bit 2  the halo's LDS read under the FIR's last chunk, its write branch-free behind the last window read
+//   bit 3  prologue: every request (taps, head, first sub-tile, twiddles) issued before the first wait
+#ifndef REDIO_EXP_SEAM
+#define REDIO_EXP_SEAM 15
+#endif
 #include "fir_core.h"
 #include "fft_wave.h"
 #include "redio_internal.h"
@@ -17,6 +26,8 @@
 namespace redio {
 
 typedef float v4f_t __attribute__((ext_vector_type(4)));
+
+constexpr int chain_gcd(int a, int b) { return b == 0 ? a : chain_gcd(b, a % b); }
 
 template <int N, typename F>
 __device__ __forceinline__ void static_for4(F &&f)
@@ -79,32 +90,73 @@ __device__ __forceinline__ void chain_v4_body(const float2 *__restrict__ x, cons
     if constexpr (RES) fir_taps_resident_load(rtaps, taps);
     // index of the first NEW pair of samples of sub-tile j (the halo precedes it): a pair is one float4, or one u32 of I/Q bytes
     using pair_t = typename std::conditional<IN_U8, unsigned, v4f_t>::type;
-    const pair_t *src0 = (IN_U8 ? reinterpret_cast<const pair_t *>(reinterpret_cast<const unsigned *>(x) + b0 * 512 * (long)D)
+    [[maybe_unused]] const pair_t *src0 = (IN_U8 ? reinterpret_cast<const pair_t *>(reinterpret_cast<const unsigned *>(x) + b0 * 512 * (long)D)
                                 : reinterpret_cast<const pair_t *>(x + b0 * 1024 * (long)D)) + lane;
     auto samples = [](pair_t w) -> v4f_t {
         if constexpr (IN_U8) return v4f_t{i2f(w & 255u), i2f((w >> 8) & 255u), i2f((w >> 16) & 255u), i2f(w >> 24)};
         else return w;
     };
 
-    pair_t pre[NLD], pre2[PF2 ? NLD : 1];
-    // PF2 reads the stream through a buffer descriptor of the wave's own run, [head of sub-tile 0, end of sub-tile nsub - 1): a request
-    // for a sub-tile behind the run's last one (the last two steps of a run ask for them) lies past num_records and returns zeros
-    // WITHOUT a memory access, so every step requests unconditionally and the number of loads in flight at every wait is a
-    // compile-time fact (a request under a condition makes the compiler wait for ALL loads at the next use, i.e. also for the
-    // request it issued a sub-tile ago -- which is the whole point of the second set)
-    __amdgpu_buffer_rsrc_t rs;
-    if constexpr (PF2) {
-        static_assert(!PF2 || !IN_U8, "PF2: cf32 input");
-        rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(x + b0 * 1024 * (long)D), 0, (int)((HALO + nsub * SUB_NEW) * 8), 0x00020000);
+    constexpr bool HOIST = (REDIO_EXP_SEAM & 1) != 0, BUF = PF2 || (REDIO_EXP_SEAM & 2) != 0, EARLY = (REDIO_EXP_SEAM & 4) != 0,
+                   PRO = (REDIO_EXP_SEAM & 8) != 0;
+    // image slot (16-byte units) of sample pair p.  Two facts about it make a wave's slots few:
+    //   the halo's source is its destination HALO_DELTA slots on (SUB_NEW / 2 pairs are a whole number of lane strides), and
+    //   park slots i and i + PER are PARK_STEP apart (so are 64 PER pairs): NLD stores share PER address registers, the rest is immediates.
+    auto slot = [](int p) { return G::lds_index(2 * p) / 2; };
+    constexpr int HSTR = G::LSTR / 2; // pairs per lane stride
+    static_assert((SUB_NEW / 2) % HSTR == 0, "a sub-tile is a whole number of lane strides");
+    constexpr int HALO_DELTA = G::lds_index(SUB_NEW) / 2;
+    constexpr int PER0 = G::PADN == 0 ? 1 : HSTR / chain_gcd(64, HSTR), PER = PER0 < NLD ? PER0 : NLD;
+    constexpr int PARK_STEP = G::lds_index(2 * 64 * PER) / 2;
+    static_assert(PER == NLD || (64 * PER) % HSTR == 0, "park slots repeat with period PER");
+    // HOIST: lane-constant for the life of the wave.  The halo move is branch-free (EARLY): the lanes behind the halo move a pair of
+    // NEW samples onto itself, harmless because the park that follows writes that slot again (one wave's LDS operations execute in
+    // issue order, fft_wave.h wave_lds_fence) -- no slot outside the image is needed.
+    auto halo_slots = [&](int lf, int &src, int &dst) {
+        dst = slot(lf);
+        if constexpr (EARLY) src = dst + (lf < HALO_V ? HALO_DELTA : 0);
+        else src = slot(SUB_NEW / 2 + lf);
+    };
+    [[maybe_unused]] int park4[PER], hsrc4 = 0, hdst4 = 0;
+    if constexpr (HOIST) {
+        static_for4<PER>([&](auto I) { park4[I.value] = slot(HALO_V + lane + 64 * I.value); });
+        halo_slots(lane, hsrc4, hdst4);
     }
+
+    pair_t pre[NLD], pre2[PF2 ? NLD : 1];
+    // BUF: the stream is read, and the output written, through buffer descriptors of the wave's own run -- input [head of sub-tile 0,
+    // end of sub-tile nsub - 1), output its b1 - b0 blocks.  An access is descriptor base + scalar offset + (lane offset + immediate):
+    // the wave-uniform part lives in scalar registers and the lane part is ONE constant register, so the loop has no vector address
+    // arithmetic.  The scalar offset is NOT range-checked, so nothing here relies on the check: every request lies inside the run.
+    // PF2 keeps the sub-tile's offset in the lane part, which IS checked: a request for a sub-tile behind the run's last one (the last two
+    // steps of a run ask for them) lies past num_records and returns zeros WITHOUT a memory access, so every PF2 step requests
+    // unconditionally and the number of loads in flight at every wait is a compile-time fact (a request under a condition makes the
+    // compiler wait for ALL loads at the next use, i.e. also for the request it issued a sub-tile ago -- the whole point of the second set)
+    constexpr unsigned PB = sizeof(pair_t);                        // bytes of a pair in the stream
+    constexpr int NT_LD = (REDIO_EXP_CHAIN_NT & 1) ? 2 : 0, NT_ST = (REDIO_EXP_CHAIN_NT & 2) ? 2 : 0; // the buffer forms' cache-policy operand: nt
+    typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
+    typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t ri, ro;
+    if constexpr (BUF) {
+        static_assert(!PF2 || !IN_U8, "PF2: cf32 input");
+        const char *xb = reinterpret_cast<const char *>(x) + b0 * (512 * (long)D) * PB;
+        ri = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(xb), 0, (int)((HALO_V + nsub * (SUB_NEW / 2)) * PB), 0x00020000);
+        ro = __builtin_amdgcn_make_buffer_rsrc(out + b0 * 1024, 0, (int)((b1 - b0) * 8192), 0x00020000);
+    }
+    [[maybe_unused]] auto buf_load = [&](unsigned vo, unsigned so, auto policy) -> pair_t {
+        if constexpr (IN_U8) return __builtin_amdgcn_raw_buffer_load_b32(ri, vo, so, decltype(policy)::value);
+        else return __builtin_bit_cast(v4f_t, __builtin_amdgcn_raw_buffer_load_b128(ri, vo, so, decltype(policy)::value));
+    };
     auto fetch_to = [&](pair_t(&dst)[NLD], long j) { // new samples of sub-tile j: [HALO + j*SUB_NEW, HALO + (j+1)*SUB_NEW)
-        if constexpr (PF2) {
-            typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
-            const unsigned vo = 16u * (unsigned)lane + (unsigned)((HALO + j * SUB_NEW) * 8);
+        if constexpr (BUF) {
+            const unsigned sub = (unsigned)((HALO_V + j * (SUB_NEW / 2)) * PB); // wave-uniform
+            const unsigned vo = PB * (unsigned)lane + (PF2 ? sub : 0u), so = PF2 ? 0u : sub;
             static_for4<NLD>([&](auto I) {
-                constexpr int k = I.value;
-                const v4u_t w = __builtin_amdgcn_raw_buffer_load_b128(rs, vo + 1024u * (k & 3), 4096 * (k >> 2), 2 /* nt */);
-                dst[k] = __builtin_bit_cast(v4f_t, w);
+                constexpr unsigned off = 64u * PB * I.value, imm = off % 4096u; // load k: an immediate below 4096 and a scalar multiple of it
+                dst[I.value] = buf_load(vo + imm, so + (off - imm), std::integral_constant<int, NT_LD>{});
+                // in ascending address order, as the parent's loads went out: left alone the scheduler groups them by scalar offset, two
+                // loads that share a 128-byte line are then no longer neighbours, and FETCH_SIZE rises by 0.6 % (r12_chain_seam.txt)
+                if constexpr (!PF2) __builtin_amdgcn_sched_barrier(0);
             });
         } else {
             const pair_t *src = src0 + HALO_V + j * (SUB_NEW / 2);
@@ -123,36 +175,120 @@ __device__ __forceinline__ void chain_v4_body(const float2 *__restrict__ x, cons
 #pragma unroll
         for (int i = 0; i < NLD; ++i) { pair_t keep = from[i]; asm volatile("" : : "v"(keep)); }
 #else
-        static_for4<NLD>([&](auto I) { xs4[G::lds_index(HALO + 2 * (lane + 64 * I.value)) / 2] = samples(from[I.value]); });
+        static_for4<NLD>([&](auto I) {
+            constexpr int i = I.value;
+            if constexpr (HOIST) xs4[park4[i % PER] + (i / PER) * PARK_STEP] = samples(from[i]);
+            else xs4[G::lds_index(HALO + 2 * (lane + 64 * i)) / 2] = samples(from[i]);
+        });
 #endif
     };
+    // a block's spectrum, a[k1 + 4 k0] = X[ln + 64 k1 + 256 k0] (fft1kn_store_spectrum's order); blk: the block's place in the run
+    [[maybe_unused]] auto store_block = [&](const float2(&a)[16], long blk, int ln) {
+        if constexpr (BUF) {
+            const unsigned so = (unsigned)(blk * 8192); // wave-uniform
+            static_for4<16>([&](auto I) {
+                constexpr unsigned k0 = I.value / 4, k1 = I.value % 4;
+                const float2 v = a[k1 + 4 * k0];
+                __builtin_amdgcn_raw_buffer_store_b64(v2u_t{__builtin_bit_cast(unsigned, v.x), __builtin_bit_cast(unsigned, v.y)}, ro,
+                                                      8u * (unsigned)ln + (512u * k1 + 2048u * (k0 & 1)), so + 4096u * (k0 >> 1), NT_ST);
+            });
+        } else fft1kn_store_spectrum(a, out + (b0 + blk) * 1024, ln);
+    };
 
-    // prologue: the head (the only halo this wave ever fetches) and the first sub-tile
-    if (lane < HALO_V) xs4[G::lds_index(2 * lane) / 2] = samples(src0[0]);
-    // PF2: the 60 twiddles of the transform's middle stages (Fft1knTw12: 15 per lane, 4 distinct sets by lane >> 4) sit in LDS behind the
+    // PF2, SCH 1, 2: the 60 twiddles of the transform's middle stages (Fft1knTw12: 15 per lane, 4 distinct sets by lane >> 4) sit in LDS behind the
     // image for the life of the wave, so the transform issues NO global load: its twiddle loads would queue behind the sub-tile request
     // (loads return in order) and make the transform wait for it
     static_assert(SCH == 0 || (!PF2 && !FIR_ONLY && TWP && WPS == 2), "the block schedules: the transforming product forms");
     constexpr int EXH_OFF = G::lds_elems(SUB_OUT) > FFT1KN_LDS ? G::lds_elems(SUB_OUT) : FFT1KN_LDS; // SCH 2: the half exchanges, behind image and one-piece exchange
     constexpr int T12_OFF = EXH_OFF + (SCH == 2 ? FFT1KN_HALF_LDS : 0);
-    static_assert(SCH == 0 || (T12_OFF + 60) * sizeof(float2) <= 160 * 1024 / 8 - 480, "within the request of chain_v4_lds at two waves per SIMD");
-    if constexpr ((PF2 || SCH != 0) && !FIR_ONLY) {
-        if (lane < 60) {
-            const int k4 = lane / 15, i = lane % 15;
-            const int idx = i < 3 ? 64 * k4 * (i + 1) : 16 * (k4 + 4 * ((i - 3) / 3)) * ((i - 3) % 3 + 1);
-            ex[T12_OFF + lane] = tw[idx];
-        }
-    }
-    fetch_to(pre, 0);
-    park_from(pre);
-    wave_lds_fence();
-
-    float2 a[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) a[i] = make_float2(0.f, 0.f);
+    constexpr bool TABLE = (PF2 || SCH != 0) && !FIR_ONLY;
+    // (64 entries: the PRO prologue stores with all lanes, the last four land in a pad behind the table; PF2's request has room for them too)
+    static_assert(!TABLE || (T12_OFF + 64) * sizeof(float2) <= 160 * 1024 / 8 - 480, "within the request of chain_v4_lds at two waves per SIMD");
+    auto table_index = [](int l) { // of the table's entry l in tw
+        const int k4 = l / 15, i = l % 15;
+        return i < 3 ? 64 * k4 * (i + 1) : 16 * (k4 + 4 * ((i - 3) / 3)) * ((i - 3) % 3 + 1);
+    };
     // the 15 lane-dependent twiddles of the last two stages stay in registers for the life of the wave
     Fft1knTw34 t34;
-    if (!FIR_ONLY && TWP) fft1kn_load_tw34(t34, lane, tw);
+    // SCH 1, 2: tw[0] (the first stage's unit twiddle) in two registers and the middle-stage twiddles from the LDS table, so that a block's
+    // transform issues no global load
+    [[maybe_unused]] float2 one = make_float2(0.f, 0.f);
+    // prologue: the head (the only halo this wave ever fetches), the first sub-tile, the twiddles
+    if constexpr (PRO) {
+        // Every request before the first wait, the stream's first: one memory latency, not one each for head, table and sub-tile.
+        // All 64 lanes fetch and store a head pair: the lanes behind the halo hold the first NEW pairs, which the park writes again.
+        pair_t head;
+        if constexpr (BUF) head = buf_load(PB * (unsigned)lane, 0u, std::integral_constant<int, 0>{});
+        else head = src0[0];
+        fetch_to(pre, 0);
+        [[maybe_unused]] float2 twv = make_float2(0.f, 0.f);
+        if constexpr (TABLE) twv = tw[table_index(lane < 60 ? lane : 0)];
+        if (!FIR_ONLY && TWP) fft1kn_load_tw34(t34, lane, tw);
+        if constexpr (SCH != 0) one = tw[0];
+        xs4[slot(lane)] = samples(head);
+        if constexpr (TABLE) ex[T12_OFF + lane] = twv; // all lanes: under a lane mask the compiler moves the load into the masked block, behind a wait of its own
+        park_from(pre);
+        wave_lds_fence();
+    } else {
+        if (lane < HALO_V) {
+            if constexpr (BUF) xs4[slot(lane)] = samples(buf_load(PB * (unsigned)lane, 0u, std::integral_constant<int, 0>{}));
+            else xs4[slot(lane)] = samples(src0[0]);
+        }
+        if constexpr (TABLE)
+            if (lane < 60) ex[T12_OFF + lane] = tw[table_index(lane)];
+        fetch_to(pre, 0);
+        park_from(pre);
+        wave_lds_fence();
+        if (!FIR_ONLY && TWP) fft1kn_load_tw34(t34, lane, tw);
+        if constexpr (SCH != 0) one = tw[0];
+    }
+    if constexpr (SCH != 0) asm volatile("" : "+v"(one.x), "+v"(one.y));
+
+    // the block in the transform's operand layout; SCH 1 writes all of it before its first transform, the sub-tile loops shift it in
+    float2 a[16];
+    if constexpr (!(PRO && SCH == 1)) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a[i] = make_float2(0.f, 0.f);
+    }
+    // one sub-tile: request sub-tile j + AHEAD into `req`, FIR of the image, transform when a block is complete,
+    // then park `parked` (= sub-tile j + 1, requested AHEAD - 1 sub-tiles ago; for AHEAD == 1 it is `req` itself) into the image.
+    // S: the sub-tile's place in its block when that is a compile-time fact (PF2: the loop below is unrolled by a whole block, the
+    // transform sits in step 3 unconditionally, and so do the request, the halo move and the park), -1 when it is not.
+    // The seam of a step: the FIR of the image and the move of the image's last HALO samples, the next image's first.
+    //   EARLY: the halo is read under the FIR's last chunk (fir_core.h's per-chunk hook), so it has long arrived when the window's last
+    //          multiply-add has; its write goes out behind the last window read with nothing to wait for, all 64 lanes (halo_slots).
+    //   else:  read behind the window under the lane mask, waited for, written under the mask (the parent's form).
+    // !HOIST: the slots are recomputed every step from an opaque copy of the lane (the parent's form: out of the loop's live set).
+    constexpr int NCH = fir_num_chunks<K, D, R, CH>();
+    struct Seam { int lf, hs, hd; v4f_t halo; };
+    auto fir = [&](Seam &s, float2(&acc)[R], auto &&hook) {
+        s.lf = lane, s.hs = hsrc4, s.hd = hdst4, s.halo = v4f_t{0.f, 0.f, 0.f, 0.f};
+        if constexpr (!HOIST) {
+            asm volatile("" : "+v"(s.lf));
+            if constexpr (EARLY) halo_slots(s.lf, s.hs, s.hd);
+        }
+        auto hk = [&](auto C) {
+            if constexpr (EARLY && decltype(C)::value == NCH - 1) s.halo = xs4[s.hs];
+            hook(C);
+        };
+        if constexpr (RES) fir_lane_v_res<K, D, R, FUSED, CH>(xs4, s.lf, rtaps, acc, hk);
+        else fir_lane_v<K, D, R, FUSED, CH>(xs4, s.lf, taps, acc, hk);
+    };
+    auto halo_read = [&](Seam &s, bool more) { // behind the fence that ends the window reads
+        if constexpr (!EARLY) {
+            if constexpr (!HOIST) halo_slots(s.lf, s.hs, s.hd);
+            if (more && s.lf < HALO_V) s.halo = xs4[s.hs];
+        }
+    };
+    auto halo_write = [&](const Seam &s) {
+        if constexpr (EARLY) xs4[s.hd] = s.halo;
+        else if (s.lf < HALO_V) xs4[HOIST ? s.hd : slot(s.lf)] = s.halo;
+    };
+    auto transform_lane = [&]() { // !HOIST: opaque per transform, so that the exchanges' address arithmetic stays out of the live set
+        int ln = lane;
+        if constexpr (!HOIST) asm volatile("" : "+v"(ln));
+        return ln;
+    };
     // one sub-tile: request sub-tile j + AHEAD into `req`, FIR of the image, transform when a block is complete,
     // then park `parked` (= sub-tile j + 1, requested AHEAD - 1 sub-tiles ago; for AHEAD == 1 it is `req` itself) into the image.
     // S: the sub-tile's place in its block when that is a compile-time fact (PF2: the loop below is unrolled by a whole block, the
@@ -164,14 +300,19 @@ __device__ __forceinline__ void chain_v4_body(const float2 *__restrict__ x, cons
         float2 acc[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = make_float2(0.f, 0.f);
-        int lf = lane; // opaque per sub-tile: keeps LDS address arithmetic out of the loop's live set
-        asm volatile("" : "+v"(lf));
-        if constexpr (RES) fir_lane_v_res<K, D, R, FUSED, CH>(xs4, lf, rtaps, acc);
-        else fir_lane_v<K, D, R, FUSED, CH>(xs4, lf, taps, acc);
+        Seam seam;
+        fir(seam, acc, FirNoHook{});
         if (FIR_ONLY) { // 32 contiguous bytes per lane, 2 KiB per wave
-            v4f_t *y4 = reinterpret_cast<v4f_t *>(out + (b0 * 4 + j) * SUB_OUT) + 2 * lane;
-            y4[0] = v4f_t{acc[0].x, acc[0].y, acc[1].x, acc[1].y};
-            y4[1] = v4f_t{acc[2].x, acc[2].y, acc[3].x, acc[3].y};
+            const v4f_t y0 = v4f_t{acc[0].x, acc[0].y, acc[1].x, acc[1].y}, y1 = v4f_t{acc[2].x, acc[2].y, acc[3].x, acc[3].y};
+            if constexpr (BUF) {
+                const unsigned so = (unsigned)(j * (SUB_OUT * 8)); // wave-uniform
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_t, y0), ro, 32u * (unsigned)lane, so, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_t, y1), ro, 32u * (unsigned)lane + 16u, so, 0);
+            } else {
+                v4f_t *y4 = reinterpret_cast<v4f_t *>(out + (b0 * 4 + j) * SUB_OUT) + 2 * lane;
+                y4[0] = y0;
+                y4[1] = y1;
+            }
         } else {
 #pragma unroll
             for (int i = 0; i < 12; ++i) a[i] = a[i + 4];
@@ -179,13 +320,10 @@ __device__ __forceinline__ void chain_v4_body(const float2 *__restrict__ x, cons
             for (int r = 0; r < R; ++r) a[12 + r] = acc[r];
         }
         wave_lds_fence(); // window reads done
-        // the last HALO samples of this image are the first HALO samples of the next one
-        v4f_t halo = v4f_t{0.f, 0.f, 0.f, 0.f};
-        if (more && lf < HALO_V) halo = xs4[G::lds_index(SUB_NEW + 2 * lf) / 2];
+        halo_read(seam, more);
         if (!FIR_ONLY && (S == 3 || (S < 0 && (j & 3) == 3))) { // a block is complete in registers: transform it, the image is scratch meanwhile
             wave_lds_fence();
-            int ln = lane;
-            asm volatile("" : "+v"(ln));
+            const int ln = transform_lane();
             Fft1knTw12 t12;
             if constexpr (PF2) {
                 const float2 *T = ex + T12_OFF + 15 * (ln >> 4);
@@ -195,22 +333,16 @@ __device__ __forceinline__ void chain_v4_body(const float2 *__restrict__ x, cons
                 for (int i = 0; i < 12; ++i) t12.b[i] = T[3 + i];
             } else fft1kn_load_tw12(t12, ln, tw);
             if (!TWP) fft1kn_load_tw34(t34, ln, tw);
-            fft1kn_wave_tw<false>(a, ex, tw, t12, t34, out + (b0 + (j >> 2)) * 1024, ln);
+            fft1kn_wave_regs<false>(a, ex, tw, t12, t34, ln);
+            store_block(a, j >> 2, ln);
             wave_lds_fence();
         }
         if (more) {
-            if (lf < HALO_V) xs4[G::lds_index(2 * lf) / 2] = halo;
+            halo_write(seam);
             park_from(parked);
         }
         wave_lds_fence();
     };
-    // SCH 1, 2: tw[0] (the first stage's unit twiddle) in two registers and the middle-stage twiddles from the LDS table, so that a block's
-    // transform issues no global load
-    [[maybe_unused]] float2 one = make_float2(0.f, 0.f);
-    if constexpr (SCH != 0) {
-        one = tw[0];
-        asm volatile("" : "+v"(one.x), "+v"(one.y));
-    }
     [[maybe_unused]] auto t12_lds = [&](Fft1knTw12 &t12, int ln) {
         const float2 *T = ex + T12_OFF + 15 * (ln >> 4);
 #pragma unroll
@@ -227,27 +359,24 @@ __device__ __forceinline__ void chain_v4_body(const float2 *__restrict__ x, cons
         float2 acc[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = make_float2(0.f, 0.f);
-        int lf = lane; // opaque per sub-tile: keeps LDS address arithmetic out of the loop's live set
-        asm volatile("" : "+v"(lf));
-        if constexpr (RES) fir_lane_v_res<K, D, R, FUSED, CH>(xs4, lf, rtaps, acc, hook);
-        else fir_lane_v<K, D, R, FUSED, CH>(xs4, lf, taps, acc, hook);
+        Seam seam;
+        fir(seam, acc, hook);
 #pragma unroll
         for (int r = 0; r < R; ++r) a[4 * S + r] = acc[r];
         wave_lds_fence(); // window reads done
-        v4f_t halo = v4f_t{0.f, 0.f, 0.f, 0.f};
-        if (more && lf < HALO_V) halo = xs4[G::lds_index(SUB_NEW + 2 * lf) / 2];
+        halo_read(seam, more);
         if (xform) {
             wave_lds_fence();
-            int ln = lane;
-            asm volatile("" : "+v"(ln));
+            const int ln = transform_lane();
             Fft1knTw12 t12;
             t12_lds(t12, ln);
             const float2 one1[1] = {one};
-            fft1kn_wave_tw<false>(a, ex, one1, t12, t34, out + (b0 + (j >> 2)) * 1024, ln);
+            fft1kn_wave_regs<false>(a, ex, one1, t12, t34, ln);
+            store_block(a, j >> 2, ln);
             wave_lds_fence();
         }
         if (more) {
-            if (lf < HALO_V) xs4[G::lds_index(2 * lf) / 2] = halo;
+            halo_write(seam);
             park_from(pre);
         }
         wave_lds_fence();
@@ -266,7 +395,6 @@ __device__ __forceinline__ void chain_v4_body(const float2 *__restrict__ x, cons
             sstep(4 * blk + 3, S3{}, blk + 1 < nb, true, FirNoHook{});
         }
     } else if constexpr (SCH == 2) {
-        constexpr int NCH = fir_num_chunks<K, D, R, CH>();
         const long nb = b1 - b0;
         sstep(0, S0{}, true, false, FirNoHook{});
 #pragma unroll 1

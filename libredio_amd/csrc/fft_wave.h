@@ -93,9 +93,10 @@ __device__ __forceinline__ void fft1kn_store_spectrum(const float2 (&a)[16], flo
 // The "native" 1024-point forward transform of fft_core.h by the calling wavefront: a[4 s + r] holds
 // y[256 s + 4 lane + r] on entry (the FIR's own register layout), ex is FFT1KN_LDS float2 of LDS owned
 // by this wave, dst the block's spectrum in global memory (natural order).
+// fft1kn_wave_regs: everything but the store -- on return a[k1 + 4 k0] = X[ln + 64 k1 + 256 k0] (the caller stores it its own way).
 template <bool INV>
-__device__ __forceinline__ void fft1kn_wave_tw(float2 (&a)[16], float2 *ex, const float2 *__restrict__ tw, const Fft1knTw12 &t12,
-                                               const Fft1knTw34 &t34, float2 *dst, int ln)
+__device__ __forceinline__ void fft1kn_wave_regs(float2 (&a)[16], float2 *ex, const float2 *__restrict__ tw, const Fft1knTw12 &t12,
+                                                 const Fft1knTw34 &t34, int ln)
 {
     fft1kn_stage0<INV>(a, tw);
 #pragma unroll
@@ -116,6 +117,12 @@ __device__ __forceinline__ void fft1kn_wave_tw(float2 (&a)[16], float2 *ex, cons
     for (int f = 0; f < 16; ++f) a[f] = ex[fft1kn_x2_load(ln, f)];
     wave_lds_fence();
     fft1kn_pass34<INV>(a, t34);
+}
+template <bool INV>
+__device__ __forceinline__ void fft1kn_wave_tw(float2 (&a)[16], float2 *ex, const float2 *__restrict__ tw, const Fft1knTw12 &t12,
+                                               const Fft1knTw34 &t34, float2 *dst, int ln)
+{
+    fft1kn_wave_regs<INV>(a, ex, tw, t12, t34, ln);
     fft1kn_store_spectrum(a, dst, ln);
 }
 

@@ -204,13 +204,22 @@ struct FirTapsResident {
 struct FirNoResidentTaps {}; // what an any-taps kernel carries in that place: nothing
 
 // h: 8-byte aligned, wave-uniform.  Device: each pair is made opaque in a scalar register pair, so it is neither
-// re-fetched nor rebuilt inside the loop.
+// re-fetched nor rebuilt inside the loop.  All pairs are requested before the first is made opaque: naming a pair waits for it,
+// and a wait per pair is NP scalar-cache latencies in a row at the head of every wave instead of one.
 template <int K, typename TapPtr>
 RD_HD void fir_taps_resident_load(FirTapsResident<K> &t, TapPtr h)
 {
+#if defined(__HIP_DEVICE_COMPILE__) && !(defined(REDIO_EXP_SEAM) && !(REDIO_EXP_SEAM & 8))
+    fir_static_for<FirTapsResident<K>::NP>([&](auto I) {
+        typedef unsigned long long u64a __attribute__((may_alias));
+        t.p[I.value] = reinterpret_cast<const u64a *>(&h[0])[I.value];
+    });
+#pragma unroll
+    for (int i = 0; i < FirTapsResident<K>::NP; ++i) asm volatile("" : "+s"(t.p[i]));
+#else
     fir_static_for<FirTapsResident<K>::NP>([&](auto I) {
         constexpr int i = I.value;
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) // the measurement build's parent form (REDIO_EXP_SEAM without bit 3): a wait per pair
         typedef unsigned long long u64a __attribute__((may_alias));
         t.p[i] = reinterpret_cast<const u64a *>(&h[0])[i];
         asm volatile("" : "+s"(t.p[i]));
@@ -222,6 +231,7 @@ RD_HD void fir_taps_resident_load(FirTapsResident<K> &t, TapPtr h)
         t.p[i] = (unsigned long long)lo | ((unsigned long long)hi << 32);
 #endif
     });
+#endif
 }
 
 // live outputs of window sample m: r in [r_lo(m), r_hi(m)], tap j = m - r*D in [0, K)
