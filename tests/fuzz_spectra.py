@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Randomised differential run of the real-input and spectrum plans against their bit-exact restatements (tests/fftr_ref.py,
-ovsave_real_ref.py, pspec_ref.py, pspec_real_ref.py), beyond the fixed shapes of their own test files: the sibling of tests/fuzz_parity.py for
-redio_fftr_*, redio_ovsave_real_*, redio_pspec_* (cf32 and u8), redio_pspec_real_* and their streams.
+ovsave_real_ref.py, pspec_ref.py, pspec_real_ref.py, pfb_pspec_ref.py), beyond the fixed shapes of their own test files: the sibling of
+tests/fuzz_parity.py for redio_fftr_*, redio_ovsave_real_*, redio_pspec_* (cf32 and u8), redio_pspec_real_* and their streams, and for the
+polyphase spectrometer redio_pfb_pspec_* (cf32 and u8, fused and generic) and its streams.
 
     python tests/fuzz_spectra.py [seconds] [seed] [--only FAMILY]     FAMILY: fftr ovsave_real pspec pspec_u8 pspec_real streams
+                                                                              pfb_pspec pfb_streams
     python tests/fuzz_spectra.py --draw COUNT [seed] [--only FAMILY]  the cases a run would draw, one JSON line each; needs no GPU
 
 A run first draws OPENING cases of every family, whatever the clock says, then draws families at random until the budget ends.  Plans are
@@ -25,7 +27,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
-FAMILIES = ["fftr", "ovsave_real", "pspec", "pspec_u8", "pspec_real", "streams"]
+FAMILIES = ["fftr", "ovsave_real", "pspec", "pspec_u8", "pspec_real", "streams", "pfb_pspec", "pfb_streams"]
 OPENING = 24           # cases per family before the clock is consulted
 POINTS = 1 << 18       # transforms per case times N, at most (the large staging sizes excepted: one or two transforms)
 WORK = 1 << 25         # the same times the largest prime factor: the restatement's generic-radix stage costs that much
@@ -35,6 +37,10 @@ ERR_ARG = -1
 ROUGH_EVEN = [14, 22, 34, 94, 442, 614, 2002, 1994, 3758, 5042, 7978]          # 2 x prime and the like
 ODD_SIZES = [1, 3, 5, 7, 11, 13, 17, 97, 127, 251, 509, 1021, 1000, 96, 625, 3125, 2187, 1215]
 STAGING = {"pspec": (65536, 8194), "pspec_u8": (65536, 8194), "pspec_real": (131072,), "fftr": (16388, 65536)}
+PFB_M = 64                                # the polyphase spectrometer's one-kernel channel count, with PFB_TAPS taps per branch
+PFB_TAPS = (4, 8, 16)
+PFB_ONE_KERNEL = (32, 128, 256, 512, 1024)   # channel counts the inner channelizer runs as one kernel (with PFB_TAPS), not as two passes
+PFB_SPLIT_WAVES = 1024                    # PFBSPEC_SPLIT_WAVES: auto lets a wave own whole rows from this many waves of ceil(64 / K) rows
 
 
 def largest_prime_factor(n):
@@ -255,6 +261,61 @@ class Gen:
                  spice=0 if kind == "pspec_u8" else self.spiced(), route=route)
         return c
 
+    # -- the polyphase spectrometer --
+    def _pfb_shape(self, stream=False):
+        # half of the shapes have 64 channels and four calls in five name their split mode: with K > 16 on about 0.58 of the shapes and the
+        # fused taps on 0.79, less would leave "fused, K > 16, mode 1" (and mode 2) under 1 % of a run's cases.  Auto, at the row
+        # counts of this tool, is the route of mode 2 (its threshold is test_gpu_pfb_pspec_launch.py's).
+        M = PFB_M if self.p(0.5) else self.pick([32, 128, 256, 512, 1024, 100, 7, 48, self.i(1, 300)])
+        P = self.pick([4, 8, 16, self.i(1, 20)])
+        K = min(self.pick([1, 2, 15, 16, 17, 31, 32, 33, 40, self.i(1, 71)]), transforms_allowed(M))
+        while stream and K > 1 and 3 * (K - 1 + P) + K + 1 > transforms_allowed(M):   # a piece longer than two windows stays within the bound
+            K //= 2
+        taps = "lpf" if M * P >= 3 and self.p(0.5) else "synth"
+        return {"M": M, "P": P, "K": K, "fir_fused": self.p(0.5), "taps": taps, "tseed": self.seed()}
+
+    def pfb_pspec(self):
+        c = self.shape_again("pfb_pspec", self._pfb_shape)
+        M, P, K = c["M"], c["P"], c["K"]
+        W, H = (K - 1 + P) * M, K * M
+        fused = M == PFB_M and P in PFB_TAPS
+        rows = self.i(0, 3 * -(-64 // K) + 3) if fused else self.i(0, 6)   # fused: several wavefronts of ceil(64 / K) rows and a short last one
+        rows = min(rows, transforms_allowed(M) // K)
+        n = W + (rows - 1) * H + self.i(0, H) if rows else self.i(0, W)
+        c.update(family="pfb_pspec", rows=rows, n=n, mode=self.pick([0, 1, 1, 2, 2]), base=2 * self.i(0, 8), cbase=8 * self.i(0, 2), u8_first=self.p(0.5),
+                 seed=self.seed(), spice=self.spiced())
+        c["route"] = pfb_route(c)
+        return c
+
+    def pfb_streams(self):
+        c = self.shape_again("pfb_streams", lambda: self._pfb_shape(stream=True))
+        M, P, K = c["M"], c["P"], c["K"]
+        W, H = (K - 1 + P) * M, K * M
+        most = max(transforms_allowed(M) * M, 3 * W + H)
+        u8 = self.p(0.5)
+        # the pieces, by the rule of `streams`: zero-length, shorter than a window, longer than two, anything (H <= W: no skipped gap)
+        pieces, pos = [], 0
+        for _ in range(self.i(1, 9)):
+            r = self.rng.random()
+            if r < 0.15:
+                ln = 0
+            elif r < 0.45:
+                ln = self.i(0, W)
+            elif r < 0.65:
+                ln = self.i(2 * W + 1, 3 * W + 2)
+            else:
+                ln = self.i(0, 2 * W + H)
+            ln = min(ln, most - pos)
+            pieces.append(ln)
+            pos += ln
+        again = sorted(self.i(0, pos + 1) for _ in range(self.i(0, 8))) if self.p(0.5) else None
+        route = {k: v for k, v in pfb_route(dict(c, rows=1, mode=0, base=0, cbase=0)).items() if k not in ("mode", "split", "base", "cbase")}
+        route.update(u8=u8, zero_piece=0 in pieces, short_piece=any(0 < v < W for v in pieces), long_piece=any(v > 2 * W for v in pieces),
+                     odd_piece=any(v % 2 for v in pieces), reset=again is not None)
+        c.update(family="pfb_streams", u8=u8, pieces=pieces, again=again, rows=int(pos), seed=self.seed(), spice=0 if u8 else self.spiced(),
+                 route=route)
+        return c
+
     def draw(self, fam):
         return getattr(self, fam)()
 
@@ -269,6 +330,16 @@ def pspec_route(fam, c):
     return {"fused": fused, "packs": c["window"] != "none" or step != N, "segments2": S >= 2, "mode": c["mode"], "split": bool(split),
             "H>W": step > N, "odd_step": step % 2 == 1, "fft_u8": N if fam == "pspec_u8" and N in (2048, 4096) else 0,
             "staging": N if N in STAGING.get(fam, ()) else 0}
+
+
+def pfb_route(c):
+    """the polyphase spectrometer's route for this call, from the documented rules (include/redio.h)"""
+    M, P, K = c["M"], c["P"], c["K"]
+    fused = M == PFB_M and P in PFB_TAPS
+    one_kernel = M in PFB_ONE_KERNEL and P in PFB_TAPS
+    split = K > SEG and (not fused or c["mode"] == 2 or (c["mode"] == 0 and c["rows"] < PFB_SPLIT_WAVES * -(-64 // K)))
+    return {"fused": fused, "one_kernel": one_kernel, "two_pass": not fused and not one_kernel, "m64_generic": M == PFB_M and not fused,
+            "segments2": K > SEG, "mode": c["mode"], "split": bool(split), "fir_fused": c["fir_fused"], "base": c["base"], "cbase": c["cbase"]}
 
 
 def sequence(gen, only):
@@ -357,6 +428,18 @@ def case_input(O, c, spiced=True):
     return spice((O.synth_iq if fam == "pspec" else O.synth_f32)(c["seed"], 0, max(n, 1))[:n], sp)
 
 
+def pfb_taps_of(O, c):
+    return O.lpf_corrected(c["M"] * c["P"], 0.45 / c["M"]) if c["taps"] == "lpf" else O.synth_f32(c["tseed"], 0, c["M"] * c["P"])
+
+
+def pfb_input(O, c, u8, spiced=True):
+    """a polyphase case's input: cf32 samples (spiced where the case says so) or the raw I/Q bytes; a stream case has `rows` samples"""
+    n = c["rows"] if c["family"] == "pfb_streams" else c["n"]
+    if u8:
+        return np.random.default_rng(c["seed"]).integers(0, 256, 2 * n, dtype=np.uint8)
+    return spice(O.synth_iq(c["seed"], 0, max(n, 1))[:n], c["spice"] if spiced else 0)
+
+
 def samples_of(O, raw):
     return O.data_to_samples(raw) if len(raw) else np.zeros(0, np.complex64)
 
@@ -366,9 +449,10 @@ class Runner:
         import torch
         import libredio_amd as R
         import oracle as O
-        import fftr_ref, ovsave_real_ref, pspec_ref, pspec_real_ref
+        import fftr_ref, ovsave_real_ref, pspec_ref, pspec_real_ref, pfb_pspec_ref
         self.t, self.R, self.O = torch, R, O
         self.fftr_ref, self.ovsave_real_ref, self.pspec_ref, self.pspec_real_ref = fftr_ref, ovsave_real_ref, pspec_ref, pspec_real_ref
+        self.pfb_pspec_ref = pfb_pspec_ref
         self.plans = {}
 
     def plan(self, key, make):
@@ -531,6 +615,85 @@ class Runner:
             if which == "after reset":
                 st.reset()
             outs = [st(dx[per * int(lo): per * int(hi)]).clone() for lo, hi in zip(cuts[:-1], cuts[1:])]
+            got = t.cat(outs).cpu().numpy() if outs else np.zeros(0, np.float32)
+            if not same_nan(got, want):
+                return False, which
+        return True, ""
+
+    # -- the polyphase spectrometer --
+    def pfb_plan(self, c):
+        key = ("PolyphaseSpectrum", c["M"], c["P"], c["K"], c["fir_fused"], c["taps"], c["tseed"] if c["taps"] == "synth" else 0)
+        return self.plan(key, lambda: self.R.PolyphaseSpectrum(pfb_taps_of(self.O, c), c["M"], c["P"], c["K"], fused=c["fir_fused"]))
+
+    def pfb_pspec(self, c):
+        ref, M, P, K, ff = self.pfb_pspec_ref, c["M"], c["P"], c["K"], c["fir_fused"]
+        h = pfb_taps_of(self.O, c)
+        x, raw = pfb_input(self.O, c, False), pfb_input(self.O, c, True)
+        want, want8 = ref.spectrum(x, h, M, P, K, ff), ref.spectrum_u8(raw, h, M, P, K, ff)
+        T = c["n"] // M
+        rows = 0 if T < P + K - 1 else (T - P + 1) // K     # redio.h: nrows = (T - P + 1) / K, 0 when T < P + K - 1
+        plan = self.pfb_plan(c)
+        plan.set_split(c["mode"])
+        if not (plan.nrows(c["n"]) == rows == len(want) == len(want8) == c["rows"]) or plan.is_fused != c["route"]["fused"]:
+            return False, ("nrows / is_fused", plan.nrows(c["n"]), rows, len(want), plan.is_fused)
+        dx = self.dev(x, c["cbase"])
+        assert dx.data_ptr() % 16 == c["cbase"]
+        out = self.nans(want.size + 8)
+        got = plan(dx, out=out).cpu().numpy()
+        if not (same_nan(got, want) and self.still_nan(out[want.size:])):
+            return False, "cf32 entry"
+        rd = self.dev(raw, c["base"])
+
+        def from_bytes():
+            out = self.nans(want8.size + 8)
+            got = plan.from_bytes(rd, out=out).cpu().numpy()
+            return same_nan(got, want8) and self.still_nan(out[want8.size:])
+
+        def two_calls():   # redio_data_to_samples, then the cf32 entry on the same plan object
+            xs = self.R.bitfount.data_to_samples(self.dev(raw)) if c["n"] else self.dev(np.zeros(0, np.complex64))
+            return same_nan(plan(xs).cpu().numpy(), want8)
+
+        for name, f in ([("from_bytes", from_bytes), ("two calls", two_calls)] if c["u8_first"] else [("two calls", two_calls), ("from_bytes", from_bytes)]):
+            if not f():
+                return False, name
+        if rows:   # the definition: redio_pfb_enqueue, then redio_pspec_enqueue_spectra of a (nfft = M, integrate = K) plan
+            chan = self.plan(("Channelizer", M, P, ff, c["taps"], c["tseed"] if c["taps"] == "synth" else 0), lambda: self.R.Channelizer(h, M, P, ff))
+            X = chan(self.dev(x))[: rows * K].reshape(-1)
+            integ = self.pspec_plan({"N": M, "K": K, "step": M, "window": "none"}, False)
+            if not same_nan(self.spectra_route(integ, X, M).cpu().numpy(), want):
+                return False, "composition"
+        return True, ""
+
+    def pfb_streams(self, c):
+        t, ref, M, P, K, u8, n = self.t, self.pfb_pspec_ref, c["M"], c["P"], c["K"], c["u8"], c["rows"]
+        H = K * M
+        h = pfb_taps_of(self.O, c)
+        x = pfb_input(self.O, c, u8)
+        want = (ref.spectrum_u8 if u8 else ref.spectrum)(x, h, M, P, K, c["fir_fused"]).reshape(-1)
+        per = 2 if u8 else 1     # elements of the device view per sample
+        dx = self.dev(x)
+        st = self.R.Stream(self.pfb_plan(c), u8=u8)
+        cuts = np.concatenate([[0], np.cumsum(c["pieces"])]).astype(np.int64)
+        for which, cuts in (("first pass", cuts), ("after reset", None if c["again"] is None else np.array([0] + c["again"] + [n], np.int64))):
+            if cuts is None:
+                break
+            if which == "after reset":
+                st.reset()
+                if st.pending != 0:
+                    return False, "pending after reset"
+            outs, made = [], 0
+            for lo, hi in zip(cuts[:-1], cuts[1:]):
+                lo, hi = int(lo), int(hi)
+                expect = ref.nrows(hi, M, P, K) - made
+                if st.nout(hi - lo) != expect * M:
+                    return False, (which, "nout", lo, hi)
+                y = st(dx[per * lo: per * hi])
+                if y.numel() != expect * M:
+                    return False, (which, "count", lo, hi)
+                outs.append(y.clone())
+                made += expect
+                if st.pending != hi - made * H:
+                    return False, (which, "pending", lo, hi)
             got = t.cat(outs).cpu().numpy() if outs else np.zeros(0, np.float32)
             if not same_nan(got, want):
                 return False, which

@@ -1,6 +1,6 @@
 """A short, seeded run of the second randomised differential tool (tests/fuzz_spectra.py) per family: the real-input transform,
-overlap-save on real streams, the power spectrum from cf32 samples, from u8 bytes and from real samples, and their streams, bit for bit
-against the restatements on random shapes, steps, windows, split modes, alignments and message cuts.  Each run starts with the tool's
+overlap-save on real streams, the power spectrum from cf32 samples, from u8 bytes and from real samples, their streams, and the polyphase
+spectrometer (cf32 and bytes, fused and generic) and its streams, bit for bit against the restatements on random shapes, steps, windows, split modes, alignments and message cuts.  Each run starts with the tool's
 opening round of 24 cases, so its route coverage (tests/test_spectra_fuzz_cpu.py) does not depend on the machine's speed."""
 import ast
 import os
@@ -12,7 +12,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 11  # tests/test_spectra_fuzz_cpu.py checks the generator's coverage at this seed
-FAMILIES = ["fftr", "ovsave_real", "pspec", "pspec_u8", "pspec_real", "streams"]
+FAMILIES = ["fftr", "ovsave_real", "pspec", "pspec_u8", "pspec_real", "streams", "pfb_pspec", "pfb_streams"]
 
 
 @pytest.mark.parametrize("family", FAMILIES)

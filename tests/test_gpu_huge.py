@@ -270,6 +270,36 @@ def test_pspec_u8_past_2_32(gpu, redio, oracle, big, nfft, k):
     del out
 
 
+@pytest.mark.parametrize("M,P,K,mode,u8", [(64, 16, 16, 1, False), (64, 16, 17, 2, False), (64, 4, 16, 0, True), (128, 8, 16, 0, False), (100, 5, 4, 0, False)])
+def test_pfb_pspec_past_2_32(gpu, redio, oracle, big, M, P, K, mode, u8):
+    """redio_pfb_pspec_enqueue on 2^32 samples and more: the fused 64-channel kernel with a wave per run of whole rows, with a wave per
+    run of segments (K = 17: about 2 GiB of partials, and the fold pass) and from more than 2^33 bytes of u8 I/Q; the generic path through
+    its chunk loop on a one-kernel shape of the channelizer (128 x 8) and a two-pass one (100 x 5), where the rows either side of the
+    chunk seams next to every mark are compared as well"""
+    import pfb_pspec_ref
+    import pspec_ref
+    h = oracle.lpf_corrected(M * P, 0.45 / M)
+    W, H = pfb_pspec_ref.shape(M, P, K)
+    plan = redio.PolyphaseSpectrum(h, M, P, K)
+    plan.set_split(mode)
+    rows = plan.nrows(NV)
+    assert rows == (NV - W) // H + 1 and plan.is_fused == (M == 64)
+    if u8:
+        raw = u8_view(gpu, big)
+        assert raw.numel() == 2 * NV > 1 << 33
+        out = plan.from_bytes(raw)
+        want_of = lambda lo, cnt: pfb_pspec_ref.spectrum_u8(host_u8(oracle, lo, cnt), h, M, P, K, True)
+    else:
+        out = plan(big)
+        want_of = lambda lo, cnt: pfb_pspec_ref.spectrum(oracle.synth_iq(SEED, lo, cnt), h, M, P, K, True)
+    assert tuple(out.shape) == (rows, M)
+    assert K <= pspec_ref.SEG or plan.is_fused                 # below: a generic row is one segment
+    chunk = max(1, (64 << 20) // (M * 8 * pspec_ref.SEG))      # rows per pass of the generic path
+    seams = [q for b in marks(rows, H) for q in (b // chunk * chunk, (b // chunk + 1) * chunk)] if not plan.is_fused else []
+    check_rows(out, rows, W, H, want_of, seams)
+    del out
+
+
 @pytest.mark.parametrize("nfft,k,mode", [(2048, 16, 1), (2048, 16, 2), (2048, 17, 2), (4096, 4, 0)])
 def test_pspec_real_past_2_32(gpu, redio, oracle, big, nfft, k, mode):
     """redio_pspec_real_enqueue on 2^32 f32 samples and more: the fused kernel in both launch modes (one segment per row at K = 16;

@@ -135,3 +135,69 @@ def test_concurrent_real_input_and_spectrum_plans(gpu, redio, oracle):
         t.join(300)
     assert not any(t.is_alive() for t in threads), "a thread did not finish"
     assert not errors, errors
+
+
+def test_concurrent_polyphase_spectrum_plans(gpu, redio, oracle):
+    """redio_pfb_pspec_*: the segment partials of the fused kernel, the generic path's row scratch with the inner channelizer's own
+    scratch behind it, the conversion scratch of its u8 entry, and a stream's carried history -- eight threads, each with a plan of its
+    own on a stream of its own, row counts that rise and fall so that scratch regrows while the other threads are inside the library;
+    every result bit for bit the restatement's"""
+    import pfb_pspec_ref as ref
+    errors = []
+    rows_of = [1, 3, 2, 5, 1, 4, 6, 2, 7, 3, 1, 8]   # per iteration: up and down, the largest last
+
+    def same(got, want):
+        return got.shape == want.shape and np.array_equal(np.ascontiguousarray(got).view(np.uint32), np.ascontiguousarray(want).view(np.uint32))
+
+    def worker(kind, seed):
+        try:
+            s = gpu.cuda.Stream()
+            with gpu.cuda.stream(s):
+                M, P, K = {"fused": (64, 16, 17), "generic": (100, 5, 17), "generic_u8": (100, 5, 17), "stream": (64, 4, 3)}[kind]
+                W, H = ref.shape(M, P, K)
+                h = oracle.synth_f32(seed, 0, M * P)
+                plan = redio.PolyphaseSpectrum(h, M, P, K)
+                assert plan.is_fused == (M == 64)
+                if kind == "stream":   # one stream in twelve pieces against the one-shot rows of the whole
+                    lens = [(W - H if it == 0 else 0) + rows * H + 7 * it for it, rows in enumerate(rows_of)]
+                    x = oracle.synth_iq(seed, 0, sum(lens))
+                    whole = ref.spectrum(x, h, M, P, K, True)
+                    d = gpu.from_numpy(x).cuda()
+                    st = redio.Stream(plan)
+                    pos = made = 0
+                    for it, n in enumerate(lens):
+                        got = st(d[pos: pos + n]).cpu().numpy().reshape(-1, M)
+                        pos += n
+                        now = ref.nrows(pos, M, P, K)
+                        if not (same(got, whole[made:now]) and st.pending == pos - now * H):
+                            errors.append((kind, it))
+                        made = now
+                    assert made == len(whole) >= sum(rows_of)
+                    return
+                for it, rows in enumerate(rows_of):
+                    if kind == "fused":
+                        rows *= 3   # runs of four segments: several wavefronts
+                    n = W + (rows - 1) * H + 7 * it
+                    if kind == "generic_u8":
+                        raw = np.random.default_rng(seed + it).integers(0, 256, 2 * n, dtype=np.uint8)
+                        buf = gpu.zeros(raw.size + 16, dtype=gpu.uint8, device="cuda")
+                        buf[2: 2 + raw.size].copy_(gpu.from_numpy(raw))
+                        got = plan.from_bytes(buf[2: 2 + raw.size]).cpu().numpy()
+                        want = ref.spectrum_u8(raw, h, M, P, K, True)
+                    else:
+                        x = oracle.synth_iq(seed + it, 0, n)
+                        got = plan(gpu.from_numpy(x).cuda()).cpu().numpy()
+                        want = ref.spectrum(x, h, M, P, K, True)
+                    if not (len(want) == rows and same(got, want)):
+                        errors.append((kind, it))
+        except Exception as e:  # noqa: BLE001
+            errors.append((kind, repr(e)))
+
+    kinds = ["fused", "generic", "generic_u8", "stream", "fused", "generic", "generic_u8", "stream"]
+    threads = [threading.Thread(target=worker, args=(k, 1000 * (i + 1))) for i, k in enumerate(kinds)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(300)
+    assert not any(t.is_alive() for t in threads), "a thread did not finish"
+    assert not errors, errors

@@ -1,18 +1,23 @@
-"""The generator of tests/fuzz_spectra.py, and the four restatements it compares the device with, checked without a GPU.
+"""The generator of tests/fuzz_spectra.py, and the five restatements it compares the device with, checked without a GPU.
 
-Generator coverage: the dry mode (`fuzz_spectra.py --draw 2000 SEED`, the seed of tests/test_gpu_fuzz_spectra.py) is run as the
+Generator coverage: the dry mode (`fuzz_spectra.py --draw 6000 SEED`, the seed of tests/test_gpu_fuzz_spectra.py) is run as the
 command it is, in a process that must import neither torch nor the product library, and every route combination the driver of
-pspec_api.hip, the stream layer and the real-input plans distinguish has to turn up in at least 1 % of the cases.
+pspec_api.hip (the polyphase spectrometer's entries included), the stream layer and the real-input plans distinguish has to turn up
+in at least 1 % of the cases.
 
-Restatements against float64: the counterpart of test_oracle_random.py for fftr_ref, ovsave_real_ref, pspec_ref and pspec_real_ref, on
-the generator's own first 300 shapes, unspiced.  The bounds are the project's: 2e-6 for transforms and spectra (SURVEY.md 8c,
-test_pspec_cpu.py, test_fftr_cpu.py) and 2e-6 sum|taps| sqrt(log2 N) + 1e-7 for overlap-save (test_ovsave_real_cpu.py), each times
-max(1, p / 8) with p the largest prime factor of the complex transform's size, the rule of test_oracle_random.py.
-Worst distances over those 300 cases, as values and as fractions of their bounds (measure: max|got - exact| / max(exact) for the
+Restatements against float64: the counterpart of test_oracle_random.py for fftr_ref, ovsave_real_ref, pspec_ref, pspec_real_ref and
+pfb_pspec_ref, on the generator's own first 400 shapes (the opening round of all eight families and as many again), unspiced.  The
+bounds are the project's: 2e-6 for transforms and spectra (test_pspec_cpu.py, test_fftr_cpu.py) and
+2e-6 sum|taps| sqrt(log2 N) + 1e-7 for overlap-save (test_ovsave_real_cpu.py), each times max(1, p / 8) with p the largest prime
+factor of the complex transform's size, the rule of test_oracle_random.py.  The polyphase spectrometer (exact: the float64 branch fold,
+numpy's transform across the branches, |.|^2 summed over K rows) is held to the spectra rule with p of M as it stands: its measured
+worst is under half of it, so the taps ask for no factor of their own.
+Worst distances over those 400 cases, as values and as fractions of their bounds (measure: max|got - exact| / max(exact) for the
 spectra, relative L2 for the transforms, the largest absolute error for overlap-save):
-    pspec        3.6e-07, 0.18 of its bound        pspec_real   3.2e-07, 0.16
+    pspec        3.6e-07, 0.18 of its bound        pspec_real   3.4e-07, 0.17
     pspec_u8     4.2e-07, 0.21                     fftr         1.5e-07, 0.07
-    ovsave_real  8.5e-08, 0.08                     streams      3.0e-07, 0.15"""
+    ovsave_real  5.5e-07, 0.08                     streams      3.0e-07, 0.15
+    pfb_pspec    2.8e-07, 0.14                     pfb_streams  2.3e-07, 0.11"""
 import json
 import os
 import subprocess
@@ -24,11 +29,13 @@ import pytest
 import fftr_ref
 import fuzz_spectra as fz
 import ovsave_real_ref
+import pfb_pspec_ref
 import pspec_real_ref
 import pspec_ref
 
 SEED = 11          # tests/test_gpu_fuzz_spectra.py runs the tool with this seed
-DRAWN, LEAST = 2000, 20
+DRAWN, LEAST = 6000, 60
+CHECKED = 400      # cases of the float64 check: the opening round of every family and as many again at random
 TOOL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fuzz_spectra.py")
 # the dry mode as a command, in an interpreter that afterwards reports whether torch or the product library were imported
 DRY = ("import runpy, sys\n"
@@ -47,7 +54,7 @@ def drawn():
 
 
 def plan_key(c):
-    return json.dumps({k: c[k] for k in ("family", "N", "inverse", "ntaps", "taps", "tseed", "K", "step", "window", "wseed") if k in c}, sort_keys=True)
+    return json.dumps({k: c[k] for k in ("family", "N", "inverse", "ntaps", "taps", "tseed", "K", "step", "window", "wseed", "M", "P", "fir_fused") if k in c}, sort_keys=True)
 
 
 def test_the_dry_mode_draws_what_a_run_draws(drawn):
@@ -83,9 +90,28 @@ def test_every_route_combination_is_drawn_often_enough(drawn):
     cond["ovsave_real even ntaps"] = [c for c in by["ovsave_real"] if r(c)["ntaps_even"]]
     cond["fftr strided forward with overlap"] = [c for c in by["fftr"] if r(c)["strided"] and not c["inverse"] and r(c)["overlap"] and c["in_stride"] < c["N"]]
     cond["refusal expected"] = [c for c in drawn if r(c).get("refusal")]
+    # the polyphase spectrometer: a pfb_pspec case runs the cf32 entry, from_bytes and the composition; "from bytes" alone is a u8 stream
+    pfb, pst8 = by["pfb_pspec"], [c for c in by["pfb_streams"] if c["u8"]]
+    for name in ("fused", "one_kernel", "two_pass"):
+        cond[f"pfb_pspec {name}"] = [c for c in pfb if r(c)[name]]
+        cond[f"pfb_streams {name} from bytes"] = [c for c in pst8 if r(c)[name]]
+    cond["pfb_pspec m64_generic"] = [c for c in pfb if r(c)["m64_generic"]]
+    cond["pfb_pspec K <= 16"] = [c for c in pfb if c["K"] <= 16]
+    for mode in (1, 2):
+        cond[f"pfb_pspec fused K > 16 in mode {mode}"] = [c for c in pfb if r(c)["fused"] and c["K"] > 16 and r(c)["segments2"] and c["mode"] == mode]
+    cond["pfb_pspec fir_fused"] = [c for c in pfb if r(c)["fir_fused"]]
+    cond["pfb_pspec not fir_fused"] = [c for c in pfb if not r(c)["fir_fused"]]
+    cond["pfb_pspec rows == 0"] = [c for c in pfb if c["rows"] == 0]
+    cond["pfb_pspec K == 1"] = [c for c in pfb if c["K"] == 1]
+    cond["pfb_pspec base not a multiple of 8"] = [c for c in pfb if r(c)["base"] % 8]
+    cond["pfb_pspec cbase == 8"] = [c for c in pfb if r(c)["cbase"] == 8]
+    cond["pfb_pspec fused, more than two wavefronts"] = [c for c in pfb if r(c)["fused"] and c["rows"] > 2 * -(-64 // c["K"])]
+    for u8 in (False, True):
+        for name in ("zero_piece", "short_piece", "long_piece", "odd_piece", "reset"):
+            cond[f"pfb_streams u8={u8} {name}"] = [c for c in by["pfb_streams"] if c["u8"] == u8 and r(c)[name]]
     seen, again = {}, []
     for c in drawn:
-        if c["family"] != "streams":
+        if c["family"] not in ("streams", "pfb_streams"):
             k = plan_key(c)
             if any(rows != c["rows"] for rows in seen.get(k, ())):
                 again.append(c)
@@ -107,9 +133,11 @@ def test_every_route_combination_is_drawn_often_enough(drawn):
     for c in drawn:
         real = c["family"] in ("pspec_real", "fftr", "ovsave_real") or c.get("kind") in ("pspec_real", "ovsave_real")
         ntr = {"fftr": c["rows"], "ovsave_real": 2 * c["rows"]}.get(c["family"], c["rows"] * c.get("K", 1))
-        if c["family"] == "streams":
+        if c["family"] in ("streams", "pfb_streams"):
             continue
-        if r(c).get("staging"):
+        if c["family"] == "pfb_pspec":
+            assert c["rows"] * c["K"] <= fz.transforms_allowed(c["M"]) and c["rows"] * c["K"] * c["M"] <= fz.POINTS, c
+        elif r(c).get("staging"):
             assert ntr <= 2, c
         else:
             assert ntr * (c["N"] // 2 if real else c["N"]) <= fz.POINTS, c
@@ -125,6 +153,16 @@ def exact_rows(x, N, K, step, window, real):
     return P.reshape(-1, K, P.shape[1]).sum(axis=1)
 
 
+def exact_pfb_rows(x, h, M, P, K):
+    """float64: the branch fold y[t][m] = sum_p x[(t + p) M + m] h[p M + m], numpy's transform across the branches (the convention of
+    test_channelizer_against_its_polyphase_definition), |.|^2 summed over K rows"""
+    nt = pfb_pspec_ref.nrows(len(x), M, P, K) * K
+    X = x[: M * (P - 1 + nt)].astype(np.complex128).reshape(P - 1 + nt, M)
+    H = h.astype(np.float64).reshape(P, M)
+    branch = np.stack([(X[t:t + P] * H).sum(axis=0) for t in range(nt)])
+    return (np.abs(np.fft.fft(branch, axis=1)) ** 2).reshape(-1, K, M).sum(axis=1)
+
+
 def test_restatements_against_float64_on_the_generators_shapes(oracle):
     gen = fz.Gen(SEED)
     worst = {}
@@ -135,9 +173,21 @@ def test_restatements_against_float64_on_the_generators_shapes(oracle):
             w[:] = [err / tol, err]
         assert err <= tol, (fam, err, tol, c)
 
-    for _, fam in zip(range(300), fz.sequence(gen, None)):
+    for _, fam in zip(range(CHECKED), fz.sequence(gen, None)):
         c = gen.draw(fam)
         kind = c.get("kind", fam)
+        if fam in ("pfb_pspec", "pfb_streams"):
+            M, P, K = c["M"], c["P"], c["K"]
+            h = fz.pfb_taps_of(oracle, c)
+            for u8 in ((False, True) if fam == "pfb_pspec" else (c["u8"],)):
+                x = fz.pfb_input(oracle, c, u8, spiced=False)
+                xs = fz.samples_of(oracle, x) if u8 else x
+                got = pfb_pspec_ref.spectrum(xs, h, M, P, K, c["fir_fused"])
+                if len(got):
+                    want = exact_pfb_rows(xs, h, M, P, K)
+                    assert got.shape == want.shape
+                    note(fam, float(np.abs(got - want).max() / want.max()), 2e-6 * max(1.0, fz.largest_prime_factor(M) / 8.0), c)
+            continue
         x = fz.case_input(oracle, c, spiced=False)
         N = c["N"]
         rough = max(1.0, fz.largest_prime_factor(max(N if kind in ("pspec", "pspec_u8") else N // 2, 1)) / 8.0)
