@@ -1119,8 +1119,9 @@ void pfb_pspec_stream_block(Receiver<View<typename T::In>> &u, Sender<View<float
 } // namespace detail
 
 // the polyphase spectrometer (redio_pfb_pspec_*: |row[c]|^2 of the nchan-channel polyphase channelizer's rows, summed over `integrate`
-// rows; proto: nchan * taps_per_branch prototype taps; flags: REDIO_FIR_FUSED or 0): cf32 messages in, rows of nchan f32 out,
-// per-message semantics -- the rows that fit in each message, a trailing partial row dropped
+// rows; proto: nchan * taps_per_branch prototype taps; flags: REDIO_FIR_FUSED or 0, or-ed with REDIO_PFB_PSPEC_BLOCK for the plan's
+// workgroup kernel at 32 / 128 / 256 / 512 / 1024 channels -- all four blocks hand `flags` to redio_pfb_pspec_create as it is): cf32
+// messages in, rows of nchan f32 out, per-message semantics -- the rows that fit in each message, a trailing partial row dropped
 inline void polyphase_spectrum(Receiver<View<std::complex<float>>> u, Sender<View<float>> v, std::vector<float> proto, int nchan, int taps_per_branch, size_t integrate, unsigned flags = REDIO_FIR_FUSED) { detail::pfb_pspec_block<detail::PfbSpecCf32>(u, v, proto, nchan, taps_per_branch, integrate, flags); }
 // the same as a STREAM: messages of any length give the rows of one call on the whole stream; a message that completes no row sends nothing
 inline void polyphase_spectrum_stream(Receiver<View<std::complex<float>>> u, Sender<View<float>> v, std::vector<float> proto, int nchan, int taps_per_branch, size_t integrate, unsigned flags = REDIO_FIR_FUSED) { detail::pfb_pspec_stream_block<detail::PfbSpecCf32>(u, v, proto, nchan, taps_per_branch, integrate, flags); }

@@ -438,23 +438,33 @@ int redio_pfb_reserve_two_pass(redio_pfb *h, size_t n_in, int ngroups);
  * Bit for bit that is redio_pfb_enqueue followed by redio_pspec_enqueue_spectra of a (nfft = M, integrate = K) plan, for every shape
  * redio_pfb_create accepts -- that composition is the definition -- without the channel rows ever reaching memory on the fused
  * shapes.  No dB, no fftshift, no normalisation: those are the caller's.
- * create: NULL h, integrate == 0 -> REDIO_ERR_ARG; a shape redio_pfb_create refuses -> its error.  flags: as redio_pfb_create.
- * nchan = 64 with taps_per_branch in {4, 8, 16} is ONE kernel (redio_pfb_pspec_is_fused() == 1), from cf32 and from bytes: 8 (or 2)
- *   bytes read and 4 / K written per sample, no scratch beyond the segment partials.  Every other shape runs the plan's own
- *   redio_pfb into plan-owned row scratch in chunks of whole segments with at most 64 MiB of rows, and an accumulate pass per chunk.
+ * create: NULL h, integrate == 0 -> REDIO_ERR_ARG; a shape redio_pfb_create refuses -> its error.  flags: as redio_pfb_create, and
+ *   REDIO_PFB_PSPEC_BLOCK, which is this plan's own (redio_pfb_create never sees it).
+ * redio_pfb_pspec_route() says what a call on the plan runs (0 for NULL):
+ *   1  nchan = 64 with taps_per_branch in {4, 8, 16} is ONE kernel, a wavefront per run of rows (redio_pfb_pspec_is_fused() == 1),
+ *      from cf32 and from bytes: 8 (or 2) bytes read and 4 / K written per sample, no scratch beyond the segment partials.
+ *   2  with REDIO_PFB_PSPEC_BLOCK, nchan in {32, 128, 256, 512, 1024} with taps_per_branch in {4, 8, 16} -- the shapes of the
+ *      channelizer's own one-kernel form -- is ONE kernel too, a workgroup per G = max(1, 256 / nchan) runs of rows: the same 8 (or 2)
+ *      + 4 / K bytes per sample and no scratch beyond the segment partials.  Opt-in; is_fused() stays 0.  On every other shape the
+ *      flag is accepted and changes nothing.
+ *   0  every other plan runs its own redio_pfb into plan-owned row scratch in chunks of whole segments with at most 64 MiB of rows, and
+ *      an accumulate pass per chunk: 8 read + 8 written + 8 read + 4 / K written per sample.
  * reserve(h, n_in) / reserve_u8(h, nbytes) size all of the scratch, the inner channelizer's included, for calls of up to that many
  *   samples / bytes, after which an enqueue neither allocates nor synchronises; un-reserved it grows on first use
- *   (REDIO_ERR_NOT_RESERVED while the stream is being captured).
+ *   (REDIO_ERR_NOT_RESERVED while the stream is being captured).  On routes 1 and 2 that is the segment partials alone, which only a
+ *   call by segments with K > REDIO_PSPEC_SEG touches: every other call there needs no scratch and captures without a reserve.
  * enqueue / enqueue_u8 (interleaved u8 I/Q bytes, rtlsdr.rs:159-162: bit for bit redio_data_to_samples + enqueue): launches only, on
  *   the caller's stream; every argument is checked before anything is launched.  NULL or overlapping buffers, d_in not 8-byte,
  *   d_bytes not 2-byte or d_out not 4-byte aligned, odd nbytes -> REDIO_ERR_ARG; fewer than W samples -> REDIO_OK, no launch.
- * set_split: 0 auto, 1 a wavefront owns whole output rows, 2 a wavefront owns a run of whole segments and a fold pass finishes: the
- *   bits are the same in every mode. */
+ * set_split: 0 auto, 1 a wavefront (route 2: a thread group of a workgroup) owns whole output rows, 2 it owns a run of whole segments
+ *   and a fold pass finishes: the bits are the same in every mode, on every route and on every device. */
+#define REDIO_PFB_PSPEC_BLOCK 4u /* redio_pfb_pspec_create flags: the workgroup kernel (route 2) where the shape has one */
 typedef struct redio_pfb_pspec redio_pfb_pspec;
 int redio_pfb_pspec_create(redio_pfb_pspec **h, const float *proto_taps_host, int nchan, int taps_per_branch, size_t integrate, unsigned flags);
 int redio_pfb_pspec_destroy(redio_pfb_pspec *h);
 size_t redio_pfb_pspec_nrows(const redio_pfb_pspec *h, size_t n_in);
 int redio_pfb_pspec_is_fused(const redio_pfb_pspec *h);
+int redio_pfb_pspec_route(const redio_pfb_pspec *h); /* 0 generic, 1 the 64-channel wave kernel, 2 the workgroup kernel */
 int redio_pfb_pspec_reserve(redio_pfb_pspec *h, size_t n_in);
 int redio_pfb_pspec_enqueue(redio_pfb_pspec *h, const void *d_in_c32, size_t n_in, void *d_out_f32, void *stream);
 int redio_pfb_pspec_enqueue_u8(redio_pfb_pspec *h, const void *d_bytes, size_t nbytes, void *d_out_f32, void *stream);

@@ -20,6 +20,7 @@ LIBSAMPLERATE = os.path.join(_BUILD, "libsamplerate.so")
 
 REDIO_FIR_COMPLEX = 1
 REDIO_FIR_FUSED = 2
+REDIO_PFB_PSPEC_BLOCK = 4
 
 
 class RedioError(RuntimeError):
@@ -188,6 +189,7 @@ def lib():
     _sig(L.redio_pfb_pspec_destroy, i, vp)
     _sig(L.redio_pfb_pspec_nrows, sz, vp, sz)
     _sig(L.redio_pfb_pspec_is_fused, i, vp)
+    _sig(L.redio_pfb_pspec_route, i, vp)
     _sig(L.redio_pfb_pspec_reserve, i, vp, sz)
     _sig(L.redio_pfb_pspec_reserve_u8, i, vp, sz)
     _sig(L.redio_pfb_pspec_enqueue, i, vp, vp, sz, vp, vp)

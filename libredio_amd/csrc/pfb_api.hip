@@ -184,6 +184,8 @@ void redio_pfb_tables(const redio_pfb *h, const float **d_taps, const float2 **d
 {
     *d_taps = h->d_h; *d_tw = h->d_tw; *flags = h->flags; *fused_kernel = h->fused_kernel ? 1 : 0;
 }
+// ... and its workgroup kernel (pfb_pspec_p2.hip): the stage-ordered twiddle copy launch_pfb_p2 gets at 512 channels, else null
+const float2 *redio_pfb_twiddles_pass(const redio_pfb *h) { return h->fft ? redio_fft_twiddles_pass_dev(h->fft) : nullptr; }
 
 extern "C" int redio_pfb_enqueue(redio_pfb *h, const void *d_in, size_t n_in, void *d_out, int ngroups, void *stream)
 {

@@ -8,6 +8,7 @@
 //                      at N = 2048 (pspec_real_kernels.hip).  Per real sample: 4 N / step read + 4 B / (K step) written.
 //   redio_pfb_pspec    X = row t of the polyphase channelizer (redio_pfb_*, ngroups = 1) of M = nchan channels, B = M; a transform starts
 //                      every M samples and reads P M of them; fused at 64 channels x 4 / 8 / 16 taps per branch (pfb_pspec_kernels.hip).
+//                      With REDIO_PFB_PSPEC_BLOCK also at 32 / 128 / 256 / 512 / 1024 channels (pfb_pspec_p2.hip, `block` below).
 //                      Per input sample: 8 (cf32) or 2 (u8 I/Q) bytes read + 4 / K written.  Contract: DESIGN.md 5.6b.
 //   fused N      one kernel: the spectra stay in the wave's registers; one more fold pass when a wave takes a segment instead of a
 //                whole row
@@ -20,7 +21,7 @@
 #include "../../include/redio.h"
 #include "redio_internal.h"
 #include "pspec_real_core.h"
-#include "pfb_pspec_core.h"
+#include "pfb_pspec_p2_core.h"
 #include <new>
 #include <type_traits>
 
@@ -35,6 +36,8 @@ struct Pspec {
     size_t B;              // bins per row: N, or N / 2 + 1 for the real plan
     size_t K, step, S;     // S = ceil(K / 16) segments per row
     bool fused;            // the plan's one-kernel size
+    bool block;            // redio_pfb_pspec with REDIO_PFB_PSPEC_BLOCK on a pfb_p2 shape: the workgroup kernel (pfb_pspec_p2.hip), as
+                           // `fused` for scratch purposes; redio_pfb_pspec_is_fused() stays the 64-channel wave kernel
     int split;             // 0 auto, 1 one wave / thread group per row, 2 one per segment
     long split_rows;       // auto: a wave per segment below this many rows (PSPEC_SPLIT_ROWS / PSPEC_REAL_SPLIT_ROWS)
     float *d_win;          // N window values, or null
@@ -119,7 +122,7 @@ int enqueue(Pspec &c, const E &e, const void *d_in, size_t n_in, size_t nrows, v
     REDIO_TRY(hipSetDevice(c.device));
     hipStream_t st = (hipStream_t)stream;
     float *out = (float *)d_out;
-    const bool fused = E::transforms && c.fused;
+    const bool fused = E::transforms && (c.fused || c.block);
     const bool split = splits(c, nrows, fused);
     const size_t pass = pass_rows(c, nrows);
     const bool short_part = split && nrows * c.S * B > c.part_cap;
@@ -157,7 +160,7 @@ int reserve(Pspec &c, const E &e, size_t nrows)
     REDIO_TRY(hipSetDevice(c.device));
     if (splits(c, nrows, false))
         if (int rc = grow_part(c, nrows)) return rc;
-    return c.fused ? REDIO_OK : e.reserve(pass_rows(c, nrows));
+    return c.fused || c.block ? REDIO_OK : e.reserve(pass_rows(c, nrows));
 }
 
 // packed, already transformed rows of B bins in (redio_pspec_enqueue_spectra, redio_pspec_real_enqueue_spectra): n_in counts spectra
@@ -321,6 +324,9 @@ struct Polyphase {
     {
         const float *taps; const float2 *tw; unsigned flags; int fk;
         redio_pfb_tables(h->pfb, &taps, &tw, &flags, &fk);
+        if (h->c.block)
+            return launch_pfbspec_p2(d_in, U8, taps, tw, redio_pfb_twiddles_pass(h->pfb), dst, nunits, (long)h->c.K, h->M, h->P, split,
+                                     (flags & REDIO_FIR_FUSED) != 0, st);
         return launch_pfbspec64(d_in, U8, taps, tw, dst, nunits, (long)h->c.K, h->P, split, (flags & REDIO_FIR_FUSED) != 0, st);
     }
     int spectra(const void *d_in, size_t g0, size_t ntr, void *stream, const float2 *&spec) const
@@ -447,14 +453,21 @@ extern "C" int redio_pfb_pspec_create(redio_pfb_pspec **h, const float *proto, i
     *h = nullptr;
     if (integrate == 0) return REDIO_ERR_ARG;
     redio_pfb *pfb = nullptr;
+    const bool want_block = (flags & REDIO_PFB_PSPEC_BLOCK) != 0; // this plan's own flag: the channelizer never sees it
+    flags &= ~REDIO_PFB_PSPEC_BLOCK;
     if (int rc = redio_pfb_create(&pfb, proto, nchan, taps_per_branch, flags)) return rc; // its own refusals
     redio_pfb_pspec *p = new (std::nothrow) redio_pfb_pspec();
     if (!p) { redio_pfb_destroy(pfb); return REDIO_ERR_NOMEM; }
     p->pfb = pfb; p->M = nchan; p->P = taps_per_branch;
     const float *taps; const float2 *tw; unsigned fl; int fused;
     redio_pfb_tables(pfb, &taps, &tw, &fl, &fused);
-    // auto mode: a wave per run of whole rows once those runs give PFBSPEC_SPLIT_WAVES waves
-    const long split_rows = PFBSPEC_SPLIT_WAVES * pfbspec_units_per_wave(1, (long)integrate, false);
+    // the workgroup kernel where the caller asked for it and the channelizer has its one-kernel form (never 64 channels)
+    const bool block = want_block && !fused && pfb_p2_supported(nchan, taps_per_branch);
+    // auto mode: a wave per run of whole rows once those runs give PFBSPEC_SPLIT_WAVES waves; the workgroup kernel: a stream per
+    // run of whole rows once those runs fill PFBSPEC_P2_SPLIT_GROUPS_PER_CU workgroups per CU (pfb_pspec_p2_core.h)
+    const long split_rows = block ? pfbspec_p2_split_rows((long)integrate, num_cus(), nchan)
+                                  : PFBSPEC_SPLIT_WAVES * pfbspec_units_per_wave(1, (long)integrate, false);
+    p->c.block = block;
     if (int rc = pspec_init(p->c, nchan * taps_per_branch, (size_t)nchan, integrate, (size_t)nchan, fused != 0, split_rows, nullptr)) {
         redio_pfb_pspec_destroy(p);
         return rc;
@@ -474,6 +487,7 @@ extern "C" int redio_pfb_pspec_destroy(redio_pfb_pspec *h)
 void redio_pfb_pspec_shape(const redio_pfb_pspec *h, int *window, size_t *K, size_t *step, int *device) { *window = h->c.nfft; *K = h->c.K; *step = h->c.step; *device = h->c.device; }
 extern "C" size_t redio_pfb_pspec_nrows(const redio_pfb_pspec *h, size_t n_in) { return h ? nrows_of(h->c, n_in) : 0; }
 extern "C" int redio_pfb_pspec_is_fused(const redio_pfb_pspec *h) { return h && h->c.fused ? 1 : 0; }
+extern "C" int redio_pfb_pspec_route(const redio_pfb_pspec *h) { return !h ? 0 : h->c.block ? 2 : h->c.fused ? 1 : 0; }
 extern "C" int redio_pfb_pspec_set_split(redio_pfb_pspec *h, int mode) { return h ? set_split(h->c, mode) : REDIO_ERR_ARG; }
 extern "C" int redio_pfb_pspec_reserve(redio_pfb_pspec *h, size_t n_in)
 {

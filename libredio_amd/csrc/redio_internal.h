@@ -131,6 +131,13 @@ hipError_t launch_pspec_fold(const float *part, float *out, long nrows, long N, 
 hipError_t launch_pfbspec64(const void *x, bool in_u8, const float *h, const float2 *tw64, float *dst, long nunits, long K, int taps_per_branch,
                             bool split, bool fused, hipStream_t s);
 
+// pfb_pspec_p2.hip: the same in the workgroup form of pfb_p2_kernel, for the shapes of pfb_p2_supported() (32, 128, 256, 512 or 1024
+// channels x 4, 8 or 16 taps per branch; hipErrorNotSupported otherwise).  dst: nchan f32 per unit; tw: the nchan-entry forward table;
+// Tord: the 512-point plan's stage-ordered copy (512 channels only).  The stream geometry is pfb_pspec_p2_core.h's.
+bool pfb_p2_supported(int nchan, int taps_per_branch); // pfb_p2.hip
+hipError_t launch_pfbspec_p2(const void *x, bool in_u8, const float *h, const float2 *tw, const float2 *Tord, float *dst, long nunits, long K, int nchan,
+                             int taps_per_branch, bool split, bool fused, hipStream_t s);
+
 // pspec_real_kernels.hip: the real-input integrated power spectrum.  launch_pspecr2k: 2048 real points per transform, one wavefront per
 // unit (a row of K transforms, or with `split` one segment of at most 16); x: 4-byte aligned; dst: 1025 f32 per unit; win: 2048 values
 // or null; tw / stw: the tables of the plan's redio_fftr.  launch_pspec_real_rows: the generic path's row gather (rows: ntr packed
@@ -206,6 +213,7 @@ void redio_pspec_shape(const redio_pspec *h, int *nfft, size_t *integrate, size_
 void redio_pspec_real_shape(const redio_pspec_real *h, int *nfft, size_t *integrate, size_t *step, int *device);
 void redio_pfb_pspec_shape(const redio_pfb_pspec *h, int *window, size_t *integrate, size_t *step, int *device); // window = nchan * taps_per_branch samples, step = nchan
 void redio_pfb_tables(const redio_pfb *h, const float **d_taps, const float2 **d_tw, unsigned *flags, int *fused_kernel); // pfb_api.hip
+const float2 *redio_pfb_twiddles_pass(const redio_pfb *h); // pfb_api.hip: what launch_pfb_p2 takes as Tord (512 channels), else null
 // redio_ovsave_real_enqueue for the carried-history layer: d_in may be only 4-byte aligned (a message that started on an odd sample)
 int redio_ovsave_real_enqueue_any(redio_ovsave_real *h, const void *d_in, size_t n_in, void *d_out, void *stream);
 

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import REDIO_FIR_COMPLEX, REDIO_FIR_FUSED, check, lib, redio_msg
+from . import REDIO_FIR_COMPLEX, REDIO_FIR_FUSED, REDIO_PFB_PSPEC_BLOCK, check, lib, redio_msg
 
 _pf = C.POINTER(C.c_float)
 
@@ -796,17 +796,21 @@ class PolyphaseSpectrum:
     """redio_pfb_pspec_*: the polyphase spectrometer -- |row[c]|^2 of a Channelizer's rows (ngroups = 1) summed over `integrate`
     consecutive rows in the blocked order of DESIGN.md 5.3c (contract: DESIGN.md 5.6b), bit for bit Channelizer followed by
     PowerSpectrum(nchan, integrate).spectra: complex64 samples (or, from_bytes, the receiver's u8 I/Q bytes) in, rows of nchan
-    float32 out.  64 channels with 4 / 8 / 16 taps per branch are one kernel (is_fused): the channel rows never reach memory."""
+    float32 out.  64 channels with 4 / 8 / 16 taps per branch are one kernel (is_fused, route WAVE): the channel rows never reach
+    memory.  one_kernel=True (REDIO_PFB_PSPEC_BLOCK) asks for the workgroup kernel (route BLOCK) at 32, 128, 256, 512 or 1024
+    channels with 4 / 8 / 16 taps per branch, where the channel rows never reach memory either; on every other shape it changes
+    nothing.  Every other plan is route GENERIC: the plan's own channelizer into row scratch, then an accumulate pass."""
 
     AUTO, ROWS, SEGMENTS = 0, 1, 2
+    GENERIC, WAVE, BLOCK = 0, 1, 2
 
-    def __init__(self, proto, nchan=64, taps_per_branch=16, integrate=1, fused=True):
+    def __init__(self, proto, nchan=64, taps_per_branch=16, integrate=1, fused=True, one_kernel=False):
         t, p = _taps(proto)
         assert len(t) == nchan * taps_per_branch
         self.nchan, self.taps_per_branch, self.integrate = int(nchan), int(taps_per_branch), int(integrate)
         self._h = C.c_void_p()
-        check(lib().redio_pfb_pspec_create(C.byref(self._h), p, self.nchan, self.taps_per_branch, self.integrate,
-                                           REDIO_FIR_FUSED if fused else 0), "pfb_pspec_create")
+        flags = (REDIO_FIR_FUSED if fused else 0) | (REDIO_PFB_PSPEC_BLOCK if one_kernel else 0)
+        check(lib().redio_pfb_pspec_create(C.byref(self._h), p, self.nchan, self.taps_per_branch, self.integrate, flags), "pfb_pspec_create")
 
     def nrows(self, n_in):
         return lib().redio_pfb_pspec_nrows(self._h, n_in)
@@ -814,6 +818,11 @@ class PolyphaseSpectrum:
     @property
     def is_fused(self):
         return bool(lib().redio_pfb_pspec_is_fused(self._h))
+
+    @property
+    def route(self):
+        """what a call runs: GENERIC, WAVE (the 64-channel kernel, is_fused) or BLOCK (the workgroup kernel, one_kernel=True)"""
+        return lib().redio_pfb_pspec_route(self._h)
 
     def reserve(self, n_in, u8=False):
         """all plan scratch (the inner channelizer's included) for calls of up to n_in samples, so that a call never allocates, e.g.

@@ -1,5 +1,5 @@
 """Throughput of the non-headline configs of BASELINE.json on one MI355X (own measurements; bench.py
-stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit]..."""
+stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit|pfbpspecp2|pfbpspecp2split]..."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, libredio_amd as R
@@ -317,6 +317,67 @@ if "pfbpspecsplit" in which:
                 ms[mode - 1] = min(ms[mode - 1], timeit(lambda: plan(x, out=out), n=10, warm=3))
         print(f"PFB-PSPEC 64x16 K={k} ({rows} rows, {min(rows, 2048) if k >= 64 else -(-rows // max(2, -(-rows // 2048)))} waves in mode 1): mode 1 {ms[0]:.3f} ms  mode 2 {ms[1]:.3f} ms", flush=True)
         del plan, out
+    del x
+if "pfbpspecp2" in which:
+    # the polyphase spectrometer's workgroup kernel (route 2, REDIO_PFB_PSPEC_BLOCK) on 2^28 samples resident in HBM: (n) the flagged
+    # plan against (a) redio_pfb_enqueue[_u8] alone on the same samples, which writes every channel row, and (b) the unflagged plan of
+    # the same shape (the generic route), whose rows are compared with (n)'s bit for bit before anything is timed.  Timed alternately,
+    # twice each, in this one process; the smaller time of each is printed.  Algorithmic bytes per sample of (n): 8 (cf32) or 2 (u8)
+    # + 4 / K; of (b): 8 or 2 read + 8 written + 8 read + 4 / K.  The bar: n < b on every shape; the target from cf32: n < a.
+    xc = R.synth_iq(0x5EED0004, 0, n)
+    xb = torch.randint(0, 256, (2 * n,), dtype=torch.uint8, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))
+    for u8 in (False, True):
+        for M, P, k in ((32, 16, 16), (128, 8, 16), (256, 8, 16), (256, 16, 16), (512, 8, 16), (1024, 4, 16), (256, 8, 1024)):
+            h = R.dsputils.lpf_corrected(M * P, 0.45 / M)
+            plan = R.PolyphaseSpectrum(h, M, P, k, one_kernel=True)
+            base = R.PolyphaseSpectrum(h, M, P, k)
+            assert plan.route == plan.BLOCK and base.route == base.GENERIC
+            plan.reserve(n, u8=u8); base.reserve(n, u8=u8)
+            x = xb if u8 else xc
+            rows = plan.nrows(n)
+            out = torch.empty(rows * M, dtype=torch.float32, device="cuda")
+            out_b = torch.empty_like(out)
+            chan = R.Channelizer(h, M, P)
+            if u8: R.check(R.lib().redio_pfb_reserve_u8(chan._h, 2 * n, 1), "pfb_reserve_u8")
+            else: chan.reserve(n)
+            crows = torch.empty((chan.nrows(n), M), dtype=torch.complex64, device="cuda")
+            run_n = (lambda: plan.from_bytes(x, out=out)) if u8 else (lambda: plan(x, out=out))
+            run_b = (lambda: base.from_bytes(x, out=out_b)) if u8 else (lambda: base(x, out=out_b))
+            run_a = (lambda: chan.from_bytes(x, out=crows)) if u8 else (lambda: chan(x, out=crows))
+            run_n(); run_b()
+            same = torch.equal(out.view(torch.int32), out_b.view(torch.int32))
+            assert same, "leg (b) and leg (n) differ"
+            ms_n = ms_a = ms_b = 1e30
+            for _ in range(2):
+                ms_n = min(ms_n, timeit(run_n, n=10, warm=3))
+                ms_a = min(ms_a, timeit(run_a, n=10 if not u8 else 3, warm=3))
+                ms_b = min(ms_b, timeit(run_b, n=3, warm=2))
+            b = (2 if u8 else 8) + 4 / k
+            print(f"PFB-PSPEC-P2 {M}x{P} K={k} from {'u8' if u8 else 'cf32'}: {rows} rows  (n) {ms_n:.3f} ms  {n/ms_n/1e6:.1f} GS/s  "
+                  f"{b*n/ms_n/1e6:.0f} GB/s algorithmic ({b*n/ms_n/1e6/8000:.1%} of 8 TB/s at {b:.3f} B/sample) | (a) channelizer alone: {ms_a:.3f} ms | "
+                  f"(b) the unflagged plan: {ms_b:.3f} ms, rows bit-equal: {same} | n/a = {ms_n/ms_a:.3f}  n/b = {ms_n/ms_b:.3f}", flush=True)
+            del plan, base, out, out_b, chan, crows
+    del xc, xb
+if "pfbpspecp2split" in which:
+    # the table behind PFBSPEC_P2_SPLIT_GROUPS_PER_CU (pfb_pspec_p2_core.h): 2^28 cf32 samples, a stream per run of whole rows
+    # against a stream per run of whole segments + fold
+    x = R.synth_iq(0x5EED0004, 0, n)
+    for M, P in ((256, 8), (1024, 4)):
+        h = R.dsputils.lpf_corrected(M * P, 0.45 / M)
+        for k in (32, 64, 128, 256, 512, 1024, 2048, 4096):
+            plan = R.PolyphaseSpectrum(h, M, P, k, one_kernel=True)
+            assert plan.route == plan.BLOCK
+            plan.reserve(n)
+            rows = plan.nrows(n)
+            out = torch.empty(rows * M, dtype=torch.float32, device="cuda")
+            ms = [1e30, 1e30]
+            for _ in range(2):
+                for mode in (1, 2):
+                    plan.set_split(mode)
+                    ms[mode - 1] = min(ms[mode - 1], timeit(lambda: plan(x, out=out), n=10, warm=3))
+            streams = -(-rows // max(-(-64 // k), -(-rows // (4 * torch.cuda.get_device_properties(0).multi_processor_count * max(1, 256 // M)))))
+            print(f"PFB-PSPEC-P2 {M}x{P} K={k} ({rows} rows, {streams} streams in mode 1): mode 1 {ms[0]:.3f} ms  mode 2 {ms[1]:.3f} ms", flush=True)
+            del plan, out
     del x
 if "fftall" in which:
     for nfft in (6, 9, 10, 12, 15, 20, 24, 25, 27, 30, 40, 45, 48, 60, 75, 80, 81, 90, 96, 100, 120, 125, 150, 160, 180, 192, 200, 225, 240, 243, 250, 300, 320, 360, 384, 400, 450, 480, 500, 600, 625, 640, 720, 729, 768, 800, 900, 960, 1000, 1200, 1280, 1440, 1536, 1600, 1800, 1920, 2000, 2187, 2400, 2560, 3072, 3125, 3200, 3600, 3840, 4000, 4800, 5120, 6144, 6400, 6561, 7680, 8000):
