@@ -1131,5 +1131,68 @@ inline void polyphase_spectrum_u8(Receiver<View<uint8_t>> u, Sender<View<float>>
 // the same as a STREAM (redio_pfb_pspec_stream_create_u8: the history is carried as bytes)
 inline void polyphase_spectrum_stream_u8(Receiver<View<uint8_t>> u, Sender<View<float>> v, std::vector<float> proto, int nchan, int taps_per_branch, size_t integrate, unsigned flags = REDIO_FIR_FUSED) { detail::pfb_pspec_stream_block<detail::PfbSpecU8>(u, v, proto, nchan, taps_per_branch, integrate, flags); }
 
+namespace detail {
+// the tuner's four blocks: cf32 or u8 I/Q messages in (per_sample elements make a sample), cf32 out
+struct TunerCf32 {
+    using In = std::complex<float>;
+    static constexpr size_t per_sample = 1;
+    static constexpr auto enqueue = redio_ddc_enqueue;
+    static constexpr auto stream_create = redio_ddc_stream_create;
+};
+struct TunerU8 {
+    using In = uint8_t;
+    static constexpr size_t per_sample = 2;
+    static constexpr auto enqueue = redio_ddc_enqueue_u8;
+    static constexpr auto stream_create = redio_ddc_stream_create_u8;
+};
+inline redio_ddc *tuner_plan(const std::vector<std::complex<float>> &osc, const std::vector<float> &taps, size_t decim, bool fused)
+{
+    redio_ddc *h = nullptr;
+    check(redio_ddc_create(&h, reinterpret_cast<const float *>(osc.data()), osc.size(), taps.data(), taps.size(), decim, fused ? REDIO_FIR_FUSED : 0));
+    return h;
+}
+template <typename T>
+void tuner_block(Receiver<View<typename T::In>> &u, Sender<View<std::complex<float>>> &v, const std::vector<std::complex<float>> &osc, const std::vector<float> &taps,
+                 size_t decim, bool fused)
+{
+    using In = typename T::In;
+    using cf = std::complex<float>;
+    redio_ddc *h = tuner_plan(osc, taps, decim, fused);
+    struct G { redio_ddc *h; ~G() { redio_ddc_destroy(h); } } g{h};
+    // every message starts the table at entry 0: mul_vecs multiplies EVERY message by the same constant vector (kpn.rs:198-203)
+    run_block<In, cf>(u, v, [&](const View<In> &d) { return redio_ddc_nout(h, d.len / T::per_sample); },
+                      [&](const View<In> &d, const View<cf> &o, void *st) { return T::enqueue(h, d.data(), d.len, 0, o.data(), st); });
+}
+template <typename T>
+void tuner_stream_block(Receiver<View<typename T::In>> &u, Sender<View<std::complex<float>>> &v, const std::vector<std::complex<float>> &osc,
+                        const std::vector<float> &taps, size_t decim, bool fused)
+{
+    using In = typename T::In;
+    using cf = std::complex<float>;
+    redio_ddc *h = tuner_plan(osc, taps, decim, fused);
+    redio_ddc_stream *s = nullptr;
+    const int rc = T::stream_create(&s, h);
+    struct G { redio_ddc *h; redio_ddc_stream *s; ~G() { redio_ddc_stream_destroy(s); redio_ddc_destroy(h); } } g{h, s};
+    check(rc);
+    run_stream_block_of<In, cf>(u, v, [&](size_t len) { return redio_ddc_stream_nout(s, len / T::per_sample); },
+                                [&](const View<In> &d, cf *o, size_t *got, void *st) {
+                                    if (d.len % T::per_sample) return (int)REDIO_ERR_ARG;
+                                    return redio_ddc_stream_enqueue(s, d.data(), d.len / T::per_sample, o, got, st);
+                                });
+}
+} // namespace detail
+
+// the tuner (redio_ddc_*: kpn::mul_vecs by the periodic table `osc`, kpn.rs:198-203, fused into the FIR of dsputils::convolve,
+// dsputils.rs:30-32, with decimation): cf32 messages in, cf32 out, per-message semantics -- the table restarts at entry 0 with every
+// message, exactly as mul_vecs multiplies every message by the same vector, and ntaps - 1 outputs are lost at every seam.  Queue-ordered
+// on the rings like dev::fir.
+inline void tuner(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<std::complex<float>> osc, std::vector<float> taps, size_t decim, bool fused) { detail::tuner_block<detail::TunerCf32>(u, v, osc, taps, decim, fused); }
+// the receiver's messages straight into the tuner: u8 I/Q bytes (rtlsdr.rs:127-162), without the cf32 intermediate; a message holds whole samples
+inline void tuner_u8(Receiver<View<uint8_t>> u, Sender<View<std::complex<float>>> v, std::vector<std::complex<float>> osc, std::vector<float> taps, size_t decim, bool fused) { detail::tuner_block<detail::TunerU8>(u, v, osc, taps, decim, fused); }
+// the same as a STREAM (redio_ddc_stream_*): history AND oscillator phase are carried, so messages of any length give the outputs of one
+// call on the whole stream; a message that completes no output sends nothing.  Queue-ordered like dev::fir_stream.
+inline void tuner_stream(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<std::complex<float>> osc, std::vector<float> taps, size_t decim, bool fused) { detail::tuner_stream_block<detail::TunerCf32>(u, v, osc, taps, decim, fused); }
+inline void tuner_stream_u8(Receiver<View<uint8_t>> u, Sender<View<std::complex<float>>> v, std::vector<std::complex<float>> osc, std::vector<float> taps, size_t decim, bool fused) { detail::tuner_stream_block<detail::TunerU8>(u, v, osc, taps, decim, fused); }
+
 } // namespace dev
 } // namespace kpn

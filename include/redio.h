@@ -123,6 +123,36 @@ size_t redio_fir_nout(const redio_fir *h, size_t n_in);
 /* valid-mode over one device buffer; d_out must hold redio_fir_nout() samples; in != out */
 int redio_fir_enqueue(redio_fir *h, const void *d_in, size_t n_in, void *d_out, void *stream);
 
+/* ---- the tuner: a frequency-translating FIR (A1c) ----
+ * kpn::mul_vecs (src/kpn/src/kpn.rs:198-203) by a periodic constant vector w of `period` cf32 entries, then dsputils::convolve
+ * (src/dsputils/src/dsputils.rs:30-32) with decimation, in ONE kernel: the oscillator mix happens while the FIR tile is staged.
+ *     m[n] = (xr*wr - xi*wi, xr*wi + xi*wr) with w = osc[(first_index + n) mod period], every operation rounded on its own
+ *     y[i] = redio_fir's fold over m[i*decim + j] * taps[j]   (REDIO_FIR_FUSED selects fmaf for the FOLD only; the mix is never contracted)
+ * so every output is bit-equal to redio_fir_enqueue (complex) on redio_mul_c32(x, the table tiled from first_index); the u8 entry
+ * converts each byte as redio_data_to_samples does (rtlsdr.rs:159-162) before the mix.  first_index is the stream index of the
+ * call's sample 0.  redio_osc_table fills a table for the shift num/den of the sample rate (kpn.rs:198-203's constant vector;
+ * dsputils.rs:30-32 is untouched by it): period = den / gcd(|num|, den) entries, entry n = exp(2 pi i k / den) with
+ * k = (num n) mod den in [0, den), computed in double and cast once, the quarter turns exact (an fs/4 shift multiplies by 1, i, -1, -i);
+ * a negative num tunes down; out_c32 == NULL only returns the period; den == 0 or a period above REDIO_DDC_MAX_PERIOD -> REDIO_ERR_ARG.
+ * create (kpn.rs:198-203, dsputils.rs:30-32): any caller table (mul_vecs' general c); table and taps are uploaded here.  NULL h /
+ *   table / taps, period == 0 or above REDIO_DDC_MAX_PERIOD, ntaps == 0, decim == 0 -> REDIO_ERR_ARG.  flags: REDIO_FIR_FUSED or 0.
+ * nout: redio_fir_nout's formula.  route: 1 the specialised tiled kernel (127 / 63 taps at decimation 5 / 1), 2 the any-taps chunked
+ *   one (decimation 1, 2, 3, 4, 5, 8, 10), 3 the direct one; 0 for NULL.
+ * enqueue / enqueue_u8 (kpn.rs:198-203, dsputils.rs:30-32; nbytes / 2 samples): launch only -- no allocation, no synchronisation, so
+ *   capturable.  NULL handle, odd nbytes, NULL or overlapping buffers (in != out) -> REDIO_ERR_ARG; fewer than ntaps samples ->
+ *   REDIO_OK, no launch.  Any whole-sample alignment of d_in / d_out and any byte alignment of d_bytes is taken; 16-byte aligned
+ *   cf32 (4-byte aligned bytes) run the two-samples-per-load path. */
+#define REDIO_DDC_MAX_PERIOD 65536 /* a 512 KiB table */
+typedef struct redio_ddc redio_ddc;
+int redio_osc_table(long long num, unsigned long long den, float *out_c32, size_t *period);
+int redio_ddc_create(redio_ddc **h, const float *osc_host_c32, size_t period, const float *taps_host, size_t ntaps, size_t decim, unsigned flags);
+int redio_ddc_destroy(redio_ddc *h);
+size_t redio_ddc_nout(const redio_ddc *h, size_t n_in);
+size_t redio_ddc_period(const redio_ddc *h);
+int redio_ddc_route(const redio_ddc *h);
+int redio_ddc_enqueue(redio_ddc *h, const void *d_in_c32, size_t n_in, uint64_t first_index, void *d_out_c32, void *stream);
+int redio_ddc_enqueue_u8(redio_ddc *h, const void *d_bytes, size_t nbytes, uint64_t first_index, void *d_out_c32, void *stream);
+
 /* ---- lists of independent messages for one launch (redio_fft_enqueue_list, redio_chain_enqueue_list) ----
  * The reference runs one kissfft::fft per message of block_size samples (src/kissfft/src/kissfft.rs:20-27 asserts din.len() ==
  * block_size) and one chain per message from a block thread (src/ratpak.rs:60-185); a launch per small message costs a fixed floor
@@ -599,6 +629,19 @@ int redio_pfb_pspec_stream_reset(redio_pfb_pspec_stream *h);
 size_t redio_pfb_pspec_stream_nout(const redio_pfb_pspec_stream *h, size_t n_new);
 size_t redio_pfb_pspec_stream_pending(const redio_pfb_pspec_stream *h);
 int redio_pfb_pspec_stream_enqueue(redio_pfb_pspec_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
+/* the tuner as a stream (kpn.rs:198-203, dsputils.rs:30-32): carried history AND carried phase -- the handle passes the stream index of
+ * every window's first sample to the plan as first_index, so any segmentation gives the bits of one redio_ddc_enqueue on the whole
+ * stream with first_index 0.  create_u8: d_new points to interleaved u8 I/Q bytes (any alignment), n_new still counts SAMPLES.
+ * redio_ddc_stream_index: the stream index of the next new sample (0 after create and reset; unchanged by a failed call). */
+typedef struct redio_ddc_stream redio_ddc_stream;
+int redio_ddc_stream_create(redio_ddc_stream **h, redio_ddc *plan);
+int redio_ddc_stream_create_u8(redio_ddc_stream **h, redio_ddc *plan);
+int redio_ddc_stream_destroy(redio_ddc_stream *h);
+int redio_ddc_stream_reset(redio_ddc_stream *h);
+size_t redio_ddc_stream_nout(const redio_ddc_stream *h, size_t n_new);
+size_t redio_ddc_stream_pending(const redio_ddc_stream *h);
+int redio_ddc_stream_enqueue(redio_ddc_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
+uint64_t redio_ddc_stream_index(const redio_ddc_stream *h);
 
 /* ---- A6: samplerate::resample's native side, src/samplerate/src/samplerate.rs:59-87 ----
  * nchan independent mono streams that share ratio and block lengths (the reference creates one

@@ -21,6 +21,7 @@ LIBSAMPLERATE = os.path.join(_BUILD, "libsamplerate.so")
 REDIO_FIR_COMPLEX = 1
 REDIO_FIR_FUSED = 2
 REDIO_PFB_PSPEC_BLOCK = 4
+REDIO_DDC_MAX_PERIOD = 65536
 
 
 class RedioError(RuntimeError):
@@ -100,6 +101,15 @@ def lib():
     _sig(L.redio_fir_destroy, i, vp)
     _sig(L.redio_fir_nout, sz, vp, sz)
     _sig(L.redio_fir_enqueue, i, vp, vp, sz, vp, vp)
+    _sig(L.redio_osc_table, i, C.c_longlong, C.c_ulonglong, pf, C.POINTER(sz))
+    _sig(L.redio_ddc_create, i, C.POINTER(vp), pf, sz, pf, sz, sz, u)
+    _sig(L.redio_ddc_destroy, i, vp)
+    _sig(L.redio_ddc_nout, sz, vp, sz)
+    _sig(L.redio_ddc_period, sz, vp)
+    _sig(L.redio_ddc_route, i, vp)
+    _sig(L.redio_ddc_enqueue, i, vp, vp, sz, C.c_uint64, vp, vp)
+    _sig(L.redio_ddc_enqueue_u8, i, vp, vp, sz, C.c_uint64, vp, vp)
+    _sig(L.redio_ddc_stream_index, C.c_uint64, vp)
     _sig(L.redio_fft_create, i, C.POINTER(vp), i, i)
     _sig(L.redio_fft_destroy, i, vp)
     _sig(L.redio_fft_enqueue, i, vp, vp, vp, sz, vp)
@@ -124,14 +134,14 @@ def lib():
     _sig(L.redio_fft_reserve, i, vp, sz)
     _sig(L.redio_pfb_reserve, i, vp, sz, i)
     _sig(L.redio_pfb_reserve_two_pass, i, vp, sz, i)
-    for n in ("fir", "chain", "pfb", "ovsave", "ovsave_real", "pspec", "pspec_real", "pfb_pspec"):
+    for n in ("fir", "chain", "pfb", "ovsave", "ovsave_real", "pspec", "pspec_real", "pfb_pspec", "ddc"):
         _sig(getattr(L, f"redio_{n}_stream_create"), i, C.POINTER(vp), vp)
         _sig(getattr(L, f"redio_{n}_stream_destroy"), i, vp)
         _sig(getattr(L, f"redio_{n}_stream_reset"), i, vp)
         _sig(getattr(L, f"redio_{n}_stream_nout"), sz, vp, sz)
         _sig(getattr(L, f"redio_{n}_stream_pending"), sz, vp)
         _sig(getattr(L, f"redio_{n}_stream_enqueue"), i, vp, vp, sz, vp, C.POINTER(sz), vp)
-    for n in ("chain", "pfb", "pspec", "pfb_pspec"):
+    for n in ("chain", "pfb", "pspec", "pfb_pspec", "ddc"):
         _sig(getattr(L, f"redio_{n}_stream_create_u8"), i, C.POINTER(vp), vp)
     _sig(L.redio_chain_enqueue, i, vp, vp, sz, vp, vp)
     _sig(L.redio_chain_enqueue_u8, i, vp, vp, sz, vp, vp)
@@ -289,4 +299,4 @@ def check(code, what="redio"):
 
 
 from . import bitfount, dsputils, kissfft, kpn_dev, plans, samplerate  # noqa: E402,F401
-from .plans import Chain, Channelizer, Comm, Fft, Fftr, Fir, Graph, OverlapSave, OverlapSaveReal, PolyphaseSpectrum, PowerSpectrum, PowerSpectrumReal, Src, Stream, channelizer_all_to_all, current_stream, planes_to_rows, rows_to_planes, synth_f32, synth_iq  # noqa: E402,F401
+from .plans import Chain, Channelizer, Comm, Ddc, Fft, Fftr, Fir, Graph, OverlapSave, OverlapSaveReal, PolyphaseSpectrum, PowerSpectrum, PowerSpectrumReal, Src, Stream, channelizer_all_to_all, current_stream, planes_to_rows, rows_to_planes, synth_f32, synth_iq  # noqa: E402,F401

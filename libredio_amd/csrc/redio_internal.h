@@ -62,6 +62,11 @@ inline bool taps_bit_palindromic(const float *taps, size_t K)
 hipError_t launch_fir(const void *x, long n_in, const float *taps, bool taps_pal, int K, long D, void *y, long n_out,
                       bool cplx, bool fused, hipStream_t s);
 
+// ddc_kernels.hip: the tuner (oscillator mix fused into the FIR tile load).  x: n_in cf32 samples or, with u8, their interleaved I/Q
+// bytes; tab: period L entries extended by DDC_TABLE_EXT (ddc_core.h); first_mod = first_index mod L; y: n_out outputs
+hipError_t launch_ddc(const void *x, bool u8, long n_in, unsigned first_mod, const float2 *tab, unsigned L, const float *taps, int K, long D, float2 *y,
+                      long n_out, bool fused, hipStream_t s);
+
 // fft_kernels.hip
 constexpr int FFT_MAX_STAGES = 32;
 struct FftPlanDev {
@@ -203,7 +208,8 @@ inline int num_cus()
 } // namespace redio
 
 // plan shapes for the carried-history layer (stream_carry.hip); defined next to each plan struct
-struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real; struct redio_pspec; struct redio_pspec_real; struct redio_pfb_pspec;
+struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real; struct redio_pspec; struct redio_pspec_real; struct redio_pfb_pspec; struct redio_ddc;
+void redio_ddc_shape(const redio_ddc *h, size_t *ntaps, size_t *decim, int *device);
 void redio_fir_shape(const redio_fir *h, size_t *ntaps, size_t *decim, unsigned *flags, int *device);
 void redio_chain_shape(const redio_chain *h, size_t *ntaps, size_t *decim, int *nfft, int *device);
 void redio_pfb_shape(const redio_pfb *h, int *nchan, int *taps_per_branch, int *device);

@@ -11,6 +11,9 @@
 //     power spectrum W = (integrate-1)*step + nfft H = integrate*step unit = 1 row (nfft f32 from cf32 samples, or from u8 I/Q byte pairs)
 //     real power spectrum  the same W and H in REAL samples  unit = 1 row (nfft/2 + 1 f32 from f32 samples)
 //     polyphase spectrum  W = (integrate-1+taps_per_branch)*nchan  H = integrate*nchan  unit = 1 row (nchan f32 from cf32 samples or u8 I/Q byte pairs)
+//     tuner        W = ntaps                       H = decim          unit = 1 output sample (from cf32 samples or u8 I/Q byte pairs); the
+//                  oscillator's phase is carried too: the layer knows the stream index of the head's and the body's first sample
+//                  (total_in - hist, and total_in + the samples of this call in front of the body) and hands it to the plan as first_index
 // so one layer serves them all.  The handle keeps the stream's unconsumed tail (fewer than W samples) on the device.
 // A call with n new samples
 //   1. appends the first min(n, W-1) new samples to the tail in a plan-owned staging buffer (one small copy),
@@ -56,7 +59,7 @@ hipError_t seam_copy(void *dst, const void *src, size_t bytes, hipStream_t st)
     SEAM_GO(uint8_t)
 #undef SEAM_GO
 }
-enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8, K_PSPEC_REAL, K_PFB_PSPEC, K_PFB_PSPEC_U8 }; // _U8: the samples are interleaved u8 I/Q byte pairs
+enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8, K_PSPEC_REAL, K_PFB_PSPEC, K_PFB_PSPEC_U8, K_DDC, K_DDC_U8 }; // _U8: the samples are interleaved u8 I/Q byte pairs
 struct Carry {
     int device = 0;
     Kind kind = K_FIR;
@@ -84,9 +87,12 @@ struct Entered { // holds Carry::busy for the life of a call
 using redio::StreamSplit;
 static StreamSplit split(const Carry &c, size_t n) { return redio::stream_split(c.hist, c.W, c.H, n); }
 
-int run(const Carry &c, const void *d_in, size_t n_in, void *d_out, void *stream)
+// first: the stream index of d_in's first sample (the tuner's phase; every other plan ignores it)
+int run(const Carry &c, const void *d_in, size_t n_in, unsigned long long first, void *d_out, void *stream)
 {
     switch (c.kind) {
+    case K_DDC: return redio_ddc_enqueue((redio_ddc *)c.plan, d_in, n_in, first, d_out, stream);
+    case K_DDC_U8: return redio_ddc_enqueue_u8((redio_ddc *)c.plan, d_in, 2 * n_in, first, d_out, stream);
     case K_FIR: return redio_fir_enqueue((redio_fir *)c.plan, d_in, n_in, d_out, stream);
     case K_CHAIN: return redio_chain_enqueue((redio_chain *)c.plan, d_in, n_in, d_out, stream);
     case K_PFB: return redio_pfb_enqueue((redio_pfb *)c.plan, d_in, n_in, d_out, 1, stream);
@@ -167,11 +173,11 @@ int carry_enqueue(Carry *c, const void *d_new, size_t n, void *d_out, size_t *no
     if (c->hist > 0 && m > 0) REDIO_TRY(seam_copy(S + c->hist * c->in_elem, src, m * c->in_elem, st));
     char *out = (char *)d_out;
     if (s.nh) {
-        const int rc = run(*c, S, s.head_in, out, stream);
+        const int rc = run(*c, S, s.head_in, redio::stream_head_first(c->total_in, c->hist), out, stream);
         if (rc) return rc;
     }
     if (s.nb) {
-        const int rc = run(*c, src + s.off * c->in_elem, s.body_in, out + s.nh * c->unit_out * c->out_elem, stream);
+        const int rc = run(*c, src + s.off * c->in_elem, s.body_in, redio::stream_body_first(c->total_in, drop, s), out + s.nh * c->unit_out * c->out_elem, stream);
         if (rc) return rc;
     }
     // the new tail: everything from the start of the first unit not yet produced
@@ -224,6 +230,7 @@ struct redio_ovsave_real_stream { Carry *c; };
 struct redio_pspec_stream { Carry *c; };
 struct redio_pspec_real_stream { Carry *c; };
 struct redio_pfb_pspec_stream { Carry *c; };
+struct redio_ddc_stream { Carry *c; };
 
 #define RD_STREAM_API(NAME)                                                                                                     \
     extern "C" int redio_##NAME##_stream_destroy(redio_##NAME##_stream *h)                                                      \
@@ -253,6 +260,7 @@ RD_STREAM_API(ovsave_real)
 RD_STREAM_API(pspec)
 RD_STREAM_API(pspec_real)
 RD_STREAM_API(pfb_pspec)
+RD_STREAM_API(ddc)
 
 template <typename Hd>
 static int make(Hd **h, Kind kind, void *plan, int dev, size_t W, size_t H, size_t in_elem, size_t unit_out, size_t out_elem, uintptr_t align = 0)
@@ -399,3 +407,17 @@ extern "C" int redio_pfb_pspec_stream_create_u8(redio_pfb_pspec_stream **h, redi
     if (!plan) return REDIO_ERR_ARG;
     return make_pspec(h, plan, K_PFB_PSPEC_U8, redio_pfb_pspec_shape, redio_pfb_pspec_reserve_u8, 2, 2, 1, pfb_pspec_bins(plan));
 }
+// the tuner's two streams: history and phase.  total_in counts every sample fed since create / reset, so it is the stream index of the
+// next new sample; it moves only when a call commits, like hist.
+static int make_ddc(redio_ddc_stream **h, redio_ddc *plan, bool u8)
+{
+    if (!h) return REDIO_ERR_ARG;
+    *h = nullptr;
+    if (!plan) return REDIO_ERR_ARG;
+    size_t K, D; int dev;
+    redio_ddc_shape(plan, &K, &D, &dev);
+    return make(h, u8 ? K_DDC_U8 : K_DDC, plan, dev, K, D, u8 ? 2 : 8, 1, 8);
+}
+extern "C" int redio_ddc_stream_create(redio_ddc_stream **h, redio_ddc *plan) { return make_ddc(h, plan, false); }
+extern "C" int redio_ddc_stream_create_u8(redio_ddc_stream **h, redio_ddc *plan) { return make_ddc(h, plan, true); }
+extern "C" uint64_t redio_ddc_stream_index(const redio_ddc_stream *h) { return h ? h->c->total_in : 0; }

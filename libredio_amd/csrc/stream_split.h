@@ -35,4 +35,10 @@ inline StreamSplit stream_split(size_t hist, size_t W, size_t H, size_t n)
     return s;
 }
 
+// Where the head's and the body's first samples lie in the STREAM (the tuner's phase, redio_ddc_stream_*): total_in samples were fed
+// before this call, the tail holds the last `hist` of them, and the call drops `drop` of its own samples first (a hop longer than the
+// window).  Both are the start u * H of the first unit u the run produces.
+inline unsigned long long stream_head_first(unsigned long long total_in, size_t hist) { return total_in - hist; }
+inline unsigned long long stream_body_first(unsigned long long total_in, size_t drop, const StreamSplit &s) { return total_in + drop + s.off; }
+
 } // namespace redio

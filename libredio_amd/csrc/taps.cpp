@@ -102,3 +102,33 @@ extern "C" int redio_lpf_corrected(size_t m, float fc, float *out)
     }
     return REDIO_OK;
 }
+
+// The tuner's oscillator table (redio_ddc_*): the constant vector of kpn::mul_vecs (src/kpn/src/kpn.rs:198-203) for a shift of num/den of
+// the sample rate.  kissfft's twiddle rule: the phase in double, one cast.  The quarter turns are exact, so an fs/4 shift only permutes
+// and negates components.
+extern "C" int redio_osc_table(long long num, unsigned long long den, float *out, size_t *period)
+{
+    if (den == 0) return REDIO_ERR_ARG;
+    const unsigned long long mag = num < 0 ? 0ull - (unsigned long long)num : (unsigned long long)num;
+    unsigned long long a = mag % den, b = den; // gcd(|num|, den) = gcd(|num| mod den, den)
+    while (a) { const unsigned long long t = b % a; b = a; a = t; }
+    const unsigned long long L = den / b;
+    if (L > REDIO_DDC_MAX_PERIOD) return REDIO_ERR_ARG;
+    if (period) *period = (size_t)L;
+    if (!out) return REDIO_OK;
+    const unsigned long long step = num < 0 ? (den - mag % den) % den : mag % den; // num mod den in [0, den)
+    unsigned long long k = 0;
+    for (unsigned long long n = 0; n < L; ++n) {
+        const unsigned __int128 k4 = (unsigned __int128)k * 4;
+        if (k4 % den == 0) {
+            static const float QR[4] = {1.0f, 0.0f, -1.0f, 0.0f}, QI[4] = {0.0f, 1.0f, 0.0f, -1.0f};
+            const int q = (int)(k4 / den);
+            out[2 * n] = QR[q]; out[2 * n + 1] = QI[q];
+        } else {
+            const double ph = ((2.0 * M_PI) * (double)k) / (double)den;
+            out[2 * n] = (float)cos(ph); out[2 * n + 1] = (float)sin(ph);
+        }
+        k = (unsigned long long)(((unsigned __int128)k + step) % den); // (num (n + 1)) mod den, exact
+    }
+    return REDIO_OK;
+}

@@ -50,4 +50,14 @@ def bpf(m, fc1, fc2): return _gen("redio_bpf", m, fc1, fc2)  # dsputils.rs:91-94
 def lpf_corrected(m, fc): return _gen("redio_lpf_corrected", m, fc)
 
 
-__all__ = ["convolve", "window", "sinc", "lpf", "hpf", "bsf", "bpf", "lpf_corrected", "RedioError"]
+def osc_table(num, den):
+    """redio_osc_table: the tuner's oscillator for a shift of num/den of the sample rate (negative num tunes down), one period of
+    den / gcd(|num|, den) complex64 entries; the constant vector of kpn::mul_vecs (kpn.rs:198-203)."""
+    period = C.c_size_t(0)
+    check(lib().redio_osc_table(int(num), int(den), None, C.byref(period)), "osc_table")
+    out = np.empty(2 * period.value, np.float32)
+    check(lib().redio_osc_table(int(num), int(den), _ptr(out), C.byref(period)), "osc_table")
+    return out.view(np.complex64)
+
+
+__all__ = ["osc_table", "convolve", "window", "sinc", "lpf", "hpf", "bsf", "bpf", "lpf_corrected", "RedioError"]

@@ -64,6 +64,59 @@ class Fir:
             self._h = None
 
 
+class Ddc:
+    """redio_ddc_*: the tuner -- kpn::mul_vecs (kpn.rs:198-203) by the periodic oscillator table `osc` (complex64, any period up to
+    REDIO_DDC_MAX_PERIOD; dsputils.osc_table makes one), then the FIR of dsputils::convolve (dsputils.rs:30-32) with decimation, in one
+    kernel; bit for bit Fir(taps, decim)(x * osc tiled from `first`).  complex64 in (or uint8 I/Q bytes through from_bytes), complex64 out."""
+
+    def __init__(self, osc, taps, decim=1, fused=False):
+        t, p = _taps(taps)
+        w = np.ascontiguousarray(osc, dtype=np.complex64).reshape(-1)
+        self.ntaps, self.decim, self.complex_input = len(t), int(decim), True
+        self._h = C.c_void_p()
+        check(lib().redio_ddc_create(C.byref(self._h), w.view(np.float32).ctypes.data_as(_pf), len(w), p, len(t), self.decim,
+                                     REDIO_FIR_FUSED if fused else 0), "ddc_create")
+
+    def nout(self, n_in):
+        return lib().redio_ddc_nout(self._h, n_in)
+
+    @property
+    def route(self):
+        """redio_ddc_route: 1 the specialised tiled kernel, 2 the any-taps chunked one, 3 the direct one."""
+        return lib().redio_ddc_route(self._h)
+
+    @property
+    def period(self):
+        return lib().redio_ddc_period(self._h)
+
+    def _run(self, fn, x, nsamp, count, first, out):
+        import torch
+        n = self.nout(nsamp)
+        if out is None:
+            out = torch.empty(n, dtype=torch.complex64, device=x.device)
+        assert out.dtype == torch.complex64 and out.numel() >= n
+        check(getattr(lib(), fn)(self._h, _dev_ptr(x), count, int(first), _dev_ptr(out), current_stream()), fn[6:])
+        return out[:n]
+
+    def __call__(self, x, first=0, out=None):
+        """`first`: the stream index of x[0] (the table entry of sample n is osc[(first + n) % period])."""
+        import torch
+        assert x.dtype == torch.complex64
+        return self._run("redio_ddc_enqueue", x, x.numel(), x.numel(), first, out)
+
+    def from_bytes(self, raw, first=0, out=None):
+        """redio_ddc_enqueue_u8: the receiver's interleaved u8 I/Q bytes (rtlsdr.rs:159-162); bitfount.data_to_samples(raw) through
+        __call__, bit for bit."""
+        import torch
+        assert raw.dtype == torch.uint8 and raw.numel() % 2 == 0
+        return self._run("redio_ddc_enqueue_u8", raw, raw.numel() // 2, raw.numel(), first, out)
+
+    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
+        if getattr(self, "_h", None):
+            _safe_destroy("redio_ddc_destroy", self._h)
+            self._h = None
+
+
 class Fft:
     """redio_fft_*: batched kissfft::fft blocks (kissfft.rs:18-31), unnormalised."""
 
@@ -265,14 +318,14 @@ class Stream:
     """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec,pspec_real,pfb_pspec}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
     segmentation of the input gives the bits of one stateless call on the whole stream (the stateless plans keep the
     reference's per-message semantics, dsputils.rs:30-32).  `plan` is a Fir, Chain, Channelizer, OverlapSave, OverlapSaveReal, PowerSpectrum
-    (complex64 in, float32 rows out), PowerSpectrumReal (float32 in, float32 rows out) or PolyphaseSpectrum (complex64 in, float32 rows
-    of nchan out)."""
+    (complex64 in, float32 rows out), PowerSpectrumReal (float32 in, float32 rows out), PolyphaseSpectrum (complex64 in, float32 rows
+    of nchan out) or Ddc (the tuner: the oscillator's phase is carried with the history)."""
 
     def __init__(self, plan, u8=False):
-        """u8=True (Chain, Channelizer, PowerSpectrum and PolyphaseSpectrum): the stream arrives as the receiver's interleaved u8 I/Q
+        """u8=True (Chain, Channelizer, PowerSpectrum, PolyphaseSpectrum and Ddc): the stream arrives as the receiver's interleaved u8 I/Q
         bytes (uint8 tensors, two bytes per sample; redio_{chain,pfb,pspec,pfb_pspec}_stream_create_u8)."""
-        kind = {Fir: "fir", Chain: "chain"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec", "PowerSpectrumReal": "pspec_real", "PolyphaseSpectrum": "pfb_pspec"}[type(plan).__name__]
-        assert not u8 or kind in ("chain", "pfb", "pspec", "pfb_pspec")
+        kind = {Fir: "fir", Chain: "chain", Ddc: "ddc"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec", "PowerSpectrumReal": "pspec_real", "PolyphaseSpectrum": "pfb_pspec"}[type(plan).__name__]
+        assert not u8 or kind in ("chain", "pfb", "pspec", "pfb_pspec", "ddc")
         self._kind, self._plan, self._u8 = kind, plan, bool(u8)          # the plan must outlive the stream handle
         self._h = C.c_void_p()
         check(getattr(lib(), f"redio_{kind}_stream_create" + ("_u8" if u8 else ""))(C.byref(self._h), plan._h), f"{kind}_stream_create")
@@ -289,6 +342,11 @@ class Stream:
 
     def reset(self):
         check(self._f("reset")(self._h), "stream_reset")
+
+    @property
+    def index(self):
+        """redio_ddc_stream_index (a Ddc stream only): the stream index of the next new sample, which is the oscillator's phase."""
+        return self._f("index")(self._h)
 
     def __call__(self, x, out=None):
         """Feed the next piece of the stream; returns the output samples that became computable (flat tensor; the

@@ -1,0 +1,56 @@
+"""What the tuner (redio_ddc_*) must give, from the oracle's own blocks alone: kpn::mul_vecs (kpn.rs:198-203) by the oscillator table
+tiled from `first`, then the FIR of dsputils::convolve (dsputils.rs:30-32).  Nothing is computed here."""
+import math
+
+import numpy as np
+
+import oracle
+
+MAX_PERIOD = 65536
+
+
+def tile_out(ntaps, decim):
+    """outputs one workgroup produces on the route of (ntaps, decim): 256 lanes x outputs per lane"""
+    if ntaps in (127, 63) and decim in (1, 5):
+        return 256 * (8 if decim == 1 else 4)
+    r = {1: 8, 2: 4, 3: 4, 4: 4, 5: 4, 8: 2, 10: 2}.get(decim)
+    return 256 * r if r else 256
+
+
+def route(ntaps, decim):
+    if ntaps in (127, 63) and decim in (1, 5):
+        return 1
+    return 2 if decim in (1, 2, 3, 4, 5, 8, 10) else 3
+
+
+def tiled(w, first, n):
+    w = np.ascontiguousarray(w, np.complex64)
+    idx = [(first + i) % len(w) for i in range(n)] if first + n >= 2 ** 63 else (np.arange(n, dtype=np.uint64) + np.uint64(first)) % np.uint64(len(w))
+    return w[np.asarray(idx, dtype=np.int64)]
+
+
+def mixed(x, w, first=0):
+    return oracle.zip_vecs(x, tiled(w, first, len(x)))
+
+
+def ddc(x, w, taps, decim=1, fused=False, first=0):
+    return oracle.fir(mixed(x, w, first), taps, decim, fused)
+
+
+def ddc_u8(raw, w, taps, decim=1, fused=False, first=0):
+    return ddc(oracle.data_to_samples(raw), w, taps, decim, fused, first)
+
+
+def osc_table_ref(num, den):
+    """the rule of redio_osc_table with Python's integers and math.cos / math.sin on the same expression"""
+    period = den // math.gcd(abs(num), den)
+    out = np.empty(period, np.complex64)
+    quarter = (1 + 0j, 0 + 1j, -1 + 0j, 0 - 1j)
+    for n in range(period):
+        k = (num * n) % den
+        if (4 * k) % den == 0:
+            out[n] = quarter[4 * k // den]
+        else:
+            a = ((2.0 * math.pi) * float(k)) / float(den)
+            out[n] = np.complex64(complex(np.float32(math.cos(a)), np.float32(math.sin(a))))
+    return out

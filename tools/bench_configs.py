@@ -1,5 +1,5 @@
 """Throughput of the non-headline configs of BASELINE.json on one MI355X (own measurements; bench.py
-stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit|pfbpspecp2|pfbpspecp2split]..."""
+stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit|pfbpspecp2|pfbpspecp2split|ddc|ddcu8]..."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, libredio_amd as R
@@ -614,3 +614,47 @@ if "trigger" in which:
     bufs = trig.feed(blocks)
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
     print(f"trigger over {ns} samples ({blocks.shape[0]} blocks): {dt*1e3:.2f} ms  {ns/dt/1e9:.1f} GS/s, {len(bufs)} buffers emitted, {sum(b.numel() for b in bufs)} samples kept")
+if "ddc" in which or "ddcu8" in which:
+    # the tuner (redio_ddc_*: oscillator mix fused into the FIR tile load) on 2^28 samples against the route it replaces, timed alternately
+    # (twice each, the smaller time printed) in this one process: (a) redio_mul_c32 on a PRE-MATERIALISED oscillator stream (its
+    # generation is not counted: a head start for the old route) + redio_fir_enqueue -- for u8 also + redio_data_to_samples -- and
+    # (b) redio_fir_enqueue alone (no mix at all; on the complex /5 and /1 shapes that call runs the chain-form data path, which the
+    # tuner does not have).  Share of 8 TB/s on the algorithmic bytes: 8 + 8/D per input sample from cf32, 2 + 8/D from u8.
+    from libredio_amd.plans import _dev_ptr, current_stream
+    x = R.synth_iq(1, 0, n)
+    for leg in [l for l in ("ddc", "ddcu8") if l in which]:
+        u8 = leg == "ddcu8"
+        raw = torch.randint(0, 256, (2 * n,), dtype=torch.uint8, device="cuda") if u8 else None
+        mixed, conv = torch.empty_like(x), (torch.empty_like(x) if u8 else None)
+        for k, d in ((127, 5), (63, 5), (63, 1), (31, 2), (255, 10)):
+            taps = R.dsputils.lpf_corrected(k, 0.4 / max(d, 2))
+            fir = R.Fir(taps, d, fused=True)
+            out = torch.empty(fir.nout(n), dtype=torch.complex64, device="cuda")
+            per = {}
+            for period in (24, 65536):
+                w = R.dsputils.osc_table(-5, 24) if period == 24 else R.dsputils.osc_table(1, 65536)
+                plan = R.Ddc(w, taps, d, fused=True)
+                osc = torch.from_numpy(w).cuda().repeat((n + period - 1) // period)[:n].contiguous()
+
+                def old():
+                    src = x
+                    if u8:
+                        R.check(R.lib().redio_data_to_samples(_dev_ptr(raw), 2 * n, _dev_ptr(conv), current_stream()), "data_to_samples")
+                        src = conv
+                    R.check(R.lib().redio_mul_c32(_dev_ptr(src), _dev_ptr(osc), _dev_ptr(mixed), n, current_stream()), "mul_c32")
+                    fir(mixed, out=out)
+                new = (lambda: plan.from_bytes(raw, out=out)) if u8 else (lambda: plan(x, out=out))
+                ms = ms_old = ms_fir = 1e30
+                for _ in range(2):
+                    ms = min(ms, timeit(new, n=20, warm=3))
+                    ms_old = min(ms_old, timeit(old, n=10, warm=3))
+                    ms_fir = min(ms_fir, timeit(lambda: fir(x, out=out), n=20, warm=3))
+                b = (2 if u8 else 8) + 8 / d
+                per[period] = ms
+                print(f"{'DDC-U8' if u8 else 'DDC'} {k} taps /{d} period {period} (route {plan.route}): {ms:.3f} ms  {n/ms/1e6:.1f} GS/s  {b*n/ms/1e6:.0f} GB/s algorithmic "
+                      f"({b*n/ms/1e6/8000:.1%} of 8 TB/s) | (a) {'data_to_samples + ' if u8 else ''}mul_c32 + fir: {ms_old:.3f} ms, tuner / (a) = {ms/ms_old:.3f} | "
+                      f"(b) fir alone: {ms_fir:.3f} ms, tuner / (b) = {ms/ms_fir:.3f}")
+                del plan, osc
+            print(f"{'DDC-U8' if u8 else 'DDC'} {k} taps /{d}: period 65536 / period 24 = {per[65536]/per[24]:.3f}")
+            del fir, out
+        del raw, mixed, conv
