@@ -1194,5 +1194,41 @@ inline void tuner_u8(Receiver<View<uint8_t>> u, Sender<View<std::complex<float>>
 inline void tuner_stream(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<std::complex<float>> osc, std::vector<float> taps, size_t decim, bool fused) { detail::tuner_stream_block<detail::TunerCf32>(u, v, osc, taps, decim, fused); }
 inline void tuner_stream_u8(Receiver<View<uint8_t>> u, Sender<View<std::complex<float>>> v, std::vector<std::complex<float>> osc, std::vector<float> taps, size_t decim, bool fused) { detail::tuner_stream_block<detail::TunerU8>(u, v, osc, taps, decim, fused); }
 
+namespace detail {
+// the rational resampler's two blocks: T is float or std::complex<float>, in and out
+template <typename T>
+redio_upfirdn *upfirdn_plan(const std::vector<float> &taps, size_t up, size_t down, bool fused)
+{
+    redio_upfirdn *h = nullptr;
+    check(redio_upfirdn_create(&h, taps.data(), taps.size(), up, down, (sizeof(T) == 8 ? REDIO_FIR_COMPLEX : 0) | (fused ? REDIO_FIR_FUSED : 0)));
+    return h;
+}
+} // namespace detail
+
+// the rational resampler (redio_upfirdn_*: up by `up`, the FIR of dsputils::convolve, dsputils.rs:30-32, down by `down`, as a polyphase
+// FIR over the original samples): f32 or cf32 messages in, the same type out, per-message semantics -- every message starts at phase 0
+// and the outputs whose taps would reach past its end are lost at every seam.  Queue-ordered on the rings like dev::fir.
+template <typename T>
+void upfirdn(Receiver<View<T>> u, Sender<View<T>> v, std::vector<float> taps, size_t up, size_t down, bool fused)
+{
+    redio_upfirdn *h = detail::upfirdn_plan<T>(taps, up, down, fused);
+    struct G { redio_upfirdn *h; ~G() { redio_upfirdn_destroy(h); } } g{h};
+    detail::run_block<T, T>(u, v, [&](const View<T> &d) { return redio_upfirdn_nout(h, d.len); },
+                            [&](const View<T> &d, const View<T> &o, void *st) { return redio_upfirdn_enqueue(h, d.data(), d.len, o.data(), st); });
+}
+// the same as a STREAM (redio_upfirdn_stream_*): the history is carried, so messages of any length give whole periods of the outputs of
+// one call on the whole stream; a message that completes no period sends nothing.  Queue-ordered like dev::fir_stream.
+template <typename T>
+void upfirdn_stream(Receiver<View<T>> u, Sender<View<T>> v, std::vector<float> taps, size_t up, size_t down, bool fused)
+{
+    redio_upfirdn *h = detail::upfirdn_plan<T>(taps, up, down, fused);
+    redio_upfirdn_stream *s = nullptr;
+    const int rc = redio_upfirdn_stream_create(&s, h);
+    struct G { redio_upfirdn *h; redio_upfirdn_stream *s; ~G() { redio_upfirdn_stream_destroy(s); redio_upfirdn_destroy(h); } } g{h, s};
+    check(rc);
+    detail::run_stream_block_of<T, T>(u, v, [&](size_t len) { return redio_upfirdn_stream_nout(s, len); },
+                                      [&](const View<T> &d, T *o, size_t *got, void *st) { return redio_upfirdn_stream_enqueue(s, d.data(), d.len, o, got, st); });
+}
+
 } // namespace dev
 } // namespace kpn

@@ -153,6 +153,37 @@ int redio_ddc_route(const redio_ddc *h);
 int redio_ddc_enqueue(redio_ddc *h, const void *d_in_c32, size_t n_in, uint64_t first_index, void *d_out_c32, void *stream);
 int redio_ddc_enqueue_u8(redio_ddc *h, const void *d_bytes, size_t nbytes, uint64_t first_index, void *d_out_c32, void *stream);
 
+/* ---- the rational resampler: up by `up`, FIR, down by `down`, as a polyphase FIR (A1d) ----
+ * dsputils::convolve (src/dsputils/src/dsputils.rs:30-32) with decimation over the stream z that holds up - 1 zeros behind EVERY sample
+ * (z[m up] = x[m], length n up), run on the original samples with every up-th tap -- a stated design, defined as
+ *     y[i] = acc after: acc = +0; for j = 0 .. ntaps-1 ascending, ONLY where (i down + j) mod up == 0:
+ *                acc = mac(x[(i down + j) / up], taps[j], acc)
+ *     mac is redio_fir's: a rounded multiply then a rounded add, or fmaf with REDIO_FIR_FUSED
+ *     nout(n) = 0 when n up < ntaps, else (n up - ntaps) / down + 1
+ * Positions that hold a stuffed zero are SKIPPED, not multiplied (redio_fir on a zero-stuffed buffer gives the same bits except for
+ * the sign of a zero where every earlier product underflows under fmaf, and wherever 0 * inf would appear).  Phase by phase, with
+ * g = gcd(up, down), U' = up / g, D' = down / g and r in [0, U'): y[r + U' q] is redio_fir's fold of x[s(r) + q D' + t] * taps[j0 + up t]
+ * with j0 = (-(r down)) mod up and s(r) = (r down + j0) / up.  One period is U' outputs from D' new samples and reads the window
+ * Wp = ((U' - 1) down + ntaps - 1) / up + 1 samples.  Samples are f32, or cf32 with REDIO_FIR_COMPLEX; the taps stay real.
+ * create (dsputils.rs:30-32): the taps are uploaded in polyphase order, one zero-padded sub-filter per phase, with a per-phase table.
+ *   flags: REDIO_FIR_COMPLEX, REDIO_FIR_FUSED, with redio_fir_create's meaning.  NULL h / taps, ntaps == 0, up == 0, down == 0 ->
+ *   REDIO_ERR_ARG; ntaps > 2^24, up > 65536 or down >= 2^31 -> REDIO_ERR_UNSUPPORTED.
+ * nout: the formula above (0 for NULL and for n_in above 2^46, where n_in up would leave 64 bits).  route: 1 the phase-walking tiled kernel (D' in {1, 2, 3, 4, 5, 8, 10}, U' <= 16 and a tile that fits),
+ *   2 the direct one; 0 for NULL.  period_out / period_in / window: U', D', Wp (0 for NULL).
+ * enqueue (dsputils.rs:30-32, the contract above): launch only -- no allocation, no synchronisation, so capturable; every argument is
+ *   checked before anything is launched.  NULL handle, NULL, overlapping or not sample-aligned buffers (in != out) -> REDIO_ERR_ARG;
+ *   nout == 0 -> REDIO_OK, no launch.  Any whole-sample alignment is taken: 16-byte aligned buffers run the wide loads and stores, the
+ *   other paths give the same bits. */
+typedef struct redio_upfirdn redio_upfirdn;
+int redio_upfirdn_create(redio_upfirdn **h, const float *taps_host, size_t ntaps, size_t up, size_t down, unsigned flags);
+int redio_upfirdn_destroy(redio_upfirdn *h);
+size_t redio_upfirdn_nout(const redio_upfirdn *h, size_t n_in);
+int redio_upfirdn_route(const redio_upfirdn *h);
+size_t redio_upfirdn_period_out(const redio_upfirdn *h);
+size_t redio_upfirdn_period_in(const redio_upfirdn *h);
+size_t redio_upfirdn_window(const redio_upfirdn *h);
+int redio_upfirdn_enqueue(redio_upfirdn *h, const void *d_in, size_t n_in, void *d_out, void *stream);
+
 /* ---- lists of independent messages for one launch (redio_fft_enqueue_list, redio_chain_enqueue_list) ----
  * The reference runs one kissfft::fft per message of block_size samples (src/kissfft/src/kissfft.rs:20-27 asserts din.len() ==
  * block_size) and one chain per message from a block thread (src/ratpak.rs:60-185); a launch per small message costs a fixed floor
@@ -642,6 +673,18 @@ size_t redio_ddc_stream_nout(const redio_ddc_stream *h, size_t n_new);
 size_t redio_ddc_stream_pending(const redio_ddc_stream *h);
 int redio_ddc_stream_enqueue(redio_ddc_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
 uint64_t redio_ddc_stream_index(const redio_ddc_stream *h);
+/* the rational resampler as a stream (dsputils.rs:30-32, redio_upfirdn_*'s contract): the unit is one PERIOD -- U' outputs from the Wp
+ * samples that start at a multiple of D' samples of the stream, which is phase 0, so samples are carried and no phase.  The stream emits
+ * whole periods: after N samples in any pieces it has written the first U' * max(0, (N - Wp) / D' + 1) outputs of one
+ * redio_upfirdn_enqueue on the whole stream, bit for bit (that call may end with a few more outputs, which only the stateless call
+ * gives).  *nout and _stream_nout count samples. */
+typedef struct redio_upfirdn_stream redio_upfirdn_stream;
+int redio_upfirdn_stream_create(redio_upfirdn_stream **h, redio_upfirdn *plan);
+int redio_upfirdn_stream_destroy(redio_upfirdn_stream *h);
+int redio_upfirdn_stream_reset(redio_upfirdn_stream *h);
+size_t redio_upfirdn_stream_nout(const redio_upfirdn_stream *h, size_t n_new);
+size_t redio_upfirdn_stream_pending(const redio_upfirdn_stream *h);
+int redio_upfirdn_stream_enqueue(redio_upfirdn_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
 
 /* ---- A6: samplerate::resample's native side, src/samplerate/src/samplerate.rs:59-87 ----
  * nchan independent mono streams that share ratio and block lengths (the reference creates one

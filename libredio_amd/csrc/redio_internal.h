@@ -67,6 +67,12 @@ hipError_t launch_fir(const void *x, long n_in, const float *taps, bool taps_pal
 hipError_t launch_ddc(const void *x, bool u8, long n_in, unsigned first_mod, const float2 *tab, unsigned L, const float *taps, int K, long D, float2 *y,
                       long n_out, bool fused, hipStream_t s);
 
+// upfirdn_kernels.hip: the rational resampler.  x: n_in samples (f32, or cf32 with cplx); ph / taps: the plan's phase table and polyphase
+// taps (upfirdn_core.h) for K taps, up U, down D; y: n_out outputs, each with its whole window inside the n_in samples
+struct UpfirdnPhase;
+hipError_t launch_upfirdn(const void *x, long n_in, const UpfirdnPhase *ph, const float *taps, long K, long U, long D, void *y, long n_out, bool cplx,
+                          bool fused, hipStream_t s);
+
 // fft_kernels.hip
 constexpr int FFT_MAX_STAGES = 32;
 struct FftPlanDev {
@@ -208,7 +214,10 @@ inline int num_cus()
 } // namespace redio
 
 // plan shapes for the carried-history layer (stream_carry.hip); defined next to each plan struct
-struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real; struct redio_pspec; struct redio_pspec_real; struct redio_pfb_pspec; struct redio_ddc;
+struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real; struct redio_pspec; struct redio_pspec_real; struct redio_pfb_pspec; struct redio_ddc; struct redio_upfirdn;
+void redio_upfirdn_shape(const redio_upfirdn *h, size_t *period_out, size_t *period_in, size_t *window, unsigned *flags, int *device);
+// redio_upfirdn_enqueue for the carried-history layer: exactly `periods` periods (periods * period_out outputs) from n_in samples
+int redio_upfirdn_enqueue_periods(redio_upfirdn *h, const void *d_in, size_t n_in, size_t periods, void *d_out, void *stream);
 void redio_ddc_shape(const redio_ddc *h, size_t *ntaps, size_t *decim, int *device);
 void redio_fir_shape(const redio_fir *h, size_t *ntaps, size_t *decim, unsigned *flags, int *device);
 void redio_chain_shape(const redio_chain *h, size_t *ntaps, size_t *decim, int *nfft, int *device);

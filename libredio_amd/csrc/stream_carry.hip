@@ -14,6 +14,9 @@
 //     tuner        W = ntaps                       H = decim          unit = 1 output sample (from cf32 samples or u8 I/Q byte pairs); the
 //                  oscillator's phase is carried too: the layer knows the stream index of the head's and the body's first sample
 //                  (total_in - hist, and total_in + the samples of this call in front of the body) and hands it to the plan as first_index
+//     resampler    W = Wp                          H = D'             unit = 1 period of U' output samples (upfirdn_core.h); every window begins
+//                  at a multiple of D' samples of the stream, which is phase 0: samples are carried, no phase.  The plan is told how many
+//                  periods to produce: a stateless call on the same samples would write more than whole periods when U > D
 // so one layer serves them all.  The handle keeps the stream's unconsumed tail (fewer than W samples) on the device.
 // A call with n new samples
 //   1. appends the first min(n, W-1) new samples to the tail in a plan-owned staging buffer (one small copy),
@@ -59,7 +62,7 @@ hipError_t seam_copy(void *dst, const void *src, size_t bytes, hipStream_t st)
     SEAM_GO(uint8_t)
 #undef SEAM_GO
 }
-enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8, K_PSPEC_REAL, K_PFB_PSPEC, K_PFB_PSPEC_U8, K_DDC, K_DDC_U8 }; // _U8: the samples are interleaved u8 I/Q byte pairs
+enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8, K_PSPEC_REAL, K_PFB_PSPEC, K_PFB_PSPEC_U8, K_DDC, K_DDC_U8, K_UPFIRDN }; // _U8: the samples are interleaved u8 I/Q byte pairs
 struct Carry {
     int device = 0;
     Kind kind = K_FIR;
@@ -87,10 +90,12 @@ struct Entered { // holds Carry::busy for the life of a call
 using redio::StreamSplit;
 static StreamSplit split(const Carry &c, size_t n) { return redio::stream_split(c.hist, c.W, c.H, n); }
 
+// units: how many units the n_in samples are for (the resampler's periods; every other plan derives it from n_in);
 // first: the stream index of d_in's first sample (the tuner's phase; every other plan ignores it)
-int run(const Carry &c, const void *d_in, size_t n_in, unsigned long long first, void *d_out, void *stream)
+int run(const Carry &c, const void *d_in, size_t n_in, size_t units, unsigned long long first, void *d_out, void *stream)
 {
     switch (c.kind) {
+    case K_UPFIRDN: return redio_upfirdn_enqueue_periods((redio_upfirdn *)c.plan, d_in, n_in, units, d_out, stream);
     case K_DDC: return redio_ddc_enqueue((redio_ddc *)c.plan, d_in, n_in, first, d_out, stream);
     case K_DDC_U8: return redio_ddc_enqueue_u8((redio_ddc *)c.plan, d_in, 2 * n_in, first, d_out, stream);
     case K_FIR: return redio_fir_enqueue((redio_fir *)c.plan, d_in, n_in, d_out, stream);
@@ -173,11 +178,11 @@ int carry_enqueue(Carry *c, const void *d_new, size_t n, void *d_out, size_t *no
     if (c->hist > 0 && m > 0) REDIO_TRY(seam_copy(S + c->hist * c->in_elem, src, m * c->in_elem, st));
     char *out = (char *)d_out;
     if (s.nh) {
-        const int rc = run(*c, S, s.head_in, redio::stream_head_first(c->total_in, c->hist), out, stream);
+        const int rc = run(*c, S, s.head_in, s.nh, redio::stream_head_first(c->total_in, c->hist), out, stream);
         if (rc) return rc;
     }
     if (s.nb) {
-        const int rc = run(*c, src + s.off * c->in_elem, s.body_in, redio::stream_body_first(c->total_in, drop, s), out + s.nh * c->unit_out * c->out_elem, stream);
+        const int rc = run(*c, src + s.off * c->in_elem, s.body_in, s.nb, redio::stream_body_first(c->total_in, drop, s), out + s.nh * c->unit_out * c->out_elem, stream);
         if (rc) return rc;
     }
     // the new tail: everything from the start of the first unit not yet produced
@@ -231,6 +236,7 @@ struct redio_pspec_stream { Carry *c; };
 struct redio_pspec_real_stream { Carry *c; };
 struct redio_pfb_pspec_stream { Carry *c; };
 struct redio_ddc_stream { Carry *c; };
+struct redio_upfirdn_stream { Carry *c; };
 
 #define RD_STREAM_API(NAME)                                                                                                     \
     extern "C" int redio_##NAME##_stream_destroy(redio_##NAME##_stream *h)                                                      \
@@ -261,6 +267,7 @@ RD_STREAM_API(pspec)
 RD_STREAM_API(pspec_real)
 RD_STREAM_API(pfb_pspec)
 RD_STREAM_API(ddc)
+RD_STREAM_API(upfirdn)
 
 template <typename Hd>
 static int make(Hd **h, Kind kind, void *plan, int dev, size_t W, size_t H, size_t in_elem, size_t unit_out, size_t out_elem, uintptr_t align = 0)
@@ -421,3 +428,14 @@ static int make_ddc(redio_ddc_stream **h, redio_ddc *plan, bool u8)
 extern "C" int redio_ddc_stream_create(redio_ddc_stream **h, redio_ddc *plan) { return make_ddc(h, plan, false); }
 extern "C" int redio_ddc_stream_create_u8(redio_ddc_stream **h, redio_ddc *plan) { return make_ddc(h, plan, true); }
 extern "C" uint64_t redio_ddc_stream_index(const redio_ddc_stream *h) { return h ? h->c->total_in : 0; }
+// the rational resampler's stream: one period per unit, samples carried and no phase (every window starts on a multiple of D')
+extern "C" int redio_upfirdn_stream_create(redio_upfirdn_stream **h, redio_upfirdn *plan)
+{
+    if (!h) return REDIO_ERR_ARG;
+    *h = nullptr;
+    if (!plan) return REDIO_ERR_ARG;
+    size_t Up, Dp, Wp; unsigned flags; int dev;
+    redio_upfirdn_shape(plan, &Up, &Dp, &Wp, &flags, &dev);
+    const size_t el = (flags & REDIO_FIR_COMPLEX) ? 8 : 4;
+    return make(h, K_UPFIRDN, plan, dev, Wp, Dp, el, Up, el);
+}

@@ -117,6 +117,58 @@ class Ddc:
             self._h = None
 
 
+class Upfirdn:
+    """redio_upfirdn_*: the rational resampler -- up by `up`, the FIR of dsputils::convolve (dsputils.rs:30-32), down by `down`, as a
+    polyphase FIR over the original samples: bit for bit the fold over the taps that meet a sample, the stuffed zeros skipped.
+    float32 streams, or complex64 with complex_input."""
+
+    def __init__(self, taps, up, down, complex_input=False, fused=False):
+        t, p = _taps(taps)
+        self.ntaps, self.up, self.down, self.complex_input = len(t), int(up), int(down), complex_input
+        flags = (REDIO_FIR_COMPLEX if complex_input else 0) | (REDIO_FIR_FUSED if fused else 0)
+        self._h = C.c_void_p()
+        check(lib().redio_upfirdn_create(C.byref(self._h), p, len(t), self.up, self.down, flags), "upfirdn_create")
+
+    def nout(self, n_in):
+        return lib().redio_upfirdn_nout(self._h, n_in)
+
+    @property
+    def route(self):
+        """redio_upfirdn_route: 1 the phase-walking tiled kernel, 2 the direct one."""
+        return lib().redio_upfirdn_route(self._h)
+
+    @property
+    def period_out(self):
+        """U' = up / gcd(up, down): outputs per period"""
+        return lib().redio_upfirdn_period_out(self._h)
+
+    @property
+    def period_in(self):
+        """D' = down / gcd(up, down): new samples per period"""
+        return lib().redio_upfirdn_period_in(self._h)
+
+    @property
+    def window(self):
+        """Wp: samples one period reads"""
+        return lib().redio_upfirdn_window(self._h)
+
+    def __call__(self, x, out=None):
+        import torch
+        want = torch.complex64 if self.complex_input else torch.float32
+        assert x.dtype == want, f"expected {want}"
+        n = self.nout(x.numel())
+        if out is None:
+            out = torch.empty(n, dtype=want, device=x.device)
+        assert out.dtype == want and out.numel() >= n
+        check(lib().redio_upfirdn_enqueue(self._h, _dev_ptr(x), x.numel(), _dev_ptr(out), current_stream()), "upfirdn_enqueue")
+        return out[:n]
+
+    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
+        if getattr(self, "_h", None):
+            _safe_destroy("redio_upfirdn_destroy", self._h)
+            self._h = None
+
+
 class Fft:
     """redio_fft_*: batched kissfft::fft blocks (kissfft.rs:18-31), unnormalised."""
 
@@ -315,16 +367,17 @@ class Chain:
 
 
 class Stream:
-    """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec,pspec_real,pfb_pspec}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
+    """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec,pspec_real,pfb_pspec,ddc,upfirdn}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
     segmentation of the input gives the bits of one stateless call on the whole stream (the stateless plans keep the
     reference's per-message semantics, dsputils.rs:30-32).  `plan` is a Fir, Chain, Channelizer, OverlapSave, OverlapSaveReal, PowerSpectrum
     (complex64 in, float32 rows out), PowerSpectrumReal (float32 in, float32 rows out), PolyphaseSpectrum (complex64 in, float32 rows
-    of nchan out) or Ddc (the tuner: the oscillator's phase is carried with the history)."""
+    of nchan out), Ddc (the tuner: the oscillator's phase is carried with the history) or Upfirdn (whole periods of period_out samples
+    from the window that starts at a multiple of period_in samples of the stream)."""
 
     def __init__(self, plan, u8=False):
         """u8=True (Chain, Channelizer, PowerSpectrum, PolyphaseSpectrum and Ddc): the stream arrives as the receiver's interleaved u8 I/Q
         bytes (uint8 tensors, two bytes per sample; redio_{chain,pfb,pspec,pfb_pspec}_stream_create_u8)."""
-        kind = {Fir: "fir", Chain: "chain", Ddc: "ddc"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec", "PowerSpectrumReal": "pspec_real", "PolyphaseSpectrum": "pfb_pspec"}[type(plan).__name__]
+        kind = {Fir: "fir", Chain: "chain", Ddc: "ddc", Upfirdn: "upfirdn"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec", "PowerSpectrumReal": "pspec_real", "PolyphaseSpectrum": "pfb_pspec"}[type(plan).__name__]
         assert not u8 or kind in ("chain", "pfb", "pspec", "pfb_pspec", "ddc")
         self._kind, self._plan, self._u8 = kind, plan, bool(u8)          # the plan must outlive the stream handle
         self._h = C.c_void_p()
@@ -352,7 +405,7 @@ class Stream:
         """Feed the next piece of the stream; returns the output samples that became computable (flat tensor; the
         chain's are whole spectra of nfft samples, the channelizer's whole rows of nchan samples)."""
         import torch
-        real = self._kind in ("ovsave_real", "pspec_real") or (self._kind == "fir" and not self._plan.complex_input)
+        real = self._kind in ("ovsave_real", "pspec_real") or (self._kind in ("fir", "upfirdn") and not self._plan.complex_input)
         want = torch.float32 if real else torch.complex64
         if self._u8:
             assert x.dtype == torch.uint8 and x.numel() % 2 == 0, "expected an even number of uint8 bytes"

@@ -1,5 +1,5 @@
 """Throughput of the non-headline configs of BASELINE.json on one MI355X (own measurements; bench.py
-stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit|pfbpspecp2|pfbpspecp2split|ddc|ddcu8]..."""
+stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit|pfbpspecp2|pfbpspecp2split|ddc|ddcu8|upfirdn]..."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, libredio_amd as R
@@ -614,6 +614,40 @@ if "trigger" in which:
     bufs = trig.feed(blocks)
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
     print(f"trigger over {ns} samples ({blocks.shape[0]} blocks): {dt*1e3:.2f} ms  {ns/dt/1e9:.1f} GS/s, {len(bufs)} buffers emitted, {sum(b.numel() for b in bufs)} samples kept")
+if "upfirdn" in which:
+    # the rational resampler (redio_upfirdn_*: up U, FIR, down D as a polyphase FIR over the original samples) on 2^28 cf32 input samples,
+    # fused fold, against the composition it replaces, timed alternately (twice each, the smaller time printed) in this one process:
+    # zero-stuff into a U-times buffer (a strided copy into a buffer zeroed ONCE outside the timing: a head start for the old route),
+    # then redio_fir(K, D).  Share of 8 TB/s on the algorithmic bytes, 8 + 8 D / U per output.  160/147 would need a 320 GiB
+    # zero-stuffed buffer at 2^28 samples: its ratio is taken at 2^22 samples, both sides, and its own time at 2^28 as well.
+    x = R.synth_iq(1, 0, n)
+    for U, D, K in ((2, 1, 63), (3, 2, 96), (2, 3, 63), (4, 5, 127), (1, 5, 127), (160, 147, 3841)):
+        taps = R.dsputils.lpf_corrected(K, 0.4 / max(U, D))
+        plan = R.Upfirdn(taps, U, D, complex_input=True, fused=True)
+        fir = R.Fir(taps, D, fused=True)
+        out = torch.empty(plan.nout(n), dtype=torch.complex64, device="cuda")
+        b = 8 + 8 * D / U
+        ms = timeit(lambda: plan(x, out=out), n=10, warm=3)
+        nc = n if U <= 4 else 1 << 22  # the samples of the comparison
+        xc = x[:nc]
+        z = torch.zeros(nc * U, dtype=torch.complex64, device="cuda") if U > 1 else None
+        outc = out[: plan.nout(nc)]
+
+        def old():
+            if U > 1:
+                z[::U].copy_(xc)
+                fir(z, out=outc)
+            else:
+                fir(xc, out=outc)
+        ms_new = ms_old = 1e30
+        for _ in range(2):
+            ms_new = min(ms_new, timeit(lambda: plan(xc, out=outc), n=10, warm=3))
+            ms_old = min(ms_old, timeit(old, n=5, warm=2))
+        what = "zero-stuff + fir" if U > 1 else "fir alone (no bar)"
+        print(f"UPFIRDN {U}/{D} {K} taps (route {plan.route}, U'={plan.period_out} D'={plan.period_in} Wp={plan.window}): {ms:.3f} ms  "
+              f"{out.numel()/ms/1e6:.1f} GS/s out  {b*out.numel()/ms/1e6:.0f} GB/s algorithmic ({b*out.numel()/ms/1e6/8000:.1%} of 8 TB/s) | "
+              f"at {nc} samples: {ms_new:.3f} ms against {what}: {ms_old:.3f} ms, resampler / composition = {ms_new/ms_old:.3f}")
+        del plan, fir, out, outc, z
 if "ddc" in which or "ddcu8" in which:
     # the tuner (redio_ddc_*: oscillator mix fused into the FIR tile load) on 2^28 samples against the route it replaces, timed alternately
     # (twice each, the smaller time printed) in this one process: (a) redio_mul_c32 on a PRE-MATERIALISED oscillator stream (its
