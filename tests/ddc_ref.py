@@ -9,18 +9,49 @@ import oracle
 MAX_PERIOD = 65536
 
 
-def tile_out(ntaps, decim):
-    """outputs one workgroup produces on the route of (ntaps, decim): 256 lanes x outputs per lane (DESIGN.md 5.2b)"""
-    if ntaps in (127, 63) and decim in (1, 5):
-        return 256 * (8 if decim == 1 else 4)
-    r = {1: 8, 2: 4, 3: 4, 4: 4, 5: 4, 8: 2, 10: 2}.get(decim)
-    return 256 * r if r else 256
+CHUNKED_R = {1: 8, 2: 4, 3: 4, 4: 4, 5: 4, 8: 2, 10: 2}  # outputs per lane of the chunked route (ddc_chunked_r)
+CHUNKED_LDS_MAX = 150 * 1024                              # bytes: beyond it the direct kernel runs
+TABLE_EXT = 20480                                         # entries behind the period in the device table (DDC_TABLE_EXT)
+
+
+def chw(decim):
+    """whole-chunk size of the chunked route (ddc_chunked_chw)"""
+    return 24 if decim == 3 else 40 if decim in (5, 10) else 16
+
+
+def tile_in(ntaps, decim):
+    """samples one workgroup of the chunked route stages (ddc_chunked_tile_in)"""
+    return (256 * CHUNKED_R[decim] - 1) * decim + (ntaps + 15) // 16 * 16
+
+
+def lds_elems(ntaps, decim):
+    """cf32 elements of its LDS: the tile, the tail of the last 16-byte load, the pad, the output transpose (ddc_chunked_lds_elems)"""
+    r = CHUNKED_R[decim]
+    t, lstr = tile_in(ntaps, decim) + 4, r * decim
+    return max(t + (t // lstr if lstr % 2 == 0 else 0) + 2, 256 * (r + 1))
 
 
 def route(ntaps, decim):
     if ntaps in (127, 63) and decim in (1, 5):
         return 1
-    return 2 if decim in (1, 2, 3, 4, 5, 8, 10) else 3
+    return 2 if decim in CHUNKED_R and ntaps <= 2 ** 20 and lds_elems(ntaps, decim) * 8 <= CHUNKED_LDS_MAX else 3
+
+
+def tile_out(ntaps, decim):
+    """outputs one workgroup produces on the route of (ntaps, decim): 256 lanes x outputs per lane (DESIGN.md 5.2b)"""
+    r = route(ntaps, decim)
+    if r == 1:
+        return 256 * (8 if decim == 1 else 4)
+    return 256 * CHUNKED_R[decim] if r == 2 else 256
+
+
+def last_chunked(decim):
+    """the largest tap count the chunked route takes at this decimation (lds_elems never falls as the taps grow)"""
+    lo, hi = 1, 2 ** 20
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if lds_elems(mid, decim) * 8 <= CHUNKED_LDS_MAX else (lo, mid - 1)
+    return lo
 
 
 def tiled(w, first, n):

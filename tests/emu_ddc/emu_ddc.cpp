@@ -15,11 +15,15 @@ struct Call {
     float2 *image, *y; int *tile_in, *tile_out, *bad;
 };
 
-// the image with a fence: a write outside [0, elems) is counted, never performed
+// the LDS image: exactly `elems` elements between two fences of NaN, FENCE elements each.  A write outside [0, elems) is counted, never
+// performed; a lane program that reads outside computes NaN from the fence
+constexpr long FENCE = 8192;
 struct Image {
-    std::vector<float2> xs; int *bad;
-    Image(long elems, int *b) : xs((size_t)elems, make_float2(NAN, NAN)), bad(b) {}
-    void put(long i, float2 v) { if (i < 0 || i >= (long)xs.size()) ++*bad; else xs[(size_t)i] = v; }
+    std::vector<float2> all; long elems; int *bad;
+    Image(long n, int *b) : all((size_t)(n + 2 * FENCE), make_float2(NAN, NAN)), elems(n), bad(b) {}
+    float2 *data() { return all.data() + FENCE; }
+    float2 at(long i) { return data()[i]; }
+    void put(long i, float2 v) { if (i < 0 || i >= elems) ++*bad; else data()[i] = v; }
 };
 
 template <bool U8, bool STREAM, typename Index>
@@ -38,14 +42,15 @@ void tiled(const Call &c)
     constexpr int TILE_OUT = 256 * R, TILE_IN = G::tile_in(TILE_OUT);
     Image im(G::lds_elems(TILE_OUT), c.bad);
     load<U8, false>(c, c.tile * TILE_OUT * D, TILE_IN, im, [](int n) { return (long)G::lds_index(n); });
-    for (int n = 0; n < TILE_IN; ++n) c.image[n] = im.xs[G::lds_index(n)];
+    for (int n = 0; n < TILE_IN; ++n) c.image[n] = im.at(G::lds_index(n));
+    *c.tile_in = TILE_IN; *c.tile_out = TILE_OUT;
+    if (!c.y) return;
     for (int tid = 0; tid < 256; ++tid) {
         float2 acc[R];
         for (int r = 0; r < R; ++r) acc[r] = make_float2(0.f, 0.f);
-        fir_lane<float2, K, D, R, FUSED>(im.xs.data(), tid, c.taps, acc);
+        fir_lane<float2, K, D, R, FUSED>(im.data(), tid, c.taps, acc);
         for (int r = 0; r < R; ++r) c.y[tid * R + r] = acc[r];
     }
-    *c.tile_in = TILE_IN; *c.tile_out = TILE_OUT;
 }
 
 template <bool U8, bool FUSED, int D>
@@ -56,27 +61,29 @@ void chunked(const Call &c)
     const int tile_in = (int)ddc_chunked_tile_in(c.K, D, R);
     Image im(ddc_chunked_lds_elems(c.K, D, R), c.bad);
     load<U8, (D >= 2)>(c, c.tile * TILE_OUT * D, tile_in, im, [](int n) { return (long)(PAD ? n + n / LSTR : n); });
-    for (int n = 0; n < tile_in; ++n) c.image[n] = im.xs[PAD ? n + n / LSTR : n];
+    for (int n = 0; n < tile_in; ++n) c.image[n] = im.at(PAD ? n + n / LSTR : n);
+    *c.tile_in = tile_in; *c.tile_out = TILE_OUT;
+    if (!c.y) return;
     for (int tid = 0; tid < 256; ++tid) {
         float2 acc[R];
         for (int r = 0; r < R; ++r) acc[r] = make_float2(0.f, 0.f);
-        fir_chunks<float2, D, R, FUSED, CHW>(im.xs.data(), tid * (LSTR + (PAD ? 1 : 0)), c.K, c.taps, acc);
+        fir_chunks<float2, D, R, FUSED, CHW>(im.data(), tid * (LSTR + (PAD ? 1 : 0)), c.K, c.taps, acc);
         for (int r = 0; r < R; ++r) c.y[tid * R + r] = acc[r];
     }
-    *c.tile_in = tile_in; *c.tile_out = TILE_OUT;
 }
 
 template <bool U8, bool FUSED>
 void direct(const Call &c)
 {
     const long n_out = c.n_in < c.K ? 0 : (c.n_in - c.K) / c.D + 1;
+    *c.tile_in = 0; *c.tile_out = 256;
+    if (!c.y) return;
     for (int tid = 0; tid < 256; ++tid) {
         const long i = c.tile * 256 + tid;
         if (i >= n_out) { c.y[tid] = make_float2(0.f, 0.f); continue; }
         const unsigned idx0 = ddc_base(ddc_first_mod(c.first, c.L), (unsigned long long)(i * c.D), c.L);
         c.y[tid] = ddc_direct_output<U8, FUSED>(c.x + i * c.D * (U8 ? 2 : 8), idx0, c.tab, c.L, c.taps, c.K);
     }
-    *c.tile_in = 0; *c.tile_out = 256;
 }
 
 template <bool U8, bool FUSED>
@@ -109,11 +116,15 @@ extern "C" {
 
 int emu_ddc_table_ext(void) { return DDC_TABLE_EXT; }
 int emu_ddc_route(long K, long D) { return ddc_route(K, D); }
+// the chunked route's geometry as the headers have it; 0 where the decimation has no chunked form
+long emu_ddc_chunked_tile_in(long K, long D) { return ddc_chunked_r(D) ? ddc_chunked_tile_in((int)K, D, ddc_chunked_r(D)) : 0; }
+long emu_ddc_chunked_lds_elems(long K, long D) { return ddc_chunked_r(D) ? ddc_chunked_lds_elems((int)K, D, ddc_chunked_r(D)) : 0; }
+int emu_ddc_chunked_chw(long D) { return ddc_chunked_chw(D); }
 
 // One workgroup (`tile`) of a call on n_in samples at x (cf32, or u8 I/Q bytes), first_index `first`.  tab: the device table's layout,
 // L + emu_ddc_table_ext() entries (the caller may append a fence behind it).  image: the tile's samples as the lane program sees them, in
 // tile order (read back through the image's index map; NaN where the loader wrote nothing); y: the workgroup's outputs, zero-filled
-// samples included.  *bad counts image writes outside the allocation.  Returns the route.
+// samples included; y == NULL runs the loader alone.  *bad counts image writes outside the allocation.  Returns the route.
 int emu_ddc_tile(int K, long D, int u8, int fused, const void *x, long n_in, unsigned long long first, const float *tab, unsigned L, const float *taps,
                  long tile, int vec_x, float *image, float *y, int *tile_in, int *tile_out, int *bad)
 {

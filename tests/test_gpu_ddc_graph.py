@@ -20,7 +20,8 @@ def bits(a):
 
 
 @pytest.mark.parametrize("u8", [False, True])
-@pytest.mark.parametrize("K,D", [(127, 5), (31, 2), (5, 9)])
+@pytest.mark.parametrize("K,D", [(127, 5), (31, 2), (5, 9),
+                                 (15008, 1)])  # the chunked route's longest tile, 150 KiB: its first enqueue ever is the captured one
 def test_capture_and_replay_and_no_allocation(gpu, redio, oracle, K, D, u8):
     L, first = 4099, 2 ** 32 + 5
     n = 2 * ref.tile_out(K, D) * D + K + 5

@@ -20,7 +20,8 @@ def bits(a):
 
 
 @pytest.mark.parametrize("cplx", [False, True])
-@pytest.mark.parametrize("U,D,K,route", [(3, 2, 64, 1), (16, 1, 255, 1), (3, 16, 33, 2)])
+@pytest.mark.parametrize("U,D,K,route", [(3, 2, 64, 1), (16, 1, 255, 1), (3, 16, 33, 2),
+                                         (2, 1, 25396, 1)])  # a tile above 48 KiB as f32 and as cf32: its first enqueue ever is the captured one
 def test_capture_and_replay_and_no_allocation(gpu, redio, oracle, U, D, K, route, cplx):
     n = ref.n_for(2 * ref.tile_out(K, U, D) + 5, K, U, D)
     taps = oracle.synth_f32(3, K, K)

@@ -54,12 +54,13 @@ def streams(oracle):
 
 @pytest.mark.parametrize("style", ["one", "tiny", "small", "mixed"])
 @pytest.mark.parametrize("cplx", [False, True])
-@pytest.mark.parametrize("U,D,K,fused", [(2, 1, 63, True), (3, 2, 64, False), (16, 1, 255, True), (17, 1, 40, False), (2, 7, 9, True)])
+@pytest.mark.parametrize("U,D,K,fused", [(2, 1, 63, True), (3, 2, 64, False), (16, 1, 255, True), (17, 1, 40, False), (2, 7, 9, True),
+                                         (2, 1, 11776, False)])  # a window of 5889 samples in a tile of 85536 bytes
 def test_any_segmentation_is_the_prefix_of_the_one_call_result(gpu, redio, streams, U, D, K, fused, cplx, style):
     rng = np.random.default_rng(K * 131 + D + U)
     Up, Dp = ref.periods(U, D)
     Wp = ref.window(K, U, D)
-    n = 1500 if style == "tiny" else 30000
+    n = max(1500, Wp + 1500) if style == "tiny" else 30000  # the long window: 1500 samples behind it
     taps, xh, want = streams(U, D, K, cplx, n)
     total = Up * ((n - Wp) // Dp + 1)
     assert total <= len(want[fused])

@@ -54,6 +54,37 @@ def route(K, U, D):
     return 1 if Dp in TILED_D and Up <= TILED_MAX_PERIOD_OUT and K <= 2 ** 20 and periods_per_lane(K, U, D) else 2
 
 
+def lane_pass(K, U, D):
+    """(R, pass) of periods_per_lane: pass 1 inside LDS_WANT, pass 2 inside LDS_MAX; (0, 0) where no tile fits"""
+    for pas, limit in ((1, LDS_WANT), (2, LDS_MAX)):
+        for R in ((4, 2, 1) if periods(U, D)[1] < 8 else (2, 1)):
+            if lds_elems(R, K, U, D) * 8 <= limit:
+                return R, pas
+    return 0, 0
+
+
+def regimes(U, D, kmax=2 ** 20):
+    """[(first K, R, pass, route)] over K in [1, kmax]: a new row wherever (R, pass, route) changes.  lds_elems never falls as K grows,
+    so each (R, limit) fits up to one K found by bisection, and nothing changes between those."""
+    edges = {1}
+    for limit in (LDS_WANT, LDS_MAX):
+        for R in (4, 2, 1):
+            if lds_elems(R, 1, U, D) * 8 > limit:
+                continue
+            lo, hi = 1, kmax
+            while lo < hi:
+                mid = (lo + hi + 1) // 2
+                lo, hi = (mid, hi) if lds_elems(R, mid, U, D) * 8 <= limit else (lo, mid - 1)
+            if lo < kmax:
+                edges.add(lo + 1)
+    rows = []
+    for K in sorted(edges):
+        row = lane_pass(K, U, D) + (route(K, U, D),)
+        if not rows or rows[-1][1:] != row:
+            rows.append((K,) + row)
+    return rows
+
+
 def tile_out(K, U, D):
     """outputs one workgroup produces: 256 lanes x R periods x U' on route 1, 256 on route 2"""
     return 256 * periods_per_lane(K, U, D) * periods(U, D)[0] if route(K, U, D) == 1 else 256
