@@ -4,8 +4,8 @@
 // (src/dsputils/src/dsputils.rs:30-32):
 //   m[n] = cmul_rn(x[n], w[(first + n) mod L])     every operation rounded on its own, never contracted
 //   y[i] = the FIR fold over m[i*D + j] * h[j]     (fir_core.h: strict tap order; FUSED selects fmaf for the fold only)
-// The loader writes m into the SAME padded LDS image the FIR kernels stage, so fir_lane (fir_core.h) and fir_chunks (fir_chunks.h)
-// run on it unchanged.  The u8 entry converts each byte with i2f (redio_device.h: the arithmetic of redio_data_to_samples) first.
+// The loader writes m into the SAME padded LDS image the FIR kernels stage (fir_tile.h), so the FIR's two tiled kernel bodies
+// (fir_tile_kernels.h) run with it as their loader policy (DdcTile below) and nothing else changed.  The u8 entry converts each byte with i2f (redio_device.h: the arithmetic of redio_data_to_samples) first.
 //
 // Table index.  The device table holds the period's L entries and then repeats them for DDC_TABLE_EXT more (entry e = w[e mod L]).
 // A workgroup takes ONE 64-bit modulo, base = (first + in0) mod L for its tile's first sample in0; a lane then reads entry
@@ -18,6 +18,7 @@
 // Host-compilable (tests/emu_ddc runs every thread of a workgroup's loader on the CPU).
 #pragma once
 #include "fir_core.h"
+#include "fir_tile.h"
 
 namespace redio {
 
@@ -28,18 +29,12 @@ RD_HD unsigned ddc_first_mod(unsigned long long first, unsigned L) { return (uns
 // table entry of tile sample 0: (first + in0) mod L from first mod L, without overflow for any first
 RD_HD unsigned ddc_base(unsigned first_mod, unsigned long long in0, unsigned L) { return (unsigned)(((unsigned long long)first_mod + in0 % L) % L); }
 
-// The any-taps chunked route's shape per decimation -- launch_fir_t's table (fir_kernels.hip): outputs per lane R and whole-chunk size CHW
-RD_HD constexpr int ddc_chunked_r(long D) { return D == 1 ? 8 : (D >= 2 && D <= 5) ? 4 : (D == 8 || D == 10) ? 2 : 0; } // 0: no chunked form
-RD_HD constexpr int ddc_chunked_chw(long D) { return D == 3 ? 24 : (D == 5 || D == 10) ? 40 : 16; }
-// its tile (256 lanes): samples staged, and cf32 elements of LDS including the pad, the tail of the last 16-byte load and the output transpose
-RD_HD constexpr long ddc_chunked_tile_in(int K, long D, int R) { return (256L * R - 1) * D + (K + 15) / 16 * 16; }
-RD_HD constexpr long ddc_chunked_lds_elems(int K, long D, int R)
-{
-    const long t = ddc_chunked_tile_in(K, D, R) + 4, lstr = R * D;
-    const long e = t + (lstr % 2 == 0 ? t / lstr : 0) + 2;
-    return e < 256L * (R + 1) ? 256L * (R + 1) : e;
-}
-constexpr long DDC_CHUNKED_LDS_MAX = 150 * 1024; // bytes: beyond it the direct kernel runs (as launch_chunked decides)
+// The any-taps chunked route's shape under the tuner's names: the shared table and tile of fir_tile.h, nothing of its own
+RD_HD constexpr int ddc_chunked_r(long D) { return tile_r(D); } // 0: no chunked form
+RD_HD constexpr int ddc_chunked_chw(long D) { return tile_chw(D); }
+RD_HD constexpr long ddc_chunked_tile_in(int K, long D, int R) { return tile_in(R, D, tile_window(K)); }
+RD_HD constexpr long ddc_chunked_lds_elems(int K, long D, int R) { return tile_lds_elems(R, D, tile_window(K)); }
+constexpr long DDC_CHUNKED_LDS_MAX = TILE_LDS_MAX; // bytes: beyond it the direct kernel runs
 // redio_ddc_route: 1 specialised tiled (127 and 63 taps at /5 and /1), 2 any-taps chunked, 3 direct
 RD_HD constexpr int ddc_route(long K, long D)
 {
@@ -50,20 +45,6 @@ RD_HD constexpr int ddc_route(long K, long D)
 
 // one u8 I/Q sample (rtlsdr.rs:159-162), mixed
 RD_HD float2 ddc_mix_u8(unsigned bi, unsigned bq, float2 w) { return cmul_rn(make_float2(i2f(bi), i2f(bq)), w); }
-
-// 16-byte loads behind a policy so that the host build has plain ones
-template <bool STREAM>
-RD_HD float4 ddc_ld16(const float4 *p)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (STREAM) {
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p));
-        return make_float4(v.x, v.y, v.z, v.w);
-    }
-#endif
-    return *p;
-}
 
 // two consecutive table entries from tab + n (n even): one 16-byte load when the workgroup's base is even
 RD_HD void ddc_tab2(const float2 *tab, int n, bool tab_vec, float2 &w0, float2 &w1)
@@ -97,8 +78,8 @@ RD_HD void ddc_load_thread(int tid, int NT, const void *x, long left, const floa
         const int nv = (tile_in + 1) / 2;
         int vfirst = tid;
         if (2L * nv <= left) {
-            // the whole tile exists (workgroup-uniform): LB sample loads and LB table loads in flight per lane, no bound checks --
-            // fir_chunked_kernel's fast path; the guarded loop below takes what is left
+            // the whole tile exists (workgroup-uniform): LB sample loads and LB table loads in flight per lane, no bound checks, for
+            // as long as all LB exist; the guarded loop below takes what is left
             constexpr int LB = U8 ? 2 : 4; // u8: four in flight cost ddc_tiled_kernel<63, 5> from bytes its eighth wave per SIMD (65 VGPRs)
             for (; vfirst + (LB - 1) * NT < nv; vfirst += LB * NT) {
                 float4 q[LB];   // cf32: two samples
@@ -108,7 +89,7 @@ RD_HD void ddc_load_thread(int tid, int NT, const void *x, long left, const floa
                 for (int b = 0; b < LB; ++b) {
                     const int v = vfirst + b * NT;
                     if constexpr (U8) u[b] = reinterpret_cast<const unsigned *>(xb)[v];
-                    else q[b] = ddc_ld16<STREAM>(reinterpret_cast<const float4 *>(xc) + v);
+                    else q[b] = tile_ld16<STREAM>(reinterpret_cast<const float4 *>(xc) + v);
                 }
 #pragma unroll
                 for (int b = 0; b < LB; ++b) ddc_tab2(tab, 2 * (vfirst + b * NT), tab_vec, w0[b], w1[b]);
@@ -131,7 +112,7 @@ RD_HD void ddc_load_thread(int tid, int NT, const void *x, long left, const floa
                     x0 = make_float2(i2f(q & 255u), i2f((q >> 8) & 255u));
                     x1 = make_float2(i2f((q >> 16) & 255u), i2f(q >> 24));
                 } else {
-                    const float4 q = ddc_ld16<STREAM>(reinterpret_cast<const float4 *>(xc) + v);
+                    const float4 q = tile_ld16<STREAM>(reinterpret_cast<const float4 *>(xc) + v);
                     x0 = make_float2(q.x, q.y); x1 = make_float2(q.z, q.w);
                 }
                 ddc_tab2(tab, n, tab_vec, w0, w1);
@@ -147,6 +128,21 @@ RD_HD void ddc_load_thread(int tid, int NT, const void *x, long left, const floa
         for (int n = tid; n < tile_in; n += NT) one(n);
     }
 }
+
+// The loader as the policy of the FIR's two tiled kernel bodies (fir_tile_kernels.h).  x: the call's first sample (u8: byte); vec_in: x
+// is 16-byte (u8: 4-byte) aligned.  LB is the plain loader's: ddc_load_thread keeps its own count in flight
+template <bool U8>
+struct DdcTile {
+    using sample_t = float2;
+    const void *x; long n_in; unsigned first_mod; const float2 *tab; unsigned L; int vec_in;
+    template <bool STREAM, int LB, typename Put>
+    RD_HD void load(int tid, long in0, int tile_in, Put &&put) const
+    {
+        const unsigned base = ddc_base(first_mod, (unsigned long long)in0, L); // wave-uniform: the workgroup's one modulo
+        ddc_load_thread<U8, STREAM>(tid, 256, reinterpret_cast<const char *>(x) + in0 * (U8 ? 2 : 8), n_in - in0, tab + base, tile_in, vec_in != 0,
+                                    (base & 1u) == 0, put);
+    }
+};
 
 // the direct form: output i of a call, any K and D, no tile; idx0 = (first + i*D) mod L, one modulo, then wrap by compare
 template <bool U8, bool FUSED>

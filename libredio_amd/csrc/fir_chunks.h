@@ -1,19 +1,11 @@
-// fir_chunks.h -- the chunked lane program of the any-taps tiled FIR kernel (fir_kernels.hip), shared with the tuner's kernels
-// (ddc_kernels.hip): both run it on the same padded LDS image.  Host-compilable (tests/emu_ddc): the device-only window reads
+// fir_chunks.h -- the chunked lane program of the any-taps tiled FIR kernel (fir_tile_kernels.h), which the tuner instantiates with its
+// own loader on the same padded LDS image (fir_tile.h).  Host-compilable (tests/emu_fir, tests/emu_ddc): the device-only window reads
 // are behind __HIP_DEVICE_COMPILE__.
 #pragma once
 #include "fir_core.h"
 
 namespace redio {
 
-#if defined(__HIPCC__)
-typedef float fir_v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 fir_nt_ld(const float4 *p)
-{
-    const fir_v4f v = __builtin_nontemporal_load(reinterpret_cast<const fir_v4f *>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-#endif
 // ---- chunked tiled kernel: ANY tap count, decimation from a small compile-time set ---------------
 // The register blocking of fir_core.h needs compile-time tap indices; here the taps are walked in chunks of
 // CH = 16 with a run-time chunk count instead: per chunk a lane reads the CH + (R-1)*D samples its R outputs

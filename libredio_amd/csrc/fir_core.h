@@ -13,6 +13,7 @@
 //
 // Host-compilable (tests/emu).
 #pragma once
+#include "fir_tile.h"
 #include "redio_device.h"
 #ifndef REDIO_EXP_ABLATE
 #define REDIO_EXP_ABLATE 0
@@ -28,7 +29,7 @@ struct FirGeom {
     static constexpr bool PAD = (LSTR % 2) == 0;   // LDS lane stride must be odd (in elements) so
                                                    // that 32 lanes hit 32 different bank pairs
     // LDS element index of tile-relative input sample n
-    RD_HD static constexpr int lds_index(int n) { return PAD ? n + n / LSTR : n; }
+    RD_HD static constexpr int lds_index(int n) { return tile_image_index(n, LSTR); }
     RD_HD static constexpr int tile_in(int tile_out) { return (tile_out - 1) * D + K; }
     RD_HD static constexpr int lds_elems(int tile_out) { return lds_index(tile_in(tile_out) - 1) + 1; }
 };
@@ -453,7 +454,7 @@ struct FirGeomPairs {
     static constexpr bool PAD = (LSTR % 2) == 0;
     static constexpr int LANE_STRIDE = LSTR + (PAD ? 1 : 0);
     static constexpr int NPAIR = R / 2 + (K - 1) / 2 + ((K - 1) % 2 ? 1 : 0); // pair slots m one lane reads from EACH copy: m < R/2 + ceil((K-1)/2)
-    RD_HD static constexpr int lds_index(int m) { return PAD ? m + m / LSTR : m; }
+    RD_HD static constexpr int lds_index(int m) { return tile_image_index(m, LSTR); }
     RD_HD static constexpr int tile_in(int tile_out) { return tile_out - 1 + K; }
     // float2 elements of ONE copy for a tile of tile_out outputs: the tile is staged in whole 16-byte loads (four samples = two
     // elements of either copy), so a copy holds 2 * ceil(tile_in / 4) elements

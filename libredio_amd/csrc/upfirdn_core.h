@@ -1,5 +1,6 @@
 // upfirdn_core.h -- the rational resampler (include/redio.h, redio_upfirdn_*): up by U, FIR, down by D as a polyphase FIR over the
-// ORIGINAL samples.  Phase arithmetic, tile geometry, the route predicate, the tile loader, the phase program and the direct form.
+// ORIGINAL samples.  Phase arithmetic, the route predicate, the phase program and the direct form; the tile's geometry, its loader and
+// its store loop are the FIR's (fir_tile.h) with the window Wp in place of the padded tap count.
 //
 // Arithmetic contract (a stated design; the fold is dsputils::convolve's, src/dsputils/src/dsputils.rs:30-32):
 //   z = x with U - 1 zeros behind every sample; y[i] = acc after acc = +0; for j = 0 .. K-1 ascending, ONLY where (i D + j) mod U == 0:
@@ -12,18 +13,18 @@
 //
 // Route 1 maps LANES TO PERIODS, not to consecutive outputs: in one phase every lane of a wave then uses the same sub-filter, so
 // {s, K(r), taps} are wave-uniform, arrive by scalar loads, and the taps sit in SGPRs as in fir_chunks.h.  A 256-lane workgroup stages
-// the (256 R - 1) D' + Wp samples of its 256 R periods once (fir_chunked_kernel's padded image), walks the U' phases over it, and the
+// the tile_in(R, D', Wp) samples of its 256 R periods once (the padded image of fir_tile.h), walks the U' phases over it, and the
 // outputs -- U' apart in memory within a phase -- leave through an LDS tile as contiguous 16-byte stores.
 //
 // Host-compilable (tests/emu_upfirdn runs every thread of a workgroup on the CPU).
 #pragma once
-#include "ddc_core.h" // ddc_ld16: the 16-byte load behind a policy
+#include "fir_tile.h"
 
 namespace redio {
 
 constexpr long UPFIRDN_MAX_UP = 65536;
 constexpr long UPFIRDN_MAX_TAPS = 1L << 24;
-constexpr long UPFIRDN_LDS_MAX = 150 * 1024;  // bytes: the chunked kernels' budget
+constexpr long UPFIRDN_LDS_MAX = TILE_LDS_MAX;  // bytes: the chunked kernels' budget (fir_tile.h)
 constexpr long UPFIRDN_LDS_WANT = 52 * 1024;  // three workgroups per CU (160 KiB): R shrinks to get there before it grows the tile
 constexpr long UPFIRDN_TILED_MAX_PERIOD_OUT = 16; // route 1: the output tile is 256 R U' elements and the phase loop U' passes over the image
 
@@ -58,20 +59,16 @@ inline void upfirdn_build(const float *taps, long K, long U, long D, PhaseVec &p
     if (tp.empty()) tp.resize(16, 0.0f);
 }
 
-// ---- route 1's tile: 256 lanes x R periods.  Image: sample n at n + n / (R D') when R D' is even (odd lane stride), else at n ----
-RD_HD constexpr bool upfirdn_tiled_d(long Dp) { return Dp == 1 || Dp == 2 || Dp == 3 || Dp == 4 || Dp == 5 || Dp == 8 || Dp == 10; }
-RD_HD constexpr long upfirdn_tile_in(int R, long Dp, long Wp) { return (256L * R - 1) * Dp + Wp; }
+// ---- route 1's tile: 256 lanes x R periods of D' samples, the decimations of the chunked table; tile_in(R, D', Wp) samples --------------
 // elements of the image (a multiple of four: the output tile behind it is 16-byte aligned for both sample types)
-RD_HD constexpr long upfirdn_img_elems(int R, long Dp, long Wp)
-{
-    const long t = upfirdn_tile_in(R, Dp, Wp), lstr = R * Dp;
-    return (t + (lstr % 2 == 0 ? t / lstr : 0) + 4) / 4 * 4;
-}
+RD_HD constexpr long upfirdn_tile_in(int R, long Dp, long Wp) { return tile_in(R, Dp, Wp); }
+RD_HD constexpr long upfirdn_img_elems(int R, long Dp, long Wp) { return (tile_image_index(upfirdn_tile_in(R, Dp, Wp), R * Dp) + 4) / 4 * 4; }
 RD_HD constexpr long upfirdn_lds_elems(int R, long Up, long Dp, long Wp) { return upfirdn_img_elems(R, Dp, Wp) + 256L * R * Up; }
 // periods per lane, decided on cf32 elements for both sample types: the largest of {4, 2, 1} inside UPFIRDN_LDS_WANT, else the largest
-// inside UPFIRDN_LDS_MAX, else 0 (no tile).  D' of 8 and 10 stop at 2, as the chunked FIR does: at 4 the window of 16 + 3 D' samples
-// spilled scalar registers in the exact-fold cf32 kernels
-RD_HD constexpr int upfirdn_r_max(long Dp) { return Dp >= 8 ? 2 : 4; }
+// inside UPFIRDN_LDS_MAX, else 0 (no tile).  Never more than the chunked FIR's R: at D' of 8 and 10 and R = 4 the window of 16 + 3 D' samples
+// spilled scalar registers in the exact-fold cf32 kernels.  Off the table no tile runs (upfirdn_route); the second term only keeps the R that
+// upfirdn_r reports there what it always was
+RD_HD constexpr int upfirdn_r_max(long Dp) { return tile_r(Dp) ? (tile_r(Dp) < 4 ? tile_r(Dp) : 4) : (Dp >= 8 ? 2 : 4); }
 RD_HD constexpr int upfirdn_r(long K, long U, long D)
 {
     const long Up = upfirdn_period_out(U, D), Dp = upfirdn_period_in(U, D), Wp = upfirdn_window(K, U, D);
@@ -83,56 +80,30 @@ RD_HD constexpr int upfirdn_r(long K, long U, long D)
 // redio_upfirdn_route: 1 the phase-walking tiled kernel, 2 the direct one
 RD_HD constexpr int upfirdn_route(long K, long U, long D)
 {
-    return upfirdn_tiled_d(upfirdn_period_in(U, D)) && upfirdn_period_out(U, D) <= UPFIRDN_TILED_MAX_PERIOD_OUT && K <= (1 << 20) &&
+    return tile_r(upfirdn_period_in(U, D)) != 0 && upfirdn_period_out(U, D) <= UPFIRDN_TILED_MAX_PERIOD_OUT && K <= (1 << 20) &&
                    upfirdn_r(K, U, D) != 0
                ? 1 : 2;
 }
 
-// The loader of ONE thread `tid` of NT: tile sample n < tile_in from x[n] (zero beyond `left` = the samples the stream has from x on)
-// through put(n, v).  vec_x: x is 16-byte aligned -- 16 / sizeof(T) samples per load, non-temporal with STREAM.
+// Route 1's loader and store loop, ONE thread `tid` of NT each: the shared plain loader (fir_tile.h) with four loads in flight and a sink
+// of single samples -- a lane stride of 2 or 4 samples (R = 1) does not keep the samples of one load side by side -- and the shared store
+// loop over the contiguous output tile
 template <typename T, bool STREAM, typename Put>
 RD_HD void upfirdn_load_thread(int tid, int NT, const T *x, long left, int tile_in, bool vec_x, Put &&put)
 {
-    constexpr int VEC = 16 / (int)sizeof(T);
-    auto put16 = [&](int v, const float4 &q) {
-        const int n = v * VEC;
-        const float f[4] = {q.x, q.y, q.z, q.w};
+    tile_load_thread<T, STREAM, 4>(tid, NT, x, left, tile_in, vec_x, [&](int n, auto v) {
+        if constexpr (std::is_same_v<decltype(v), float4>) {
 #pragma unroll
-        for (int e = 0; e < VEC; ++e)
-            if (n + e < tile_in) {
-                if constexpr (sizeof(T) == 8) put(n + e, T{f[2 * e], f[2 * e + 1]});
-                else put(n + e, f[e]);
-            }
-    };
-    if (vec_x) {
-        const float4 *x4 = reinterpret_cast<const float4 *>(x);
-        const int nv = (tile_in + VEC - 1) / VEC;
-        int vfirst = tid;
-        if ((long)nv * VEC <= left) { // the whole tile exists (workgroup-uniform): LB loads in flight per lane, no bound checks
-            constexpr int LB = 4;
-            for (; vfirst + (LB - 1) * NT < nv; vfirst += LB * NT) {
-                float4 q[LB];
-#pragma unroll
-                for (int b = 0; b < LB; ++b) q[b] = ddc_ld16<STREAM>(x4 + vfirst + b * NT);
-#pragma unroll
-                for (int b = 0; b < LB; ++b) put16(vfirst + b * NT, q[b]);
-            }
+            for (int e = 0; e < 16 / (int)sizeof(T); ++e) put(n + e, tile_elem<T>(v, e));
+        } else {
+            put(n, v);
         }
-#pragma unroll 4
-        for (int v = vfirst; v < nv; v += NT) {
-            const int n = v * VEC;
-            if (n + VEC <= left) {
-                put16(v, ddc_ld16<STREAM>(x4 + v));
-            } else {
-#pragma unroll
-                for (int e = 0; e < VEC; ++e)
-                    if (n + e < tile_in) put(n + e, n + e < left ? x[n + e] : T{});
-            }
-        }
-    } else {
-#pragma unroll 4
-        for (int n = tid; n < tile_in; n += NT) put(n, n < left ? x[n] : T{});
-    }
+    });
+}
+template <typename T, bool STREAM>
+RD_HD void upfirdn_store_thread(int tid, int NT, const T *ys, int nel, T *y, long left, bool vec_y)
+{
+    tile_store_thread<T, STREAM>(tid, NT, ys, nel, y, left, vec_y, [](int e) { return e; });
 }
 
 // CH taps of one phase for the R periods of a lane: fir_chunk's program (fir_chunks.h) with the window begun `o` samples into the
@@ -143,14 +114,10 @@ template <typename T, int D, int R, bool FUSED, int CH>
 RD_HD void upfirdn_chunk(const T *xs, int base, int o, const float *__restrict__ g, T (&acc)[R])
 {
     constexpr int WIN = CH + (R - 1) * D, LSTR = R * D;
-    constexpr bool PAD = (LSTR % 2) == 0;
     T xv[WIN];
     float h[CH];
 #pragma unroll
-    for (int i = 0; i < WIN; ++i) {
-        const int m = o + i; // wave-uniform
-        xv[i] = xs[base + (PAD ? m + m / LSTR : m)];
-    }
+    for (int i = 0; i < WIN; ++i) xv[i] = xs[base + tile_image_index(o + i, LSTR)]; // o + i is wave-uniform
 #pragma unroll
     for (int j = 0; j < CH; ++j) h[j] = g[j];
 #pragma unroll
@@ -180,13 +147,12 @@ RD_HD void upfirdn_phase(const T *xs, int base, int s, int k, const float *__res
 }
 
 // ONE thread of route 1 behind the loader: the U' phases of its R periods into the output tile ys (output e of the tile at ys[e],
-// e = period * U' + phase).  The reads of ys by the store loop are consecutive; the writes here are R U' elements apart from lane to
+// e = period * U' + phase).  The reads of ys by the store loop (tile_store_thread with the identity index) are consecutive; the writes here are R U' elements apart from lane to
 // lane and take the bank conflicts that come with it (one write per output against K(r) / R window reads).
 template <typename T, int D, int R, bool FUSED, int CHW>
 RD_HD void upfirdn_phases_thread(const T *xs, T *ys, int tid, const UpfirdnPhase *__restrict__ ph, const float *__restrict__ taps, int Up)
 {
-    constexpr int LSTR = R * D;
-    const int base = tid * (LSTR + (LSTR % 2 == 0 ? 1 : 0));
+    const int base = tile_lane_base(tid, R * D);
     for (int r = 0; r < Up; ++r) {
         const UpfirdnPhase p = ph[r]; // wave-uniform: a scalar load
         T acc[R];
@@ -195,32 +161,6 @@ RD_HD void upfirdn_phases_thread(const T *xs, T *ys, int tid, const UpfirdnPhase
         upfirdn_phase<T, D, R, FUSED, CHW>(xs, base, p.s, p.k, taps + p.off, acc);
 #pragma unroll
         for (int q = 0; q < R; ++q) ys[(tid * R + q) * Up + r] = acc[q];
-    }
-}
-
-// ONE thread of route 1's store loop: the tile's nel outputs from ys to y (the tile's first output), `left` of which exist.
-// vec_y: y is 16-byte aligned -- 16-byte stores, non-temporal with STREAM; nel is a multiple of 16 / sizeof(T).
-template <typename T, bool STREAM>
-RD_HD void upfirdn_store_thread(int tid, int NT, const T *ys, int nel, T *y, long left, bool vec_y)
-{
-    constexpr int VEC = 16 / (int)sizeof(T);
-    for (int v = tid; v < nel / VEC; v += NT) {
-        const int e0 = v * VEC;
-        if (vec_y && e0 + VEC <= left) {
-            const float4 q = *reinterpret_cast<const float4 *>(ys + e0);
-#if defined(__HIP_DEVICE_COMPILE__)
-            if constexpr (STREAM) {
-                typedef float v4f __attribute__((ext_vector_type(4)));
-                __builtin_nontemporal_store(v4f{q.x, q.y, q.z, q.w}, reinterpret_cast<v4f *>(y) + v);
-                continue;
-            }
-#endif
-            reinterpret_cast<float4 *>(y)[v] = q;
-        } else {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e)
-                if (e0 + e < left) y[e0 + e] = ys[e0 + e];
-        }
     }
 }
 

@@ -16,7 +16,6 @@ __global__ __launch_bounds__(256) void upfirdn_tiled_kernel(const T *__restrict_
                                                             int vec_out)
 {
     constexpr int NT = 256, NQ = NT * R, LSTR = R * D;
-    constexpr bool PAD = (LSTR % 2) == 0;
     constexpr bool STREAM = D >= 2; // fir_chunked_kernel's policy: non-temporal tile loads and output stores where the samples go by once
     extern __shared__ __attribute__((aligned(16))) char smem[];
     T *xs = reinterpret_cast<T *>(smem);
@@ -25,7 +24,7 @@ __global__ __launch_bounds__(256) void upfirdn_tiled_kernel(const T *__restrict_
     const long t = blockIdx.x;
     const long in0 = t * NQ * D;
     upfirdn_load_thread<T, STREAM>(tid, NT, x + in0, n_in - in0, (int)upfirdn_tile_in(R, D, Wp), vec_in != 0,
-                                   [&](int n, T v) { xs[PAD ? n + n / LSTR : n] = v; });
+                                   [&](int n, T v) { xs[tile_image_index(n, LSTR)] = v; });
     __syncthreads();
     upfirdn_phases_thread<T, D, R, FUSED, CHW>(xs, ys, tid, ph, taps, Up);
     __syncthreads();
@@ -84,18 +83,8 @@ template <typename T, bool FUSED>
 hipError_t launch_upfirdn_t(const UpfirdnArgs &a)
 {
     const long Up = upfirdn_period_out(a.U, a.D), Dp = upfirdn_period_in(a.U, a.D);
-    if (upfirdn_route(a.K, a.U, a.D) == 1) {
-        switch (Dp) {
-        case 1: return launch_tiled_r<T, 1, FUSED>(a);
-        case 2: return launch_tiled_r<T, 2, FUSED>(a);
-        case 3: return launch_tiled_r<T, 3, FUSED>(a);
-        case 4: return launch_tiled_r<T, 4, FUSED>(a);
-        case 5: return launch_tiled_r<T, 5, FUSED>(a);
-        case 8: return launch_tiled_r<T, 8, FUSED>(a);
-        case 10: return launch_tiled_r<T, 10, FUSED>(a);
-        default: return hipErrorNotSupported;
-        }
-    }
+    if (upfirdn_route(a.K, a.U, a.D) == 1)
+        return tile_dispatch_d(Dp, hipErrorNotSupported, [&](auto d) { return launch_tiled_r<T, decltype(d)::value, FUSED>(a); });
     hipLaunchKernelGGL((upfirdn_direct_kernel<T, FUSED>), dim3((unsigned)((a.n_out + 255) / 256)), dim3(256), 0, a.s, static_cast<const T *>(a.x), a.ph,
                        a.taps, Up, Dp, static_cast<T *>(a.y), a.n_out);
     return hipGetLastError();

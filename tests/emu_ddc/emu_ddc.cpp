@@ -1,5 +1,5 @@
-// emu_ddc.cpp -- CPU emulation of the tuner's kernels (libredio_amd/csrc/ddc_kernels.hip): every thread of one workgroup runs the loader
-// of ddc_core.h into the padded LDS image, then the FIR lane program (fir_core.h fir_lane, fir_chunks.h fir_chunks) runs on that image --
+// emu_ddc.cpp -- CPU emulation of the tuner's kernels (the FIR's tiled bodies with the loader of ddc_core.h): every thread of one workgroup
+// runs that loader into the padded LDS image (fir_tile.h), then the FIR lane program (fir_core.h fir_lane, fir_chunks.h fir_chunks) runs on that image --
 // the very sources the device compiles.  Also the counters of one carried-history call (stream_split.h) with the tuner's phase.
 #include "../../libredio_amd/csrc/ddc_core.h"
 #include "../../libredio_amd/csrc/fir_chunks.h"
@@ -56,18 +56,17 @@ void tiled(const Call &c)
 template <bool U8, bool FUSED, int D>
 void chunked(const Call &c)
 {
-    constexpr int R = ddc_chunked_r(D), CHW = ddc_chunked_chw(D), LSTR = R * D, TILE_OUT = 256 * R;
-    constexpr bool PAD = LSTR % 2 == 0;
-    const int tile_in = (int)ddc_chunked_tile_in(c.K, D, R);
-    Image im(ddc_chunked_lds_elems(c.K, D, R), c.bad);
-    load<U8, (D >= 2)>(c, c.tile * TILE_OUT * D, tile_in, im, [](int n) { return (long)(PAD ? n + n / LSTR : n); });
-    for (int n = 0; n < tile_in; ++n) c.image[n] = im.at(PAD ? n + n / LSTR : n);
+    constexpr int R = tile_r(D), CHW = tile_chw(D), LSTR = R * D, TILE_OUT = 256 * R;
+    const int tile_in = (int)redio::tile_in(R, D, tile_window(c.K));
+    Image im(tile_lds_elems(R, D, tile_window(c.K)), c.bad);
+    load<U8, (D >= 2)>(c, c.tile * TILE_OUT * D, tile_in, im, [](int n) { return (long)tile_image_index(n, LSTR); });
+    for (int n = 0; n < tile_in; ++n) c.image[n] = im.at(tile_image_index(n, LSTR));
     *c.tile_in = tile_in; *c.tile_out = TILE_OUT;
     if (!c.y) return;
     for (int tid = 0; tid < 256; ++tid) {
         float2 acc[R];
         for (int r = 0; r < R; ++r) acc[r] = make_float2(0.f, 0.f);
-        fir_chunks<float2, D, R, FUSED, CHW>(im.data(), tid * (LSTR + (PAD ? 1 : 0)), c.K, c.taps, acc);
+        fir_chunks<float2, D, R, FUSED, CHW>(im.data(), tile_lane_base(tid, LSTR), c.K, c.taps, acc);
         for (int r = 0; r < R; ++r) c.y[tid * R + r] = acc[r];
     }
 }
@@ -96,15 +95,7 @@ int run(const Call &c)
         else if (c.K == 63 && c.D == 1) tiled<U8, FUSED, 63, 1, 8>(c);
         else tiled<U8, FUSED, 63, 5, 4>(c);
     } else if (route == 2) {
-        switch (c.D) {
-        case 1: chunked<U8, FUSED, 1>(c); break;
-        case 2: chunked<U8, FUSED, 2>(c); break;
-        case 3: chunked<U8, FUSED, 3>(c); break;
-        case 4: chunked<U8, FUSED, 4>(c); break;
-        case 5: chunked<U8, FUSED, 5>(c); break;
-        case 8: chunked<U8, FUSED, 8>(c); break;
-        default: chunked<U8, FUSED, 10>(c); break;
-        }
+        tile_dispatch_d(c.D, 0, [&](auto d) { chunked<U8, FUSED, decltype(d)::value>(c); return 0; });
     } else {
         direct<U8, FUSED>(c);
     }
@@ -117,9 +108,9 @@ extern "C" {
 int emu_ddc_table_ext(void) { return DDC_TABLE_EXT; }
 int emu_ddc_route(long K, long D) { return ddc_route(K, D); }
 // the chunked route's geometry as the headers have it; 0 where the decimation has no chunked form
-long emu_ddc_chunked_tile_in(long K, long D) { return ddc_chunked_r(D) ? ddc_chunked_tile_in((int)K, D, ddc_chunked_r(D)) : 0; }
-long emu_ddc_chunked_lds_elems(long K, long D) { return ddc_chunked_r(D) ? ddc_chunked_lds_elems((int)K, D, ddc_chunked_r(D)) : 0; }
-int emu_ddc_chunked_chw(long D) { return ddc_chunked_chw(D); }
+long emu_ddc_chunked_tile_in(long K, long D) { return tile_r(D) ? tile_in(tile_r(D), D, tile_window(K)) : 0; }
+long emu_ddc_chunked_lds_elems(long K, long D) { return tile_r(D) ? tile_lds_elems(tile_r(D), D, tile_window(K)) : 0; }
+int emu_ddc_chunked_chw(long D) { return tile_chw(D); }
 
 // One workgroup (`tile`) of a call on n_in samples at x (cf32, or u8 I/Q bytes), first_index `first`.  tab: the device table's layout,
 // L + emu_ddc_table_ext() entries (the caller may append a fence behind it).  image: the tile's samples as the lane program sees them, in

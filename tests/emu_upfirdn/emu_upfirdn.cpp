@@ -73,7 +73,7 @@ template <typename T, int DP, int R, bool FUSED>
 void tiled_call(const T *x, long n_in, const UpfirdnPhase *ph, const float *taps, int Up, int Wp, T *y, long n_out, bool vec_in, bool vec_out, int *bad)
 {
     constexpr int NT = 256, NQ = NT * R, LSTR = R * DP;
-    constexpr bool PAD = LSTR % 2 == 0, STREAM = DP >= 2;
+    constexpr bool STREAM = DP >= 2;
     const long img = upfirdn_img_elems(R, DP, Wp), lds = upfirdn_lds_elems(R, Up, DP, Wp);
     const long per_tile = (long)NQ * Up;
     if (lds - img != per_tile || lds * 8 > UPFIRDN_LDS_MAX) ++*bad; // the launch's allocation is the image and the output tile, and fits
@@ -83,7 +83,7 @@ void tiled_call(const T *x, long n_in, const UpfirdnPhase *ph, const float *taps
         const long in0 = t * NQ * DP;
         for (int tid = 0; tid < NT; ++tid)
             upfirdn_load_thread<T, STREAM>(tid, NT, x + in0, n_in - in0, (int)upfirdn_tile_in(R, DP, Wp), vec_in, [&](int n, T v) {
-                const long at = PAD ? n + n / LSTR : n;
+                const long at = tile_image_index(n, LSTR);
                 if (at < 0 || at >= img) ++*bad; else xs[at] = v;
             });
         for (int tid = 0; tid < NT; ++tid) upfirdn_phases_thread<T, DP, R, FUSED, 16>(xs, ys, tid, ph, taps, Up);
@@ -144,15 +144,10 @@ void one_call(long K, long U, long D, long n_in, unsigned seed, bool light = fal
             if (route == 1) {
                 for (auto &v : ybuf.all) v = nan_of(T{});
                 const float *taps = tbuf.data();
-                switch (Dp) {
-                case 1: tiled_r<T, 1, FUSED>(R, x, n_in, ph.data(), taps, (int)Up, (int)Wp, y, n_out, aligned, yal, &bad); break;
-                case 2: tiled_r<T, 2, FUSED>(R, x, n_in, ph.data(), taps, (int)Up, (int)Wp, y, n_out, aligned, yal, &bad); break;
-                case 3: tiled_r<T, 3, FUSED>(R, x, n_in, ph.data(), taps, (int)Up, (int)Wp, y, n_out, aligned, yal, &bad); break;
-                case 4: tiled_r<T, 4, FUSED>(R, x, n_in, ph.data(), taps, (int)Up, (int)Wp, y, n_out, aligned, yal, &bad); break;
-                case 5: tiled_r<T, 5, FUSED>(R, x, n_in, ph.data(), taps, (int)Up, (int)Wp, y, n_out, aligned, yal, &bad); break;
-                case 8: tiled_r<T, 8, FUSED>(R, x, n_in, ph.data(), taps, (int)Up, (int)Wp, y, n_out, aligned, yal, &bad); break;
-                default: tiled_r<T, 10, FUSED>(R, x, n_in, ph.data(), taps, (int)Up, (int)Wp, y, n_out, aligned, yal, &bad); break;
-                }
+                tile_dispatch_d(Dp, 0, [&](auto d) {
+                    tiled_r<T, decltype(d)::value, FUSED>(R, x, n_in, ph.data(), taps, (int)Up, (int)Wp, y, n_out, aligned, yal, &bad);
+                    return 0;
+                });
                 for (long i = 0; i < n_out; ++i) wrong += !same(y[i], want[(size_t)i]);
                 if (!untouched()) ++bad;
             }

@@ -91,6 +91,29 @@ def test_fir_chunked_whole_chunk_seams(gpu, redio, oracle, d, chunk, fused):
         assert same_bits(plan(dx[1:]).cpu().numpy(), oracle.fir(x[1:], taps, d, fused)), (k, d, fused, "view off the 16-byte grid")
 
 
+@pytest.mark.parametrize("d,r,chunk", [(1, 8, 16), (2, 4, 16), (3, 4, 24), (4, 4, 16), (5, 4, 40), (8, 2, 16), (10, 2, 40)])
+@pytest.mark.parametrize("fused", [False, True])
+def test_fir_chunked_real_samples_off_the_16_byte_grid(gpu, redio, oracle, d, r, chunk, fused):
+    # real samples go four to a 16-byte load and store: views 1, 2 and 3 floats off the grid on the input (scalar tile loads), on the output
+    # (scalar stores behind wide loads) and on both; one output, exactly one tile, and one output into the next (the guarded tail), and
+    # 64 outputs into the next, where the first tile's samples all exist (the loads in flight); one tap past a whole chunk
+    k = chunk + 1
+    taps = oracle.synth_f32(200 + k, 0, k)
+    plan = redio.Fir(taps, d, complex_input=False, fused=fused)
+    tile_out = 256 * r
+    for n_out in (1, tile_out, tile_out + 1, tile_out + 64):
+        n = (n_out - 1) * d + k
+        x = oracle.synth_f32(9, d, n + 3)
+        dx = gpu.from_numpy(x).cuda()
+        for xoff, yoff in [(1, 0), (2, 0), (3, 0), (0, 1), (0, 2), (0, 3), (1, 3), (2, 2), (3, 1)]:
+            assert plan.nout(n) == n_out
+            buf = gpu.full((n_out + 8,), float("nan"), dtype=gpu.float32, device="cuda")
+            got = plan(dx[xoff: xoff + n], out=buf[yoff: yoff + n_out]).cpu().numpy()
+            assert same_bits(got, oracle.fir(x[xoff: xoff + n], taps, d, fused)), (d, fused, n_out, xoff, yoff)
+            rest = buf.cpu().numpy()
+            assert np.isnan(rest[:yoff]).all() and np.isnan(rest[yoff + n_out:]).all(), (d, fused, n_out, xoff, yoff)
+
+
 def test_fir_short_input_is_empty(gpu, redio, oracle):
     plan = redio.Fir(oracle.lpf_corrected(63, 0.1), 1)
     assert plan.nout(62) == 0 and plan.nout(63) == 1
