@@ -949,6 +949,35 @@ inline void channelizer_stream(Receiver<View<std::complex<float>>> u, Sender<Vie
                              [&](const View<cf> &d, cf *o, size_t *got, void *st) { return redio_pfb_stream_enqueue(s, d.data(), d.len, o, got, st); });
 }
 
+// the synthesis filterbank (redio_pfb_synth_*: the inverse transform of every row of nchan channel values, then the channelizer's
+// branch filter) as a block: rows of channel values in -- dev::channelizer's output -- samples of ONE stream out.
+// Per message: the first taps_per_branch - 1 rows of a message only fill the filter.
+inline void synthesizer(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<float> proto, int nchan,
+                        int taps_per_branch, bool fused)
+{
+    using cf = std::complex<float>;
+    redio_pfb_synth *h = nullptr;
+    check(redio_pfb_synth_create(&h, proto.data(), nchan, taps_per_branch, fused ? REDIO_FIR_FUSED : 0));
+    struct G { redio_pfb_synth *h; ~G() { redio_pfb_synth_destroy(h); } } g{h};
+    detail::run_block<cf, cf>(u, v, [&](const View<cf> &d) { return redio_pfb_synth_nout(h, d.len); },
+                              [&](const View<cf> &d, const View<cf> &o, void *st) { return redio_pfb_synth_enqueue(h, d.data(), d.len, o.data(), st); });
+}
+
+// ... and as a stream: messages of any length, taps_per_branch - 1 rows and a partial row carried, whole output rows sent
+inline void synthesizer_stream(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<float> proto, int nchan,
+                               int taps_per_branch, bool fused)
+{
+    using cf = std::complex<float>;
+    redio_pfb_synth *h = nullptr;
+    check(redio_pfb_synth_create(&h, proto.data(), nchan, taps_per_branch, fused ? REDIO_FIR_FUSED : 0));
+    redio_pfb_synth_stream *s = nullptr;
+    const int rc = redio_pfb_synth_stream_create(&s, h);
+    struct G { redio_pfb_synth *h; redio_pfb_synth_stream *s; ~G() { redio_pfb_synth_stream_destroy(s); redio_pfb_synth_destroy(h); } } g{h, s};
+    check(rc);
+    detail::run_stream_block(u, v, [&](size_t len) { return redio_pfb_synth_stream_nout(s, len); },
+                             [&](const View<cf> &d, cf *o, size_t *got, void *st) { return redio_pfb_synth_stream_enqueue(s, d.data(), d.len, o, got, st); });
+}
+
 inline void overlap_save_stream(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<float> taps, int nfft)
 {
     using cf = std::complex<float>;

@@ -532,6 +532,45 @@ int redio_pfb_pspec_enqueue_u8(redio_pfb_pspec *h, const void *d_bytes, size_t n
 int redio_pfb_pspec_reserve_u8(redio_pfb_pspec *h, size_t nbytes);
 int redio_pfb_pspec_set_split(redio_pfb_pspec *h, int mode);
 
+/* ---- the synthesis filterbank: many narrow channels into one wideband stream (a NEW composition) ----
+ * The channelizer is "branch filter, then forward transform".  This is "inverse transform, then the same branch filter".
+ * What brings a channelized stream back to one stream after per-channel work, and the transmit direction (a transmultiplexer).
+ * M = nchan, P = taps_per_branch; the prototype has M P taps in the channelizer's own layout, g_m[p] = proto[M p + m].  The input is
+ * T = n_in / M rows X_t[0 .. M) of cf32 in natural channel order -- redio_pfb_enqueue's ngroups = 1 output layout; a trailing partial
+ * row is ignored:
+ *     v_t = kissfft's unnormalised M-point INVERSE transform of X_t (kissfft.rs:26 with inv != 0: the bits of an inverse redio_fft);
+ *     y[M t + m] = the fold of dsputils::convolve (dsputils.rs:31) over v_{t+p}[m] * g_m[p], from 0.0f in ascending p = 0 .. P - 1:
+ *     multiply and add rounded separately, or fmaf with REDIO_FIR_FUSED -- per branch the bits of redio_fir on the column v[:, m].
+ * The output is (T - P + 1) M cf32 samples of one stream (0 when T < P); in samples the window is P M and the hop M.  Like every FIR
+ * here this is valid-mode correlation with the taps not reversed: for the convolution form pass the prototype with the p order
+ * flipped.  There is no 1 / M, as kissfft has none: with one-tap prototypes (1.0 at tap pa on the analysis side, at ps here) the round
+ * trip through redio_pfb_enqueue gives M x[i + (pa + ps) M] up to the transforms' rounding.
+ * create: NULL h / taps, nchan < 1, taps_per_branch < 1 -> REDIO_ERR_ARG, as redio_pfb_create; a size redio_fft_create refuses ->
+ *   its error.  flags: REDIO_FIR_FUSED or 0.
+ * redio_pfb_synth_route() says what a call on the plan runs (0 for NULL):
+ *   1  nchan = 64 with taps_per_branch in {4, 8, 16} is ONE kernel, a wavefront per run of output rows (is_fused() == 1): 8 bytes read
+ *      and 8 written per sample, no scratch; it captures without a reserve.
+ *   0  every other plan runs its own inverse redio_fft over the rows into plan-owned scratch and the channelizer's branch pass on the
+ *      result, in chunks of at most 64 MiB of rows: 32 bytes per sample.
+ * set_unfused(h, 1) sends a route-1 plan down route 0 (tests and measurement, as redio_chain_set_unfused): the same bits.
+ * reserve(h, n_in) sizes route 0's scratch (the transform's staging included) for calls of up to n_in values on the plan's CURRENT
+ *   route, after which an enqueue neither allocates nor synchronises; un-reserved it grows on first use (REDIO_ERR_NOT_RESERVED
+ *   while the stream is being captured).  On route 1 it does nothing.
+ * enqueue: launches only, on the caller's stream; every argument is checked before anything is launched.  NULL handle or buffers,
+ *   overlapping buffers (d_in == d_out included), either pointer not 8-byte aligned -> REDIO_ERR_ARG; fewer than P M values ->
+ *   REDIO_OK, no launch.
+ * set_chunk_rows: input rows per pass of route 0 (0 restores the 64 MiB default) -- for tests of the chunk seam; the same bits. */
+typedef struct redio_pfb_synth redio_pfb_synth;
+int redio_pfb_synth_create(redio_pfb_synth **h, const float *proto_taps_host, int nchan, int taps_per_branch, unsigned flags);
+int redio_pfb_synth_destroy(redio_pfb_synth *h);
+size_t redio_pfb_synth_nout(const redio_pfb_synth *h, size_t n_in); /* samples out for n_in cf32 values in */
+int redio_pfb_synth_route(const redio_pfb_synth *h);                /* 1 the 64-channel wave kernel, 0 two passes; 0 for NULL */
+int redio_pfb_synth_is_fused(const redio_pfb_synth *h);
+int redio_pfb_synth_set_unfused(redio_pfb_synth *h, int unfused);
+int redio_pfb_synth_set_chunk_rows(redio_pfb_synth *h, size_t rows);
+int redio_pfb_synth_reserve(redio_pfb_synth *h, size_t n_in);
+int redio_pfb_synth_enqueue(redio_pfb_synth *h, const void *d_rows_c32, size_t n_in, void *d_out_c32, void *stream);
+
 /* ---- the channelizer's one exchange step over RCCL / xGMI (the only collective on the path) ----
  * Time-sharded channelizer: every rank runs redio_pfb_enqueue(..., ngroups = G) on its own slice of the stream and
  * holds d_grouped = [G groups][its rows][chans_per_rank cf32]; the exchange sends group q to rank q
@@ -685,6 +724,18 @@ int redio_upfirdn_stream_reset(redio_upfirdn_stream *h);
 size_t redio_upfirdn_stream_nout(const redio_upfirdn_stream *h, size_t n_new);
 size_t redio_upfirdn_stream_pending(const redio_upfirdn_stream *h);
 int redio_upfirdn_stream_enqueue(redio_upfirdn_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
+/* the synthesis filterbank as a stream: the unit is one output row (nchan samples) from the P nchan values that start at a multiple of
+ * nchan values of the stream, so P - 1 whole rows and the values of a partial row are carried.  A message may have any length (d_new
+ * 8-byte aligned); whole output rows are emitted, and a stream fed in any pieces concatenates to one redio_pfb_synth_enqueue on the
+ * whole stream, bit for bit.  Create reserves the plan's scratch for the seam windows (redio_pfb_synth_reserve for the largest
+ * message + P nchan keeps longer bodies allocation-free on route 0).  *nout and _stream_nout count samples; pending() = values carried. */
+typedef struct redio_pfb_synth_stream redio_pfb_synth_stream;
+int redio_pfb_synth_stream_create(redio_pfb_synth_stream **h, redio_pfb_synth *plan);
+int redio_pfb_synth_stream_destroy(redio_pfb_synth_stream *h);
+int redio_pfb_synth_stream_reset(redio_pfb_synth_stream *h);
+size_t redio_pfb_synth_stream_nout(const redio_pfb_synth_stream *h, size_t n_new);
+size_t redio_pfb_synth_stream_pending(const redio_pfb_synth_stream *h);
+int redio_pfb_synth_stream_enqueue(redio_pfb_synth_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
 
 /* ---- A6: samplerate::resample's native side, src/samplerate/src/samplerate.rs:59-87 ----
  * nchan independent mono streams that share ratio and block lengths (the reference creates one

@@ -61,6 +61,18 @@ __global__ __launch_bounds__(256) void pfb_branch_kernel(const float2 *__restric
         if (t0 + r < rows) v[(t0 + r) * M + m] = acc[r];
 }
 
+// the branch filters alone: x = rows + P - 1 rows of M cf32, v = rows rows.  Also the second pass of the synthesis filterbank's
+// two-pass route (pfb_synth_api.hip), which runs it behind its inverse transform.
+hipError_t launch_pfb_branch(const float2 *x, const float *h, float2 *v, long rows, int M, int P, bool fused, hipStream_t st)
+{
+    if (rows <= 0) return hipSuccess;
+    const long bthreads = ((rows + PFB_BR - 1) / PFB_BR) * M;
+    const unsigned bgrid = (unsigned)((bthreads + 255) / 256);
+    if (fused) hipLaunchKernelGGL(pfb_branch_kernel<true>, dim3(bgrid), dim3(256), 0, st, x, h, v, rows, M, P);
+    else hipLaunchKernelGGL(pfb_branch_kernel<false>, dim3(bgrid), dim3(256), 0, st, x, h, v, rows, M, P);
+    return hipGetLastError();
+}
+
 // [row][M] -> [group][row][M / ngroups] (the layout the multi-GPU exchange sends)
 __global__ __launch_bounds__(256) void pfb_regroup_kernel(const float2 *__restrict__ in, float2 *__restrict__ out, long rows, int M, int ngroups)
 {
@@ -211,14 +223,7 @@ extern "C" int redio_pfb_enqueue(redio_pfb *h, const void *d_in, size_t n_in, vo
         }
         long blocks = (long)((total + 255) / 256);
         if (blocks > 65536) blocks = 65536;
-        const long bthreads = (long)((rows + PFB_BR - 1) / PFB_BR) * h->nchan;
-        const unsigned bgrid = (unsigned)((bthreads + 255) / 256);
-        if (h->flags & REDIO_FIR_FUSED)
-            hipLaunchKernelGGL(pfb_branch_kernel<true>, dim3(bgrid), dim3(256), 0, st, (const float2 *)d_in, h->d_h, h->d_v, (long)rows,
-                               h->nchan, h->taps_per_branch);
-        else
-            hipLaunchKernelGGL(pfb_branch_kernel<false>, dim3(bgrid), dim3(256), 0, st, (const float2 *)d_in, h->d_h, h->d_v, (long)rows,
-                               h->nchan, h->taps_per_branch);
+        REDIO_TRY(launch_pfb_branch((const float2 *)d_in, h->d_h, h->d_v, (long)rows, h->nchan, h->taps_per_branch, (h->flags & REDIO_FIR_FUSED) != 0, st));
         int rc = redio_fft_enqueue(h->fft, h->d_v, ngroups > 1 ? (void *)h->d_w : d_out, rows, stream);
         if (rc != REDIO_OK) return rc;
         if (ngroups > 1)

@@ -17,6 +17,7 @@
 //     resampler    W = Wp                          H = D'             unit = 1 period of U' output samples (upfirdn_core.h); every window begins
 //                  at a multiple of D' samples of the stream, which is phase 0: samples are carried, no phase.  The plan is told how many
 //                  periods to produce: a stateless call on the same samples would write more than whole periods when U > D
+//     synthesis bank  W = nchan*taps_per_branch    H = nchan          unit = 1 output row (nchan samples of the one stream, from rows of nchan channel values)
 // so one layer serves them all.  The handle keeps the stream's unconsumed tail (fewer than W samples) on the device.
 // A call with n new samples
 //   1. appends the first min(n, W-1) new samples to the tail in a plan-owned staging buffer (one small copy),
@@ -62,7 +63,7 @@ hipError_t seam_copy(void *dst, const void *src, size_t bytes, hipStream_t st)
     SEAM_GO(uint8_t)
 #undef SEAM_GO
 }
-enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8, K_PSPEC_REAL, K_PFB_PSPEC, K_PFB_PSPEC_U8, K_DDC, K_DDC_U8, K_UPFIRDN }; // _U8: the samples are interleaved u8 I/Q byte pairs
+enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8, K_PSPEC_REAL, K_PFB_PSPEC, K_PFB_PSPEC_U8, K_DDC, K_DDC_U8, K_UPFIRDN, K_PFB_SYNTH }; // _U8: the samples are interleaved u8 I/Q byte pairs
 struct Carry {
     int device = 0;
     Kind kind = K_FIR;
@@ -109,6 +110,7 @@ int run(const Carry &c, const void *d_in, size_t n_in, size_t units, unsigned lo
     case K_PSPEC_REAL: return redio_pspec_real_enqueue((redio_pspec_real *)c.plan, d_in, n_in, d_out, stream); // takes 4-byte aligned input itself
     case K_PFB_PSPEC: return redio_pfb_pspec_enqueue((redio_pfb_pspec *)c.plan, d_in, n_in, d_out, stream);
     case K_PFB_PSPEC_U8: return redio_pfb_pspec_enqueue_u8((redio_pfb_pspec *)c.plan, d_in, 2 * n_in, d_out, stream);
+    case K_PFB_SYNTH: return redio_pfb_synth_enqueue((redio_pfb_synth *)c.plan, d_in, n_in, d_out, stream);
     case K_OVSAVE_REAL: return redio_ovsave_real_enqueue_any((redio_ovsave_real *)c.plan, d_in, n_in, d_out, stream); // a unit may start on an odd sample
     }
     return REDIO_ERR_ARG;
@@ -237,6 +239,7 @@ struct redio_pspec_real_stream { Carry *c; };
 struct redio_pfb_pspec_stream { Carry *c; };
 struct redio_ddc_stream { Carry *c; };
 struct redio_upfirdn_stream { Carry *c; };
+struct redio_pfb_synth_stream { Carry *c; };
 
 #define RD_STREAM_API(NAME)                                                                                                     \
     extern "C" int redio_##NAME##_stream_destroy(redio_##NAME##_stream *h)                                                      \
@@ -268,6 +271,7 @@ RD_STREAM_API(pspec_real)
 RD_STREAM_API(pfb_pspec)
 RD_STREAM_API(ddc)
 RD_STREAM_API(upfirdn)
+RD_STREAM_API(pfb_synth)
 
 template <typename Hd>
 static int make(Hd **h, Kind kind, void *plan, int dev, size_t W, size_t H, size_t in_elem, size_t unit_out, size_t out_elem, uintptr_t align = 0)
@@ -438,4 +442,17 @@ extern "C" int redio_upfirdn_stream_create(redio_upfirdn_stream **h, redio_upfir
     redio_upfirdn_shape(plan, &Up, &Dp, &Wp, &flags, &dev);
     const size_t el = (flags & REDIO_FIR_COMPLEX) ? 8 : 4;
     return make(h, K_UPFIRDN, plan, dev, Wp, Dp, el, Up, el);
+}
+// the synthesis filterbank's stream: P - 1 whole rows and a partial row carried.  Route 0's scratch is sized here for the seam windows
+// (at most 2*W values per head run; nothing on route 1)
+extern "C" int redio_pfb_synth_stream_create(redio_pfb_synth_stream **h, redio_pfb_synth *plan)
+{
+    if (!h) return REDIO_ERR_ARG;
+    *h = nullptr;
+    if (!plan) return REDIO_ERR_ARG;
+    int M, P, dev;
+    redio_pfb_synth_shape(plan, &M, &P, &dev);
+    const int rr = redio_pfb_synth_reserve(plan, 2 * (size_t)M * P);
+    if (rr) return rr;
+    return make(h, K_PFB_SYNTH, plan, dev, (size_t)M * P, (size_t)M, 8, (size_t)M, 8, 7);
 }

@@ -367,17 +367,18 @@ class Chain:
 
 
 class Stream:
-    """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec,pspec_real,pfb_pspec,ddc,upfirdn}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
+    """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec,pspec_real,pfb_pspec,ddc,upfirdn,pfb_synth}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
     segmentation of the input gives the bits of one stateless call on the whole stream (the stateless plans keep the
     reference's per-message semantics, dsputils.rs:30-32).  `plan` is a Fir, Chain, Channelizer, OverlapSave, OverlapSaveReal, PowerSpectrum
     (complex64 in, float32 rows out), PowerSpectrumReal (float32 in, float32 rows out), PolyphaseSpectrum (complex64 in, float32 rows
     of nchan out), Ddc (the tuner: the oscillator's phase is carried with the history) or Upfirdn (whole periods of period_out samples
-    from the window that starts at a multiple of period_in samples of the stream)."""
+    from the window that starts at a multiple of period_in samples of the stream), or a Synthesizer (channel values in, whole rows of
+    nchan samples of the one stream out: see SynthesizerStream)."""
 
     def __init__(self, plan, u8=False):
         """u8=True (Chain, Channelizer, PowerSpectrum, PolyphaseSpectrum and Ddc): the stream arrives as the receiver's interleaved u8 I/Q
         bytes (uint8 tensors, two bytes per sample; redio_{chain,pfb,pspec,pfb_pspec}_stream_create_u8)."""
-        kind = {Fir: "fir", Chain: "chain", Ddc: "ddc", Upfirdn: "upfirdn"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec", "PowerSpectrumReal": "pspec_real", "PolyphaseSpectrum": "pfb_pspec"}[type(plan).__name__]
+        kind = {Fir: "fir", Chain: "chain", Ddc: "ddc", Upfirdn: "upfirdn"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec", "PowerSpectrumReal": "pspec_real", "PolyphaseSpectrum": "pfb_pspec", "Synthesizer": "pfb_synth"}[type(plan).__name__]
         assert not u8 or kind in ("chain", "pfb", "pspec", "pfb_pspec", "ddc")
         self._kind, self._plan, self._u8 = kind, plan, bool(u8)          # the plan must outlive the stream handle
         self._h = C.c_void_p()
@@ -971,3 +972,69 @@ class PolyphaseSpectrum:
         if getattr(self, "_h", None):
             _safe_destroy("redio_pfb_pspec_destroy", self._h)
             self._h = None
+
+
+class Synthesizer:
+    """redio_pfb_synth_*: the synthesis filterbank, many narrow channels into one wideband stream (contract: DESIGN.md 5.6c).  The
+    Channelizer is "branch filter, then forward transform"; this is "inverse transform, then the same branch filter": rows of nchan
+    complex64 channel values in (the Channelizer's ngroups = 1 layout), kissfft's unnormalised inverse transform per row, then per
+    branch the dsputils fold over taps_per_branch rows with g_m[p] = proto[nchan p + m]; (T - taps_per_branch + 1) * nchan samples of
+    one stream out.  No 1 / nchan.  64 channels with 4 / 8 / 16 taps per branch are one kernel (route WAVE, is_fused); every other plan
+    runs its own inverse transform into scratch and the branch pass (route TWO_PASS): the same bits."""
+
+    TWO_PASS, WAVE = 0, 1
+
+    def __init__(self, proto, nchan=64, taps_per_branch=16, fused=True):
+        t, p = _taps(proto)
+        assert len(t) == nchan * taps_per_branch
+        self.nchan, self.taps_per_branch = int(nchan), int(taps_per_branch)
+        self._h = C.c_void_p()
+        check(lib().redio_pfb_synth_create(C.byref(self._h), p, self.nchan, self.taps_per_branch, REDIO_FIR_FUSED if fused else 0), "pfb_synth_create")
+
+    def nout(self, n_in):
+        return lib().redio_pfb_synth_nout(self._h, int(n_in))
+
+    @property
+    def route(self):
+        """what a call runs: WAVE (the 64-channel kernel) or TWO_PASS"""
+        return lib().redio_pfb_synth_route(self._h)
+
+    @property
+    def is_fused(self):
+        return bool(lib().redio_pfb_synth_is_fused(self._h))
+
+    def set_unfused(self, unfused=True):
+        """send a WAVE plan down the two-pass route (tests and measurement): the same bits"""
+        check(lib().redio_pfb_synth_set_unfused(self._h, int(bool(unfused))), "pfb_synth_set_unfused")
+
+    def set_chunk_rows(self, rows):
+        """input rows per pass of the two-pass route (0: the 64 MiB default); for tests of the chunk seam: the same bits"""
+        check(lib().redio_pfb_synth_set_chunk_rows(self._h, int(rows)), "pfb_synth_set_chunk_rows")
+
+    def reserve(self, n_in):
+        """the two-pass route's scratch for calls of up to n_in values, so that a call never allocates, e.g. inside a Graph"""
+        check(lib().redio_pfb_synth_reserve(self._h, int(n_in)), "pfb_synth_reserve")
+
+    def __call__(self, rows, out=None):
+        import torch
+        assert rows.dtype == torch.complex64
+        n = self.nout(rows.numel())
+        if out is None:
+            out = torch.empty(n, dtype=torch.complex64, device=rows.device)
+        assert out.dtype == torch.complex64 and out.numel() >= n
+        check(lib().redio_pfb_synth_enqueue(self._h, _dev_ptr(rows), rows.numel(), _dev_ptr(out), current_stream()), "pfb_synth_enqueue")
+        return out[:n]
+
+    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
+        if getattr(self, "_h", None):
+            _safe_destroy("redio_pfb_synth_destroy", self._h)
+            self._h = None
+
+
+class SynthesizerStream(Stream):
+    """redio_pfb_synth_stream_*: a Synthesizer fed as a stream of channel values in messages of ANY length; taps_per_branch - 1 whole
+    rows and the values of a partial row are carried, whole output rows come out, and any segmentation concatenates to the one-shot call."""
+
+    def __init__(self, plan):
+        assert isinstance(plan, Synthesizer)
+        super().__init__(plan)

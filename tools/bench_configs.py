@@ -1,5 +1,5 @@
 """Throughput of the non-headline configs of BASELINE.json on one MI355X (own measurements; bench.py
-stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit|pfbpspecp2|pfbpspecp2split|ddc|ddcu8|upfirdn]..."""
+stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit|pfbpspecp2|pfbpspecp2split|ddc|ddcu8|upfirdn|pfbsynth]..."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, libredio_amd as R
@@ -648,6 +648,34 @@ if "upfirdn" in which:
               f"{out.numel()/ms/1e6:.1f} GS/s out  {b*out.numel()/ms/1e6:.0f} GB/s algorithmic ({b*out.numel()/ms/1e6/8000:.1%} of 8 TB/s) | "
               f"at {nc} samples: {ms_new:.3f} ms against {what}: {ms_old:.3f} ms, resampler / composition = {ms_new/ms_old:.3f}")
         del plan, fir, out, outc, z
+if "pfbsynth" in which:
+    # the synthesis filterbank (redio_pfb_synth_*: inverse transform per row, then the channelizer's branch filter) on 2^28 channel values in,
+    # fused fold: 64 x 16 and 64 x 4 on the wave kernel (route 1) and the same plans through set_unfused (route 0: the inverse transform into
+    # scratch, then the branch pass), 256 x 8 on route 0; and the Channelizer of the same prototype on as many samples.  The variants of a
+    # shape are timed alternately (twice each, the smaller time printed) in this one process; the two routes' outputs are compared bit for bit.
+    # Share of 8 TB/s on 16 B per sample (8 read + 8 written: route 1's traffic; route 0 moves 32).
+    x = R.synth_iq(0x5EED0004, 0, n)
+    for M, P in ((64, 16), (64, 4), (256, 8)):
+        h = R.dsputils.lpf_corrected(M * P, 0.45 / M)
+        plan, two, ana = R.Synthesizer(h, M, P, fused=True), R.Synthesizer(h, M, P, fused=True), R.Channelizer(h, M, P, fused=True)
+        two.set_unfused(True)
+        two.reserve(n)
+        out, out2 = (torch.empty(plan.nout(n), dtype=torch.complex64, device="cuda") for _ in range(2))
+        rows = torch.empty((ana.nrows(n), M), dtype=torch.complex64, device="cuda")
+        ms = {}
+        legs = {"synth": lambda: plan(x, out=out), "two-pass": lambda: two(x, out=out2), "channelizer": lambda: ana(x, out=rows)}
+        if plan.route == 0:
+            del legs["two-pass"]
+        for _ in range(2):
+            for name, f in legs.items():
+                ms[name] = min(ms.get(name, 1e30), timeit(f, n=10, warm=3))
+        line = (f"PFBSYNTH {M}ch P={P} (route {plan.route}): {ms['synth']:.3f} ms  {n/ms['synth']/1e6:.1f} GS/s  ({16*n/ms['synth']/1e6/8000:.1%} of 8 TB/s on 16 B/sample)")
+        if plan.route == 1:
+            same = torch.equal(torch.view_as_real(out).view(torch.int32), torch.view_as_real(out2).view(torch.int32))
+            line += f" | set_unfused (route {two.route}): {ms['two-pass']:.3f} ms, route 1 / route 0 = {ms['synth']/ms['two-pass']:.3f}, outputs bit-equal: {same}"
+        line += f" | Channelizer on as many samples: {ms['channelizer']:.3f} ms, synthesizer / channelizer = {ms['synth']/ms['channelizer']:.3f}"
+        print(line)
+        del plan, two, ana, out, out2, rows
 if "ddc" in which or "ddcu8" in which:
     # the tuner (redio_ddc_*: oscillator mix fused into the FIR tile load) on 2^28 samples against the route it replaces, timed alternately
     # (twice each, the smaller time printed) in this one process: (a) redio_mul_c32 on a PRE-MATERIALISED oscillator stream (its
