@@ -1259,5 +1259,68 @@ void upfirdn_stream(Receiver<View<T>> u, Sender<View<T>> v, std::vector<float> t
                                       [&](const View<T> &d, T *o, size_t *got, void *st) { return redio_upfirdn_stream_enqueue(s, d.data(), d.len, o, got, st); });
 }
 
+namespace detail {
+// the tuned resampler's four blocks: cf32 or u8 I/Q messages in (per_sample elements make a sample), cf32 out
+struct TunedResamplerCf32 {
+    using In = std::complex<float>;
+    static constexpr size_t per_sample = 1;
+    static constexpr auto enqueue = redio_ddc_upfirdn_enqueue;
+    static constexpr auto stream_create = redio_ddc_upfirdn_stream_create;
+};
+struct TunedResamplerU8 {
+    using In = uint8_t;
+    static constexpr size_t per_sample = 2;
+    static constexpr auto enqueue = redio_ddc_upfirdn_enqueue_u8;
+    static constexpr auto stream_create = redio_ddc_upfirdn_stream_create_u8;
+};
+inline redio_ddc_upfirdn *tuned_resampler_plan(const std::vector<std::complex<float>> &osc, const std::vector<float> &taps, size_t up, size_t down, bool fused)
+{
+    redio_ddc_upfirdn *h = nullptr;
+    check(redio_ddc_upfirdn_create(&h, reinterpret_cast<const float *>(osc.data()), osc.size(), taps.data(), taps.size(), up, down, fused ? REDIO_FIR_FUSED : 0));
+    return h;
+}
+template <typename T>
+void tuned_resampler_block(Receiver<View<typename T::In>> &u, Sender<View<std::complex<float>>> &v, const std::vector<std::complex<float>> &osc,
+                           const std::vector<float> &taps, size_t up, size_t down, bool fused)
+{
+    using In = typename T::In;
+    using cf = std::complex<float>;
+    redio_ddc_upfirdn *h = tuned_resampler_plan(osc, taps, up, down, fused);
+    struct G { redio_ddc_upfirdn *h; ~G() { redio_ddc_upfirdn_destroy(h); } } g{h};
+    // every message starts the table at entry 0 and the resampler at phase 0, as dev::tuner and dev::upfirdn do
+    run_block<In, cf>(u, v, [&](const View<In> &d) { return redio_ddc_upfirdn_nout(h, d.len / T::per_sample); },
+                      [&](const View<In> &d, const View<cf> &o, void *st) { return T::enqueue(h, d.data(), d.len, 0, o.data(), st); });
+}
+template <typename T>
+void tuned_resampler_stream_block(Receiver<View<typename T::In>> &u, Sender<View<std::complex<float>>> &v, const std::vector<std::complex<float>> &osc,
+                                  const std::vector<float> &taps, size_t up, size_t down, bool fused)
+{
+    using In = typename T::In;
+    using cf = std::complex<float>;
+    redio_ddc_upfirdn *h = tuned_resampler_plan(osc, taps, up, down, fused);
+    redio_ddc_upfirdn_stream *s = nullptr;
+    const int rc = T::stream_create(&s, h);
+    struct G { redio_ddc_upfirdn *h; redio_ddc_upfirdn_stream *s; ~G() { redio_ddc_upfirdn_stream_destroy(s); redio_ddc_upfirdn_destroy(h); } } g{h, s};
+    check(rc);
+    run_stream_block_of<In, cf>(u, v, [&](size_t len) { return redio_ddc_upfirdn_stream_nout(s, len / T::per_sample); },
+                                [&](const View<In> &d, cf *o, size_t *got, void *st) {
+                                    if (d.len % T::per_sample) return (int)REDIO_ERR_ARG;
+                                    return redio_ddc_upfirdn_stream_enqueue(s, d.data(), d.len / T::per_sample, o, got, st);
+                                });
+}
+} // namespace detail
+
+// the tuned resampler (redio_ddc_upfirdn_*: kpn::mul_vecs by the periodic table `osc`, kpn.rs:198-203, fused into the tile load of the
+// rational resampler, the polyphase form of dsputils::convolve, dsputils.rs:30-32): cf32 messages in, cf32 out, per-message semantics --
+// the table restarts at entry 0 and the resampler at phase 0 with every message, and the outputs whose taps would reach past its end are
+// lost at every seam.  Queue-ordered on the rings like dev::fir.
+inline void tuned_resampler(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<std::complex<float>> osc, std::vector<float> taps, size_t up, size_t down, bool fused) { detail::tuned_resampler_block<detail::TunedResamplerCf32>(u, v, osc, taps, up, down, fused); }
+// the receiver's messages straight into it: u8 I/Q bytes (rtlsdr.rs:127-162), without the cf32 intermediate; a message holds whole samples
+inline void tuned_resampler_u8(Receiver<View<uint8_t>> u, Sender<View<std::complex<float>>> v, std::vector<std::complex<float>> osc, std::vector<float> taps, size_t up, size_t down, bool fused) { detail::tuned_resampler_block<detail::TunedResamplerU8>(u, v, osc, taps, up, down, fused); }
+// the same as a STREAM (redio_ddc_upfirdn_stream_*): history AND oscillator phase are carried, so messages of any length give whole
+// periods of the outputs of one call on the whole stream; a message that completes no period sends nothing.  Queue-ordered like dev::fir_stream.
+inline void tuned_resampler_stream(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<std::complex<float>> osc, std::vector<float> taps, size_t up, size_t down, bool fused) { detail::tuned_resampler_stream_block<detail::TunedResamplerCf32>(u, v, osc, taps, up, down, fused); }
+inline void tuned_resampler_stream_u8(Receiver<View<uint8_t>> u, Sender<View<std::complex<float>>> v, std::vector<std::complex<float>> osc, std::vector<float> taps, size_t up, size_t down, bool fused) { detail::tuned_resampler_stream_block<detail::TunedResamplerU8>(u, v, osc, taps, up, down, fused); }
+
 } // namespace dev
 } // namespace kpn

@@ -184,6 +184,40 @@ size_t redio_upfirdn_period_in(const redio_upfirdn *h);
 size_t redio_upfirdn_window(const redio_upfirdn *h);
 int redio_upfirdn_enqueue(redio_upfirdn *h, const void *d_in, size_t n_in, void *d_out, void *stream);
 
+/* ---- the tuned resampler: the tuner's mix in front of the rational resampler, in one kernel (A1e) ----
+ * kpn::mul_vecs (src/kpn/src/kpn.rs:198-203) by a periodic constant vector of `period` cf32 entries, then the polyphase form of
+ * dsputils::convolve (src/dsputils/src/dsputils.rs:30-32) that redio_upfirdn_* runs -- tuner -> resampler, the receiver's usual pair,
+ * without the mixed stream ever written to memory:
+ *     m[n] = (xr*wr - xi*wi, xr*wi + xi*wr) with w = osc[(first_index + n) mod period]   redio_ddc's mix: every operation rounded on
+ *                                                                                         its own, never contracted
+ *     y    = redio_upfirdn's contract over m   (stuffed zeros skipped; REDIO_FIR_FUSED selects fmaf for the FOLD only)
+ *     nout = redio_upfirdn_nout's formula
+ * so every output is bit-equal to redio_upfirdn_enqueue (complex) on redio_mul_c32(x, the table tiled from first_index).  Input is cf32,
+ * or the receiver's interleaved u8 I/Q bytes, converted as redio_data_to_samples does (rtlsdr.rs:159-162) before the mix; the output is
+ * always cf32 and the taps are real.  first_index is the stream index of the call's sample 0.
+ * create (kpn.rs:198-203, dsputils.rs:30-32): table and taps are uploaded here, the table as redio_ddc's, the taps in redio_upfirdn's
+ *   polyphase order.  flags: REDIO_FIR_FUSED or 0.  NULL h / table / taps, period == 0 or above REDIO_DDC_MAX_PERIOD, ntaps == 0,
+ *   up == 0, down == 0 -> REDIO_ERR_ARG; ntaps > 2^24, up > 65536 or down >= 2^31 -> REDIO_ERR_UNSUPPORTED.
+ * nout / route / period_out / period_in / window: redio_upfirdn's (the route is decided on the cf32 geometry for both entries);
+ *   period: the oscillator's.  All 0 for NULL.
+ * enqueue / enqueue_u8 (kpn.rs:198-203, dsputils.rs:30-32; nbytes / 2 samples): launch only -- no allocation, no synchronisation, so
+ *   capturable; every argument is checked before anything is launched.  NULL handle, odd nbytes, NULL or overlapping buffers
+ *   (in != out), a cf32 pointer that is not 8-byte aligned -> REDIO_ERR_ARG; nout == 0 -> REDIO_OK, no launch.  Bytes are taken at any
+ *   alignment; 16-byte aligned cf32 (4-byte aligned bytes) run the two-samples-per-load path, a 16-byte aligned output the wide stores,
+ *   the other paths give the same bits. */
+typedef struct redio_ddc_upfirdn redio_ddc_upfirdn;
+int redio_ddc_upfirdn_create(redio_ddc_upfirdn **h, const float *osc_host_c32, size_t period, const float *taps_host, size_t ntaps, size_t up, size_t down,
+                             unsigned flags);
+int redio_ddc_upfirdn_destroy(redio_ddc_upfirdn *h);
+size_t redio_ddc_upfirdn_nout(const redio_ddc_upfirdn *h, size_t n_in);
+int redio_ddc_upfirdn_route(const redio_ddc_upfirdn *h);
+size_t redio_ddc_upfirdn_period(const redio_ddc_upfirdn *h);
+size_t redio_ddc_upfirdn_period_out(const redio_ddc_upfirdn *h);
+size_t redio_ddc_upfirdn_period_in(const redio_ddc_upfirdn *h);
+size_t redio_ddc_upfirdn_window(const redio_ddc_upfirdn *h);
+int redio_ddc_upfirdn_enqueue(redio_ddc_upfirdn *h, const void *d_in_c32, size_t n_in, uint64_t first_index, void *d_out_c32, void *stream);
+int redio_ddc_upfirdn_enqueue_u8(redio_ddc_upfirdn *h, const void *d_bytes, size_t nbytes, uint64_t first_index, void *d_out_c32, void *stream);
+
 /* ---- lists of independent messages for one launch (redio_fft_enqueue_list, redio_chain_enqueue_list) ----
  * The reference runs one kissfft::fft per message of block_size samples (src/kissfft/src/kissfft.rs:20-27 asserts din.len() ==
  * block_size) and one chain per message from a block thread (src/ratpak.rs:60-185); a launch per small message costs a fixed floor
@@ -724,6 +758,22 @@ int redio_upfirdn_stream_reset(redio_upfirdn_stream *h);
 size_t redio_upfirdn_stream_nout(const redio_upfirdn_stream *h, size_t n_new);
 size_t redio_upfirdn_stream_pending(const redio_upfirdn_stream *h);
 int redio_upfirdn_stream_enqueue(redio_upfirdn_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
+/* the tuned resampler as a stream (kpn.rs:198-203, dsputils.rs:30-32): the resampler's geometry and the tuner's phase.  The unit is one
+ * PERIOD -- U' outputs from the Wp samples that start at a multiple of D' samples of the stream -- and the handle passes the stream index
+ * of every window's first sample to the plan as first_index.  After N samples in any pieces the stream has written the first
+ * U' * max(0, (N - Wp) / D' + 1) outputs of one redio_ddc_upfirdn_enqueue on the whole stream with first_index 0, bit for bit.
+ * create_u8: d_new points to interleaved u8 I/Q bytes (any alignment), carried as bytes; n_new still counts SAMPLES.  *nout and
+ * _stream_nout count output samples.  _stream_index: the stream index of the next new sample (0 after create and reset; unchanged by a
+ * failed call). */
+typedef struct redio_ddc_upfirdn_stream redio_ddc_upfirdn_stream;
+int redio_ddc_upfirdn_stream_create(redio_ddc_upfirdn_stream **h, redio_ddc_upfirdn *plan);
+int redio_ddc_upfirdn_stream_create_u8(redio_ddc_upfirdn_stream **h, redio_ddc_upfirdn *plan);
+int redio_ddc_upfirdn_stream_destroy(redio_ddc_upfirdn_stream *h);
+int redio_ddc_upfirdn_stream_reset(redio_ddc_upfirdn_stream *h);
+size_t redio_ddc_upfirdn_stream_nout(const redio_ddc_upfirdn_stream *h, size_t n_new);
+size_t redio_ddc_upfirdn_stream_pending(const redio_ddc_upfirdn_stream *h);
+int redio_ddc_upfirdn_stream_enqueue(redio_ddc_upfirdn_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
+uint64_t redio_ddc_upfirdn_stream_index(const redio_ddc_upfirdn_stream *h);
 /* the synthesis filterbank as a stream: the unit is one output row (nchan samples) from the P nchan values that start at a multiple of
  * nchan values of the stream, so P - 1 whole rows and the values of a partial row are carried.  A message may have any length (d_new
  * 8-byte aligned); whole output rows are emitted, and a stream fed in any pieces concatenates to one redio_pfb_synth_enqueue on the

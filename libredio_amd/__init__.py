@@ -117,6 +117,15 @@ def lib():
     for n in ("period_out", "period_in", "window"):
         _sig(getattr(L, f"redio_upfirdn_{n}"), sz, vp)
     _sig(L.redio_upfirdn_enqueue, i, vp, vp, sz, vp, vp)
+    _sig(L.redio_ddc_upfirdn_create, i, C.POINTER(vp), pf, sz, pf, sz, sz, sz, u)
+    _sig(L.redio_ddc_upfirdn_destroy, i, vp)
+    _sig(L.redio_ddc_upfirdn_nout, sz, vp, sz)
+    _sig(L.redio_ddc_upfirdn_route, i, vp)
+    for n in ("period", "period_out", "period_in", "window"):
+        _sig(getattr(L, f"redio_ddc_upfirdn_{n}"), sz, vp)
+    _sig(L.redio_ddc_upfirdn_enqueue, i, vp, vp, sz, C.c_uint64, vp, vp)
+    _sig(L.redio_ddc_upfirdn_enqueue_u8, i, vp, vp, sz, C.c_uint64, vp, vp)
+    _sig(L.redio_ddc_upfirdn_stream_index, C.c_uint64, vp)
     _sig(L.redio_fft_create, i, C.POINTER(vp), i, i)
     _sig(L.redio_fft_destroy, i, vp)
     _sig(L.redio_fft_enqueue, i, vp, vp, vp, sz, vp)
@@ -141,14 +150,14 @@ def lib():
     _sig(L.redio_fft_reserve, i, vp, sz)
     _sig(L.redio_pfb_reserve, i, vp, sz, i)
     _sig(L.redio_pfb_reserve_two_pass, i, vp, sz, i)
-    for n in ("fir", "chain", "pfb", "ovsave", "ovsave_real", "pspec", "pspec_real", "pfb_pspec", "ddc", "upfirdn", "pfb_synth"):
+    for n in ("fir", "chain", "pfb", "ovsave", "ovsave_real", "pspec", "pspec_real", "pfb_pspec", "ddc", "upfirdn", "pfb_synth", "ddc_upfirdn"):
         _sig(getattr(L, f"redio_{n}_stream_create"), i, C.POINTER(vp), vp)
         _sig(getattr(L, f"redio_{n}_stream_destroy"), i, vp)
         _sig(getattr(L, f"redio_{n}_stream_reset"), i, vp)
         _sig(getattr(L, f"redio_{n}_stream_nout"), sz, vp, sz)
         _sig(getattr(L, f"redio_{n}_stream_pending"), sz, vp)
         _sig(getattr(L, f"redio_{n}_stream_enqueue"), i, vp, vp, sz, vp, C.POINTER(sz), vp)
-    for n in ("chain", "pfb", "pspec", "pfb_pspec", "ddc"):
+    for n in ("chain", "pfb", "pspec", "pfb_pspec", "ddc", "ddc_upfirdn"):
         _sig(getattr(L, f"redio_{n}_stream_create_u8"), i, C.POINTER(vp), vp)
     _sig(L.redio_chain_enqueue, i, vp, vp, sz, vp, vp)
     _sig(L.redio_chain_enqueue_u8, i, vp, vp, sz, vp, vp)
@@ -315,4 +324,4 @@ def check(code, what="redio"):
 
 
 from . import bitfount, dsputils, kissfft, kpn_dev, plans, samplerate  # noqa: E402,F401
-from .plans import Chain, Channelizer, Comm, Ddc, Fft, Fftr, Fir, Graph, OverlapSave, OverlapSaveReal, PolyphaseSpectrum, PowerSpectrum, PowerSpectrumReal, Src, Stream, Synthesizer, SynthesizerStream, Upfirdn, channelizer_all_to_all, current_stream, planes_to_rows, rows_to_planes, synth_f32, synth_iq  # noqa: E402,F401
+from .plans import Chain, Channelizer, Comm, Ddc, DdcUpfirdn, Fft, Fftr, Fir, Graph, OverlapSave, OverlapSaveReal, PolyphaseSpectrum, PowerSpectrum, PowerSpectrumReal, Src, Stream, Synthesizer, SynthesizerStream, Upfirdn, channelizer_all_to_all, current_stream, planes_to_rows, rows_to_planes, synth_f32, synth_iq  # noqa: E402,F401

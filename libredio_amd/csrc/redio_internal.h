@@ -73,6 +73,11 @@ struct UpfirdnPhase;
 hipError_t launch_upfirdn(const void *x, long n_in, const UpfirdnPhase *ph, const float *taps, long K, long U, long D, void *y, long n_out, bool cplx,
                           bool fused, hipStream_t s);
 
+// ddc_upfirdn_kernels.hip: the tuned resampler (the tuner's mix fused into the resampler's tile load).  x, tab, first_mod as launch_ddc's;
+// ph, taps, K, U, D, y, n_out as launch_upfirdn's, the outputs cf32
+hipError_t launch_ddc_upfirdn(const void *x, bool u8, long n_in, unsigned first_mod, const float2 *tab, unsigned L, const UpfirdnPhase *ph, const float *taps,
+                              long K, long U, long D, float2 *y, long n_out, bool fused, hipStream_t s);
+
 // fft_kernels.hip
 constexpr int FFT_MAX_STAGES = 32;
 struct FftPlanDev {
@@ -214,11 +219,15 @@ inline int num_cus()
 } // namespace redio
 
 // plan shapes for the carried-history layer (stream_carry.hip); defined next to each plan struct
-struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real; struct redio_pspec; struct redio_pspec_real; struct redio_pfb_pspec; struct redio_ddc; struct redio_upfirdn; struct redio_pfb_synth;
+struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real; struct redio_pspec; struct redio_pspec_real; struct redio_pfb_pspec; struct redio_ddc; struct redio_upfirdn; struct redio_pfb_synth; struct redio_ddc_upfirdn;
 void redio_upfirdn_shape(const redio_upfirdn *h, size_t *period_out, size_t *period_in, size_t *window, unsigned *flags, int *device);
 // redio_upfirdn_enqueue for the carried-history layer: exactly `periods` periods (periods * period_out outputs) from n_in samples
 int redio_upfirdn_enqueue_periods(redio_upfirdn *h, const void *d_in, size_t n_in, size_t periods, void *d_out, void *stream);
 void redio_ddc_shape(const redio_ddc *h, size_t *ntaps, size_t *decim, int *device);
+void redio_ddc_upfirdn_shape(const redio_ddc_upfirdn *h, size_t *period_out, size_t *period_in, size_t *window, int *device);
+// redio_ddc_upfirdn_enqueue[_u8] for the carried-history layer: exactly `periods` periods from n_in samples (u8: 2 * n_in bytes)
+int redio_ddc_upfirdn_enqueue_periods(redio_ddc_upfirdn *h, const void *d_in, size_t n_in, bool u8, size_t periods, uint64_t first_index, void *d_out,
+                                      void *stream);
 void redio_fir_shape(const redio_fir *h, size_t *ntaps, size_t *decim, unsigned *flags, int *device);
 void redio_chain_shape(const redio_chain *h, size_t *ntaps, size_t *decim, int *nfft, int *device);
 void redio_pfb_shape(const redio_pfb *h, int *nchan, int *taps_per_branch, int *device);

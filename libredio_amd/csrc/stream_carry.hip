@@ -17,6 +17,8 @@
 //     resampler    W = Wp                          H = D'             unit = 1 period of U' output samples (upfirdn_core.h); every window begins
 //                  at a multiple of D' samples of the stream, which is phase 0: samples are carried, no phase.  The plan is told how many
 //                  periods to produce: a stateless call on the same samples would write more than whole periods when U > D
+//     tuned resampler  the resampler's W, H and unit (from cf32 samples or u8 I/Q byte pairs) with the tuner's carried phase: every window's
+//                  first sample has a stream index, handed to the plan as first_index
 //     synthesis bank  W = nchan*taps_per_branch    H = nchan          unit = 1 output row (nchan samples of the one stream, from rows of nchan channel values)
 // so one layer serves them all.  The handle keeps the stream's unconsumed tail (fewer than W samples) on the device.
 // A call with n new samples
@@ -63,7 +65,7 @@ hipError_t seam_copy(void *dst, const void *src, size_t bytes, hipStream_t st)
     SEAM_GO(uint8_t)
 #undef SEAM_GO
 }
-enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8, K_PSPEC_REAL, K_PFB_PSPEC, K_PFB_PSPEC_U8, K_DDC, K_DDC_U8, K_UPFIRDN, K_PFB_SYNTH }; // _U8: the samples are interleaved u8 I/Q byte pairs
+enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8, K_PSPEC_REAL, K_PFB_PSPEC, K_PFB_PSPEC_U8, K_DDC, K_DDC_U8, K_UPFIRDN, K_PFB_SYNTH, K_DDC_UPFIRDN, K_DDC_UPFIRDN_U8 }; // _U8: the samples are interleaved u8 I/Q byte pairs
 struct Carry {
     int device = 0;
     Kind kind = K_FIR;
@@ -97,6 +99,8 @@ int run(const Carry &c, const void *d_in, size_t n_in, size_t units, unsigned lo
 {
     switch (c.kind) {
     case K_UPFIRDN: return redio_upfirdn_enqueue_periods((redio_upfirdn *)c.plan, d_in, n_in, units, d_out, stream);
+    case K_DDC_UPFIRDN: return redio_ddc_upfirdn_enqueue_periods((redio_ddc_upfirdn *)c.plan, d_in, n_in, false, units, first, d_out, stream);
+    case K_DDC_UPFIRDN_U8: return redio_ddc_upfirdn_enqueue_periods((redio_ddc_upfirdn *)c.plan, d_in, n_in, true, units, first, d_out, stream);
     case K_DDC: return redio_ddc_enqueue((redio_ddc *)c.plan, d_in, n_in, first, d_out, stream);
     case K_DDC_U8: return redio_ddc_enqueue_u8((redio_ddc *)c.plan, d_in, 2 * n_in, first, d_out, stream);
     case K_FIR: return redio_fir_enqueue((redio_fir *)c.plan, d_in, n_in, d_out, stream);
@@ -240,6 +244,7 @@ struct redio_pfb_pspec_stream { Carry *c; };
 struct redio_ddc_stream { Carry *c; };
 struct redio_upfirdn_stream { Carry *c; };
 struct redio_pfb_synth_stream { Carry *c; };
+struct redio_ddc_upfirdn_stream { Carry *c; };
 
 #define RD_STREAM_API(NAME)                                                                                                     \
     extern "C" int redio_##NAME##_stream_destroy(redio_##NAME##_stream *h)                                                      \
@@ -272,6 +277,7 @@ RD_STREAM_API(pfb_pspec)
 RD_STREAM_API(ddc)
 RD_STREAM_API(upfirdn)
 RD_STREAM_API(pfb_synth)
+RD_STREAM_API(ddc_upfirdn)
 
 template <typename Hd>
 static int make(Hd **h, Kind kind, void *plan, int dev, size_t W, size_t H, size_t in_elem, size_t unit_out, size_t out_elem, uintptr_t align = 0)
@@ -443,6 +449,20 @@ extern "C" int redio_upfirdn_stream_create(redio_upfirdn_stream **h, redio_upfir
     const size_t el = (flags & REDIO_FIR_COMPLEX) ? 8 : 4;
     return make(h, K_UPFIRDN, plan, dev, Wp, Dp, el, Up, el);
 }
+// the tuned resampler's two streams: the resampler's geometry (one period per unit, windows at multiples of D') and the tuner's phase
+// (total_in is the stream index of the next new sample; it moves only when a call commits).  The u8 form carries its history as bytes
+static int make_ddc_upfirdn(redio_ddc_upfirdn_stream **h, redio_ddc_upfirdn *plan, bool u8)
+{
+    if (!h) return REDIO_ERR_ARG;
+    *h = nullptr;
+    if (!plan) return REDIO_ERR_ARG;
+    size_t Up, Dp, Wp; int dev;
+    redio_ddc_upfirdn_shape(plan, &Up, &Dp, &Wp, &dev);
+    return make(h, u8 ? K_DDC_UPFIRDN_U8 : K_DDC_UPFIRDN, plan, dev, Wp, Dp, u8 ? 2 : 8, Up, 8);
+}
+extern "C" int redio_ddc_upfirdn_stream_create(redio_ddc_upfirdn_stream **h, redio_ddc_upfirdn *plan) { return make_ddc_upfirdn(h, plan, false); }
+extern "C" int redio_ddc_upfirdn_stream_create_u8(redio_ddc_upfirdn_stream **h, redio_ddc_upfirdn *plan) { return make_ddc_upfirdn(h, plan, true); }
+extern "C" uint64_t redio_ddc_upfirdn_stream_index(const redio_ddc_upfirdn_stream *h) { return h ? h->c->total_in : 0; }
 // the synthesis filterbank's stream: P - 1 whole rows and a partial row carried.  Route 0's scratch is sized here for the seam windows
 // (at most 2*W values per head run; nothing on route 1)
 extern "C" int redio_pfb_synth_stream_create(redio_pfb_synth_stream **h, redio_pfb_synth *plan)

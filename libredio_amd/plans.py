@@ -169,6 +169,76 @@ class Upfirdn:
             self._h = None
 
 
+class DdcUpfirdn:
+    """redio_ddc_upfirdn_*: the tuned resampler -- kpn::mul_vecs (kpn.rs:198-203) by the periodic oscillator table `osc` (as Ddc's), then
+    the rational resampler (as Upfirdn's: up by `up`, the FIR of dsputils::convolve, dsputils.rs:30-32, down by `down`) in one kernel;
+    bit for bit Upfirdn(taps, up, down, complex_input=True)(x * osc tiled from `first`).  complex64 in (or uint8 I/Q bytes through
+    from_bytes), complex64 out."""
+
+    def __init__(self, osc, taps, up, down, fused=False):
+        t, p = _taps(taps)
+        w = np.ascontiguousarray(osc, dtype=np.complex64).reshape(-1)
+        self.ntaps, self.up, self.down, self.complex_input = len(t), int(up), int(down), True
+        self._h = C.c_void_p()
+        check(lib().redio_ddc_upfirdn_create(C.byref(self._h), w.view(np.float32).ctypes.data_as(_pf), len(w), p, len(t), self.up, self.down,
+                                             REDIO_FIR_FUSED if fused else 0), "ddc_upfirdn_create")
+
+    def nout(self, n_in):
+        return lib().redio_ddc_upfirdn_nout(self._h, n_in)
+
+    @property
+    def route(self):
+        """redio_ddc_upfirdn_route: 1 the phase-walking tiled kernel, 2 the direct one."""
+        return lib().redio_ddc_upfirdn_route(self._h)
+
+    @property
+    def period(self):
+        """the oscillator's"""
+        return lib().redio_ddc_upfirdn_period(self._h)
+
+    @property
+    def period_out(self):
+        """U' = up / gcd(up, down): outputs per period"""
+        return lib().redio_ddc_upfirdn_period_out(self._h)
+
+    @property
+    def period_in(self):
+        """D' = down / gcd(up, down): new samples per period"""
+        return lib().redio_ddc_upfirdn_period_in(self._h)
+
+    @property
+    def window(self):
+        """Wp: samples one period reads"""
+        return lib().redio_ddc_upfirdn_window(self._h)
+
+    def _run(self, fn, x, nsamp, count, first, out):
+        import torch
+        n = self.nout(nsamp)
+        if out is None:
+            out = torch.empty(n, dtype=torch.complex64, device=x.device)
+        assert out.dtype == torch.complex64 and out.numel() >= n
+        check(getattr(lib(), fn)(self._h, _dev_ptr(x), count, int(first), _dev_ptr(out), current_stream()), fn[6:])
+        return out[:n]
+
+    def __call__(self, x, first=0, out=None):
+        """`first`: the stream index of x[0] (the table entry of sample n is osc[(first + n) % period])."""
+        import torch
+        assert x.dtype == torch.complex64
+        return self._run("redio_ddc_upfirdn_enqueue", x, x.numel(), x.numel(), first, out)
+
+    def from_bytes(self, raw, first=0, out=None):
+        """redio_ddc_upfirdn_enqueue_u8: the receiver's interleaved u8 I/Q bytes (rtlsdr.rs:159-162); bitfount.data_to_samples(raw)
+        through __call__, bit for bit."""
+        import torch
+        assert raw.dtype == torch.uint8 and raw.numel() % 2 == 0
+        return self._run("redio_ddc_upfirdn_enqueue_u8", raw, raw.numel() // 2, raw.numel(), first, out)
+
+    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
+        if getattr(self, "_h", None):
+            _safe_destroy("redio_ddc_upfirdn_destroy", self._h)
+            self._h = None
+
+
 class Fft:
     """redio_fft_*: batched kissfft::fft blocks (kissfft.rs:18-31), unnormalised."""
 
@@ -367,19 +437,20 @@ class Chain:
 
 
 class Stream:
-    """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec,pspec_real,pfb_pspec,ddc,upfirdn,pfb_synth}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
+    """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec,pspec_real,pfb_pspec,ddc,upfirdn,ddc_upfirdn,pfb_synth}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
     segmentation of the input gives the bits of one stateless call on the whole stream (the stateless plans keep the
     reference's per-message semantics, dsputils.rs:30-32).  `plan` is a Fir, Chain, Channelizer, OverlapSave, OverlapSaveReal, PowerSpectrum
     (complex64 in, float32 rows out), PowerSpectrumReal (float32 in, float32 rows out), PolyphaseSpectrum (complex64 in, float32 rows
     of nchan out), Ddc (the tuner: the oscillator's phase is carried with the history) or Upfirdn (whole periods of period_out samples
-    from the window that starts at a multiple of period_in samples of the stream), or a Synthesizer (channel values in, whole rows of
+    from the window that starts at a multiple of period_in samples of the stream), a DdcUpfirdn (the tuned resampler: the resampler's whole
+    periods with the oscillator's phase carried as the tuner's is), or a Synthesizer (channel values in, whole rows of
     nchan samples of the one stream out: see SynthesizerStream)."""
 
     def __init__(self, plan, u8=False):
-        """u8=True (Chain, Channelizer, PowerSpectrum, PolyphaseSpectrum and Ddc): the stream arrives as the receiver's interleaved u8 I/Q
-        bytes (uint8 tensors, two bytes per sample; redio_{chain,pfb,pspec,pfb_pspec}_stream_create_u8)."""
-        kind = {Fir: "fir", Chain: "chain", Ddc: "ddc", Upfirdn: "upfirdn"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec", "PowerSpectrumReal": "pspec_real", "PolyphaseSpectrum": "pfb_pspec", "Synthesizer": "pfb_synth"}[type(plan).__name__]
-        assert not u8 or kind in ("chain", "pfb", "pspec", "pfb_pspec", "ddc")
+        """u8=True (Chain, Channelizer, PowerSpectrum, PolyphaseSpectrum, Ddc and DdcUpfirdn): the stream arrives as the receiver's interleaved u8 I/Q
+        bytes (uint8 tensors, two bytes per sample; redio_{chain,pfb,pspec,pfb_pspec,ddc,ddc_upfirdn}_stream_create_u8)."""
+        kind = {Fir: "fir", Chain: "chain", Ddc: "ddc", Upfirdn: "upfirdn", DdcUpfirdn: "ddc_upfirdn"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec", "PowerSpectrumReal": "pspec_real", "PolyphaseSpectrum": "pfb_pspec", "Synthesizer": "pfb_synth"}[type(plan).__name__]
+        assert not u8 or kind in ("chain", "pfb", "pspec", "pfb_pspec", "ddc", "ddc_upfirdn")
         self._kind, self._plan, self._u8 = kind, plan, bool(u8)          # the plan must outlive the stream handle
         self._h = C.c_void_p()
         check(getattr(lib(), f"redio_{kind}_stream_create" + ("_u8" if u8 else ""))(C.byref(self._h), plan._h), f"{kind}_stream_create")
@@ -399,7 +470,7 @@ class Stream:
 
     @property
     def index(self):
-        """redio_ddc_stream_index (a Ddc stream only): the stream index of the next new sample, which is the oscillator's phase."""
+        """redio_ddc_stream_index / redio_ddc_upfirdn_stream_index (a Ddc or DdcUpfirdn stream only): the stream index of the next new sample, which is the oscillator's phase."""
         return self._f("index")(self._h)
 
     def __call__(self, x, out=None):

@@ -1,5 +1,5 @@
 """Throughput of the non-headline configs of BASELINE.json on one MI355X (own measurements; bench.py
-stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit|pfbpspecp2|pfbpspecp2split|ddc|ddcu8|upfirdn|pfbsynth]..."""
+stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit|pfbpspecp2|pfbpspecp2split|ddc|ddcu8|upfirdn|pfbsynth|ddcupfirdn|ddcupfirdnu8]..."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, libredio_amd as R
@@ -719,4 +719,60 @@ if "ddc" in which or "ddcu8" in which:
                 del plan, osc
             print(f"{'DDC-U8' if u8 else 'DDC'} {k} taps /{d}: period 65536 / period 24 = {per[65536]/per[24]:.3f}")
             del fir, out
+        del raw, mixed, conv
+if "ddcupfirdn" in which or "ddcupfirdnu8" in which:
+    # the tuned resampler (redio_ddc_upfirdn_*: oscillator mix fused into the resampler's tile load) on 2^28 input samples, fused fold,
+    # against the route it replaces, timed alternately (twice each, the smaller time printed) in this one process: (a) redio_mul_c32 on a
+    # PRE-MATERIALISED oscillator stream (its generation is not counted: a head start for the old route) + redio_upfirdn_enqueue -- for
+    # u8 also + redio_data_to_samples in front -- after the two outputs were compared bit for bit, and (b) redio_upfirdn_enqueue alone on
+    # already-mixed samples (no mix at all: no bar).  Share of 8 TB/s on the algorithmic bytes per OUTPUT: 8 + 8 D / U from cf32,
+    # 8 + 2 D / U from u8.  160/147 (route 2) is compared at 2^22 samples, both sides, as the `upfirdn` leg does; its own time at 2^28 too.
+    from libredio_amd.plans import _dev_ptr, current_stream
+    x = R.synth_iq(1, 0, n)
+    for leg in [l for l in ("ddcupfirdn", "ddcupfirdnu8") if l in which]:
+        u8 = leg == "ddcupfirdnu8"
+        name = "DDCUPFIRDN-U8" if u8 else "DDCUPFIRDN"
+        raw = torch.randint(0, 256, (2 * n,), dtype=torch.uint8, device="cuda") if u8 else None
+        mixed, conv = torch.empty_like(x), (torch.empty_like(x) if u8 else None)
+        for U, D, K in ((2, 1, 63), (3, 2, 96), (2, 3, 63), (4, 5, 127), (160, 147, 3841)):
+            taps = R.dsputils.lpf_corrected(K, 0.4 / max(U, D))
+            res = R.Upfirdn(taps, U, D, complex_input=True, fused=True)
+            out, out_old = (torch.empty(res.nout(n), dtype=torch.complex64, device="cuda") for _ in range(2))
+            nc = n if U <= 4 else 1 << 22  # the samples of the comparison
+            outc, outc_old = out[: res.nout(nc)], out_old[: res.nout(nc)]
+            per = {}
+            for period in (24, 65536):
+                w = R.dsputils.osc_table(-5, 24) if period == 24 else R.dsputils.osc_table(1, 65536)
+                plan = R.DdcUpfirdn(w, taps, U, D, fused=True)
+                osc = torch.from_numpy(w).cuda().repeat((nc + period - 1) // period)[:nc].contiguous()
+
+                def old():
+                    src = x[:nc]
+                    if u8:
+                        R.check(R.lib().redio_data_to_samples(_dev_ptr(raw), 2 * nc, _dev_ptr(conv), current_stream()), "data_to_samples")
+                        src = conv[:nc]
+                    R.check(R.lib().redio_mul_c32(_dev_ptr(src), _dev_ptr(osc), _dev_ptr(mixed), nc, current_stream()), "mul_c32")
+                    res(mixed[:nc], out=outc_old)
+                new_c = (lambda: plan.from_bytes(raw[: 2 * nc], out=outc)) if u8 else (lambda: plan(x[:nc], out=outc))
+                new = (lambda: plan.from_bytes(raw, out=out)) if u8 else (lambda: plan(x, out=out))
+                old(); new_c()
+                torch.cuda.synchronize()
+                assert torch.equal(torch.view_as_real(outc).view(torch.int32), torch.view_as_real(outc_old).view(torch.int32)), "plan and composition differ"
+                ms = timeit(new, n=10, warm=3) if nc != n else 1e30
+                ms_new = ms_old = ms_res = 1e30
+                for _ in range(2):
+                    ms_new = min(ms_new, timeit(new_c, n=10, warm=3))
+                    ms_old = min(ms_old, timeit(old, n=5, warm=2))
+                    ms_res = min(ms_res, timeit(lambda: res(mixed[:nc], out=outc_old), n=10, warm=3))
+                if nc == n:
+                    ms = ms_new
+                b = 8 + (2 if u8 else 8) * D / U
+                per[period] = ms
+                print(f"{name} {U}/{D} {K} taps period {period} (route {plan.route}, U'={plan.period_out} D'={plan.period_in} Wp={plan.window}): {ms:.3f} ms  "
+                      f"{out.numel()/ms/1e6:.1f} GS/s out  {b*out.numel()/ms/1e6:.0f} GB/s algorithmic ({b*out.numel()/ms/1e6/8000:.1%} of 8 TB/s) | at {nc} samples, "
+                      f"outputs bit-equal: {ms_new:.3f} ms against (a) {'data_to_samples + ' if u8 else ''}mul_c32 + upfirdn: {ms_old:.3f} ms, plan / (a) = {ms_new/ms_old:.3f} | "
+                      f"(b) upfirdn alone: {ms_res:.3f} ms, plan / (b) = {ms_new/ms_res:.3f}")
+                del plan, osc
+            print(f"{name} {U}/{D} {K} taps: period 65536 / period 24 = {per[65536]/per[24]:.3f}")
+            del res, out, out_old, outc, outc_old
         del raw, mixed, conv
