@@ -605,6 +605,48 @@ int redio_pfb_synth_set_chunk_rows(redio_pfb_synth *h, size_t rows);
 int redio_pfb_synth_reserve(redio_pfb_synth *h, size_t n_in);
 int redio_pfb_synth_enqueue(redio_pfb_synth *h, const void *d_rows_c32, size_t n_in, void *d_out_c32, void *stream);
 
+/* ---- the oversampled channelizer: a row of nchan channels every hop <= nchan samples (a NEW composition) ----
+ * redio_pfb_* is critically sampled: a row of M channels every M samples, so the prototype's transition band aliases back into the
+ * channel edges.  This is the weighted overlap-add bank with the same prototype and transform and a hop H < M between rows (H = M / 2,
+ * 2x oversampling, is the common case): every channel comes out at M / H times its bandwidth and nothing aliases into its passband.
+ * M = nchan, P = taps_per_branch, H = hop with 1 <= H <= M; the prototype has M P taps in the channelizer's layout,
+ * g_m[p] = proto[M p + m].  For a call on n_in cf32 samples with first_row = F:
+ *     rows = (n_in - M P) / H + 1 (integer division) when n_in >= M P, else 0 (at H = M: redio_pfb_nrows);
+ *     u_r[m] = the fold of dsputils::convolve (dsputils.rs:31) over x[r H + M p + m] * g_m[p], from 0.0f in ascending p = 0 .. P - 1:
+ *       multiply and add rounded separately, or fmaf with REDIO_FIR_FUSED -- the bits of redio_fir on that column;
+ *     v_r[(m + s_r) mod M] = u_r[m] with s_r = ((F + r) H) mod M: a permutation, no arithmetic;
+ *     output row r = kissfft's forward M-point transform of v_r (the bits of a forward redio_fft); layout [row][M], natural channel
+ *       order, packed.
+ * With the shift channel k of every row is referred to absolute time: X_r[k] = sum_n h[n] x[r H + n] W^(k ((F + r) H + n)),
+ * W = e^(-2 pi i / M), so a call on a later part of a stream continues an earlier one when F is the index of its first row.  F + rows
+ * must not pass 2^64.  At H = M the shift is 0 and the rows are redio_pfb_enqueue's (ngroups = 1), bit for bit.
+ * create: NULL h / taps, nchan < 1, taps_per_branch < 1 (what redio_pfb_create refuses), hop == 0 or hop > nchan -> REDIO_ERR_ARG;
+ *   a size redio_fft_create refuses -> its error.  flags: REDIO_FIR_FUSED or 0.
+ * redio_pfb_os_route() says what a call on the plan runs (0 for NULL):
+ *   1  nchan = 64, hop = 32 with taps_per_branch in {4, 8, 16} is ONE kernel, a wavefront per run of output rows (is_fused() == 1):
+ *      8 bytes read and 16 written per input sample, no scratch; it captures without a reserve.
+ *   0  every other plan runs a branch pass (row stride H, rotated store) into plan-owned scratch and its own forward redio_fft over
+ *      those rows, in chunks of at most 64 MiB of whole rows.
+ * set_unfused(h, 1) sends a route-1 plan down route 0 (tests and measurement, as redio_chain_set_unfused): the same bits.
+ * reserve(h, n_in) sizes route 0's scratch (the transform's staging included) for calls of up to n_in samples on the plan's CURRENT
+ *   route, after which an enqueue neither allocates nor synchronises; un-reserved it grows on first use (REDIO_ERR_NOT_RESERVED
+ *   while the stream is being captured).  On route 1 it does nothing.
+ * enqueue: launches only, on the caller's stream; every argument is checked before anything is launched.  NULL handle or buffers,
+ *   overlapping buffers (d_in == d_out included), either pointer not 8-byte aligned -> REDIO_ERR_ARG; fewer than M P samples ->
+ *   REDIO_OK, no launch.  Samples behind the last row's window are not read.
+ * set_chunk_rows: rows per pass of route 0 (0 restores the 64 MiB default) -- for tests of the chunk seam; the same bits. */
+typedef struct redio_pfb_os redio_pfb_os;
+int redio_pfb_os_create(redio_pfb_os **h, const float *proto_taps_host, int nchan, int taps_per_branch, size_t hop, unsigned flags);
+int redio_pfb_os_destroy(redio_pfb_os *h);
+size_t redio_pfb_os_nrows(const redio_pfb_os *h, size_t n_in); /* rows of nchan cf32 out for n_in cf32 samples in */
+size_t redio_pfb_os_hop(const redio_pfb_os *h);                /* 0 for NULL */
+int redio_pfb_os_route(const redio_pfb_os *h);                 /* 1 the 64-channel wave kernel, 0 two passes; 0 for NULL */
+int redio_pfb_os_is_fused(const redio_pfb_os *h);
+int redio_pfb_os_set_unfused(redio_pfb_os *h, int unfused);
+int redio_pfb_os_set_chunk_rows(redio_pfb_os *h, size_t rows);
+int redio_pfb_os_reserve(redio_pfb_os *h, size_t n_in);
+int redio_pfb_os_enqueue(redio_pfb_os *h, const void *d_in_c32, size_t n_in, uint64_t first_row, void *d_out_c32, void *stream);
+
 /* ---- the channelizer's one exchange step over RCCL / xGMI (the only collective on the path) ----
  * Time-sharded channelizer: every rank runs redio_pfb_enqueue(..., ngroups = G) on its own slice of the stream and
  * holds d_grouped = [G groups][its rows][chans_per_rank cf32]; the exchange sends group q to rank q
@@ -786,6 +828,20 @@ int redio_pfb_synth_stream_reset(redio_pfb_synth_stream *h);
 size_t redio_pfb_synth_stream_nout(const redio_pfb_synth_stream *h, size_t n_new);
 size_t redio_pfb_synth_stream_pending(const redio_pfb_synth_stream *h);
 int redio_pfb_synth_stream_enqueue(redio_pfb_synth_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
+/* the oversampled channelizer as a stream, on the conventions of redio_pfb_stream_*: the unit is one row (nchan cf32) from the
+ * P nchan samples that start at a multiple of hop samples of the stream.  The handle carries the unconsumed samples -- everything from
+ * the next row's first sample on -- and the running row index, which is every call's first_row: the shift continues across messages.
+ * A message may have any length (d_new 8-byte aligned); a stream fed in any pieces concatenates to one redio_pfb_os_enqueue with
+ * first_row = 0 on the whole stream, bit for bit.  reset zeroes both.  Create reserves the plan's scratch for the seam windows
+ * (redio_pfb_os_reserve for the largest message + P nchan keeps longer bodies allocation-free on route 0).  *nout and _stream_nout
+ * count output SAMPLES (rows * nchan); pending() = samples carried. */
+typedef struct redio_pfb_os_stream redio_pfb_os_stream;
+int redio_pfb_os_stream_create(redio_pfb_os_stream **h, redio_pfb_os *plan);
+int redio_pfb_os_stream_destroy(redio_pfb_os_stream *h);
+int redio_pfb_os_stream_reset(redio_pfb_os_stream *h);
+size_t redio_pfb_os_stream_nout(const redio_pfb_os_stream *h, size_t n_new);
+size_t redio_pfb_os_stream_pending(const redio_pfb_os_stream *h);
+int redio_pfb_os_stream_enqueue(redio_pfb_os_stream *h, const void *d_new, size_t n_new, void *d_out, size_t *nout, void *stream);
 
 /* ---- A6: samplerate::resample's native side, src/samplerate/src/samplerate.rs:59-87 ----
  * nchan independent mono streams that share ratio and block lengths (the reference creates one
