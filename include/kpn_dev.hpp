@@ -1007,6 +1007,34 @@ inline void oversampled_channelizer_stream(Receiver<View<std::complex<float>>> u
                              [&](const View<cf> &d, cf *o, size_t *got, void *st) { return redio_pfb_os_stream_enqueue(s, d.data(), d.len, o, got, st); });
 }
 
+// the oversampled synthesis bank (redio_pfb_os_synth_*: the inverse transform of every row of nchan channel values, then a weighted
+// overlap-add at hop <= nchan) as a block.  Per message: every message is a stream of its own, its first row is row F = 0.
+inline void oversampled_synthesizer(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<float> proto, int nchan,
+                                    int taps_per_branch, size_t hop, bool fused)
+{
+    using cf = std::complex<float>;
+    redio_pfb_os_synth *h = nullptr;
+    check(redio_pfb_os_synth_create(&h, proto.data(), nchan, taps_per_branch, hop, fused ? REDIO_FIR_FUSED : 0));
+    struct G { redio_pfb_os_synth *h; ~G() { redio_pfb_os_synth_destroy(h); } } g{h};
+    detail::run_block<cf, cf>(u, v, [&](const View<cf> &d) { return redio_pfb_os_synth_nout(h, d.len); },
+                              [&](const View<cf> &d, const View<cf> &o, void *st) { return redio_pfb_os_synth_enqueue(h, d.data(), d.len, 0, o.data(), st); });
+}
+
+// ... and as a stream: messages of any length, the unconsumed rows and the running row index carried, whole hops of samples sent
+inline void oversampled_synthesizer_stream(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<float> proto, int nchan,
+                                           int taps_per_branch, size_t hop, bool fused)
+{
+    using cf = std::complex<float>;
+    redio_pfb_os_synth *h = nullptr;
+    check(redio_pfb_os_synth_create(&h, proto.data(), nchan, taps_per_branch, hop, fused ? REDIO_FIR_FUSED : 0));
+    redio_pfb_os_synth_stream *s = nullptr;
+    const int rc = redio_pfb_os_synth_stream_create(&s, h);
+    struct G { redio_pfb_os_synth *h; redio_pfb_os_synth_stream *s; ~G() { redio_pfb_os_synth_stream_destroy(s); redio_pfb_os_synth_destroy(h); } } g{h, s};
+    check(rc);
+    detail::run_stream_block(u, v, [&](size_t len) { return redio_pfb_os_synth_stream_nout(s, len); },
+                             [&](const View<cf> &d, cf *o, size_t *got, void *st) { return redio_pfb_os_synth_stream_enqueue(s, d.data(), d.len, o, got, st); });
+}
+
 inline void overlap_save_stream(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<float> taps, int nfft)
 {
     using cf = std::complex<float>;

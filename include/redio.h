@@ -931,4 +931,7 @@ int redio_synth_f32(void *d_out, uint32_t seed, uint64_t first_sample, size_t n,
 #ifdef __cplusplus
 }
 #endif
+/* the oversampled synthesis bank, the way back from the oversampled channelizer's rows to one stream: its contract
+ * and declarations, in the style of the plans above, are in a header of their own that this one brings in */
+#include "redio_pfb_os_synth.h"
 #endif /* REDIO_H */

@@ -150,7 +150,7 @@ def lib():
     _sig(L.redio_fft_reserve, i, vp, sz)
     _sig(L.redio_pfb_reserve, i, vp, sz, i)
     _sig(L.redio_pfb_reserve_two_pass, i, vp, sz, i)
-    for n in ("fir", "chain", "pfb", "ovsave", "ovsave_real", "pspec", "pspec_real", "pfb_pspec", "ddc", "upfirdn", "pfb_synth", "ddc_upfirdn", "pfb_os"):
+    for n in ("fir", "chain", "pfb", "ovsave", "ovsave_real", "pspec", "pspec_real", "pfb_pspec", "ddc", "upfirdn", "pfb_synth", "ddc_upfirdn", "pfb_os", "pfb_os_synth"):
         _sig(getattr(L, f"redio_{n}_stream_create"), i, C.POINTER(vp), vp)
         _sig(getattr(L, f"redio_{n}_stream_destroy"), i, vp)
         _sig(getattr(L, f"redio_{n}_stream_reset"), i, vp)
@@ -240,6 +240,16 @@ def lib():
     _sig(L.redio_pfb_os_set_chunk_rows, i, vp, sz)
     _sig(L.redio_pfb_os_reserve, i, vp, sz)
     _sig(L.redio_pfb_os_enqueue, i, vp, vp, sz, C.c_uint64, vp, vp)
+    _sig(L.redio_pfb_os_synth_create, i, C.POINTER(vp), pf, i, i, sz, u)
+    _sig(L.redio_pfb_os_synth_destroy, i, vp)
+    _sig(L.redio_pfb_os_synth_nout, sz, vp, sz)
+    _sig(L.redio_pfb_os_synth_hop, sz, vp)
+    _sig(L.redio_pfb_os_synth_route, i, vp)
+    _sig(L.redio_pfb_os_synth_is_fused, i, vp)
+    _sig(L.redio_pfb_os_synth_set_unfused, i, vp, i)
+    _sig(L.redio_pfb_os_synth_set_chunk_rows, i, vp, sz)
+    _sig(L.redio_pfb_os_synth_reserve, i, vp, sz)
+    _sig(L.redio_pfb_os_synth_enqueue, i, vp, vp, sz, C.c_uint64, vp, vp)
     psz = C.POINTER(sz)
     _sig(L.redio_data_to_samples, i, vp, sz, vp, vp)
     _sig(L.redio_norm_c32, i, vp, sz, vp, vp)
@@ -334,4 +344,4 @@ def check(code, what="redio"):
 
 
 from . import bitfount, dsputils, kissfft, kpn_dev, plans, samplerate  # noqa: E402,F401
-from .plans import Chain, Channelizer, Comm, Ddc, DdcUpfirdn, Fft, Fftr, Fir, Graph, OverlapSave, OverlapSaveReal, OversampledChannelizer, OversampledChannelizerStream, PolyphaseSpectrum, PowerSpectrum, PowerSpectrumReal, Src, Stream, Synthesizer, SynthesizerStream, Upfirdn, channelizer_all_to_all, current_stream, planes_to_rows, rows_to_planes, synth_f32, synth_iq  # noqa: E402,F401
+from .plans import Chain, Channelizer, Comm, Ddc, DdcUpfirdn, Fft, Fftr, Fir, Graph, OverlapSave, OverlapSaveReal, OversampledChannelizer, OversampledChannelizerStream, OversampledSynthesizer, OversampledSynthesizerStream, PolyphaseSpectrum, PowerSpectrum, PowerSpectrumReal, Src, Stream, Synthesizer, SynthesizerStream, Upfirdn, channelizer_all_to_all, current_stream, planes_to_rows, rows_to_planes, synth_f32, synth_iq  # noqa: E402,F401

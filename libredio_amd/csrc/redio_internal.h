@@ -219,7 +219,7 @@ inline int num_cus()
 } // namespace redio
 
 // plan shapes for the carried-history layer (stream_carry.hip); defined next to each plan struct
-struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real; struct redio_pspec; struct redio_pspec_real; struct redio_pfb_pspec; struct redio_ddc; struct redio_upfirdn; struct redio_pfb_synth; struct redio_ddc_upfirdn; struct redio_pfb_os;
+struct redio_fir; struct redio_chain; struct redio_pfb; struct redio_ovsave; struct redio_ovsave_real; struct redio_pspec; struct redio_pspec_real; struct redio_pfb_pspec; struct redio_ddc; struct redio_upfirdn; struct redio_pfb_synth; struct redio_ddc_upfirdn; struct redio_pfb_os; struct redio_pfb_os_synth;
 void redio_upfirdn_shape(const redio_upfirdn *h, size_t *period_out, size_t *period_in, size_t *window, unsigned *flags, int *device);
 // redio_upfirdn_enqueue for the carried-history layer: exactly `periods` periods (periods * period_out outputs) from n_in samples
 int redio_upfirdn_enqueue_periods(redio_upfirdn *h, const void *d_in, size_t n_in, size_t periods, void *d_out, void *stream);
@@ -233,6 +233,7 @@ void redio_chain_shape(const redio_chain *h, size_t *ntaps, size_t *decim, int *
 void redio_pfb_shape(const redio_pfb *h, int *nchan, int *taps_per_branch, int *device);
 void redio_pfb_synth_shape(const redio_pfb_synth *h, int *nchan, int *taps_per_branch, int *device);
 void redio_pfb_os_shape(const redio_pfb_os *h, int *nchan, int *taps_per_branch, size_t *hop, int *device);
+void redio_pfb_os_synth_shape(const redio_pfb_os_synth *h, int *nchan, int *taps_per_branch, size_t *hop, int *device);
 void redio_ovsave_shape(const redio_ovsave *h, int *nfft, size_t *hop, int *device);
 void redio_ovsave_real_shape(const redio_ovsave_real *h, int *nfft, size_t *hop, int *device);
 void redio_pspec_shape(const redio_pspec *h, int *nfft, size_t *integrate, size_t *step, int *device);

@@ -22,6 +22,8 @@
 //     synthesis bank  W = nchan*taps_per_branch    H = nchan          unit = 1 output row (nchan samples of the one stream, from rows of nchan channel values)
 //     oversampled channelizer  W = nchan*taps_per_branch  H = hop     unit = 1 row (nchan samples); the running row index is carried too: every
 //                  window begins at a multiple of H samples of the stream, so the index of a run's first row is its first sample's stream index / H
+//     oversampled synthesis bank  W = nchan*ceil(nchan*taps_per_branch/hop)  H = nchan  unit = 1 hop (hop samples of the one stream, from rows of nchan
+//                  channel values); the running row index is carried too: a run's first value is the first of a row, its stream index / nchan
 // so one layer serves them all.  The handle keeps the stream's unconsumed tail (fewer than W samples) on the device.
 // A call with n new samples
 //   1. appends the first min(n, W-1) new samples to the tail in a plan-owned staging buffer (one small copy),
@@ -67,7 +69,7 @@ hipError_t seam_copy(void *dst, const void *src, size_t bytes, hipStream_t st)
     SEAM_GO(uint8_t)
 #undef SEAM_GO
 }
-enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8, K_PSPEC_REAL, K_PFB_PSPEC, K_PFB_PSPEC_U8, K_DDC, K_DDC_U8, K_UPFIRDN, K_PFB_SYNTH, K_DDC_UPFIRDN, K_DDC_UPFIRDN_U8, K_PFB_OS }; // _U8: the samples are interleaved u8 I/Q byte pairs
+enum Kind { K_FIR, K_CHAIN, K_PFB, K_OVSAVE, K_CHAIN_U8, K_PFB_U8, K_OVSAVE_REAL, K_PSPEC, K_PSPEC_U8, K_PSPEC_REAL, K_PFB_PSPEC, K_PFB_PSPEC_U8, K_DDC, K_DDC_U8, K_UPFIRDN, K_PFB_SYNTH, K_DDC_UPFIRDN, K_DDC_UPFIRDN_U8, K_PFB_OS, K_PFB_OS_SYNTH }; // _U8: the samples are interleaved u8 I/Q byte pairs
 struct Carry {
     int device = 0;
     Kind kind = K_FIR;
@@ -118,6 +120,7 @@ int run(const Carry &c, const void *d_in, size_t n_in, size_t units, unsigned lo
     case K_PFB_PSPEC_U8: return redio_pfb_pspec_enqueue_u8((redio_pfb_pspec *)c.plan, d_in, 2 * n_in, d_out, stream);
     case K_PFB_SYNTH: return redio_pfb_synth_enqueue((redio_pfb_synth *)c.plan, d_in, n_in, d_out, stream);
     case K_PFB_OS: return redio_pfb_os_enqueue((redio_pfb_os *)c.plan, d_in, n_in, first / c.H, d_out, stream);
+    case K_PFB_OS_SYNTH: return redio_pfb_os_synth_enqueue((redio_pfb_os_synth *)c.plan, d_in, n_in, first / c.H, d_out, stream);
     case K_OVSAVE_REAL: return redio_ovsave_real_enqueue_any((redio_ovsave_real *)c.plan, d_in, n_in, d_out, stream); // a unit may start on an odd sample
     }
     return REDIO_ERR_ARG;
@@ -249,6 +252,7 @@ struct redio_upfirdn_stream { Carry *c; };
 struct redio_pfb_synth_stream { Carry *c; };
 struct redio_ddc_upfirdn_stream { Carry *c; };
 struct redio_pfb_os_stream { Carry *c; };
+struct redio_pfb_os_synth_stream { Carry *c; };
 
 #define RD_STREAM_API(NAME)                                                                                                     \
     extern "C" int redio_##NAME##_stream_destroy(redio_##NAME##_stream *h)                                                      \
@@ -283,6 +287,7 @@ RD_STREAM_API(upfirdn)
 RD_STREAM_API(pfb_synth)
 RD_STREAM_API(ddc_upfirdn)
 RD_STREAM_API(pfb_os)
+RD_STREAM_API(pfb_os_synth)
 
 template <typename Hd>
 static int make(Hd **h, Kind kind, void *plan, int dev, size_t W, size_t H, size_t in_elem, size_t unit_out, size_t out_elem, uintptr_t align = 0)
@@ -494,4 +499,19 @@ extern "C" int redio_pfb_os_stream_create(redio_pfb_os_stream **h, redio_pfb_os 
     const int rr = redio_pfb_os_reserve(plan, 2 * (size_t)M * P);
     if (rr) return rr;
     return make(h, K_PFB_OS, plan, dev, (size_t)M * P, H, 8, (size_t)M, 8, 7);
+}
+// the oversampled synthesis bank's stream: L - 1 whole rows and a partial row carried (L = ceil(M P / H) rows make one hop), and with them
+// the running row index (a run's first value is the first of a row: `first / M` in run()).  Route 0's scratch is sized here for the
+// seam windows (at most 2*W values per head run; nothing on route 1)
+extern "C" int redio_pfb_os_synth_stream_create(redio_pfb_os_synth_stream **h, redio_pfb_os_synth *plan)
+{
+    if (!h) return REDIO_ERR_ARG;
+    *h = nullptr;
+    if (!plan) return REDIO_ERR_ARG;
+    int M, P, dev; size_t H;
+    redio_pfb_os_synth_shape(plan, &M, &P, &H, &dev);
+    const size_t L = ((size_t)M * P + H - 1) / H;
+    const int rr = redio_pfb_os_synth_reserve(plan, 2 * (size_t)M * L);
+    if (rr) return rr;
+    return make(h, K_PFB_OS_SYNTH, plan, dev, (size_t)M * L, (size_t)M, 8, H, 8, 7);
 }

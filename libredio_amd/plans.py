@@ -437,7 +437,7 @@ class Chain:
 
 
 class Stream:
-    """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec,pspec_real,pfb_pspec,ddc,upfirdn,ddc_upfirdn,pfb_synth,pfb_os}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
+    """redio_{fir,chain,pfb,ovsave,ovsave_real,pspec,pspec_real,pfb_pspec,ddc,upfirdn,ddc_upfirdn,pfb_synth,pfb_os,pfb_os_synth}_stream_*: a plan fed as a STREAM with the history carried on the device, so that any
     segmentation of the input gives the bits of one stateless call on the whole stream (the stateless plans keep the
     reference's per-message semantics, dsputils.rs:30-32).  `plan` is a Fir, Chain, Channelizer, OverlapSave, OverlapSaveReal, PowerSpectrum
     (complex64 in, float32 rows out), PowerSpectrumReal (float32 in, float32 rows out), PolyphaseSpectrum (complex64 in, float32 rows
@@ -445,12 +445,13 @@ class Stream:
     from the window that starts at a multiple of period_in samples of the stream), a DdcUpfirdn (the tuned resampler: the resampler's whole
     periods with the oscillator's phase carried as the tuner's is), or a Synthesizer (channel values in, whole rows of
     nchan samples of the one stream out: see SynthesizerStream), or an OversampledChannelizer (whole rows of nchan channels, the running
-    row index carried with the samples: see OversampledChannelizerStream)."""
+    row index carried with the samples: see OversampledChannelizerStream), or an OversampledSynthesizer (channel values in, whole hops of
+    the one stream out: see OversampledSynthesizerStream)."""
 
     def __init__(self, plan, u8=False):
         """u8=True (Chain, Channelizer, PowerSpectrum, PolyphaseSpectrum, Ddc and DdcUpfirdn): the stream arrives as the receiver's interleaved u8 I/Q
         bytes (uint8 tensors, two bytes per sample; redio_{chain,pfb,pspec,pfb_pspec,ddc,ddc_upfirdn}_stream_create_u8)."""
-        kind = {Fir: "fir", Chain: "chain", Ddc: "ddc", Upfirdn: "upfirdn", DdcUpfirdn: "ddc_upfirdn"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec", "PowerSpectrumReal": "pspec_real", "PolyphaseSpectrum": "pfb_pspec", "Synthesizer": "pfb_synth", "OversampledChannelizer": "pfb_os"}[type(plan).__name__]
+        kind = {Fir: "fir", Chain: "chain", Ddc: "ddc", Upfirdn: "upfirdn", DdcUpfirdn: "ddc_upfirdn"}.get(type(plan)) or {"Channelizer": "pfb", "OverlapSave": "ovsave", "OverlapSaveReal": "ovsave_real", "PowerSpectrum": "pspec", "PowerSpectrumReal": "pspec_real", "PolyphaseSpectrum": "pfb_pspec", "Synthesizer": "pfb_synth", "OversampledChannelizer": "pfb_os", "OversampledSynthesizer": "pfb_os_synth"}[type(plan).__name__]
         assert not u8 or kind in ("chain", "pfb", "pspec", "pfb_pspec", "ddc", "ddc_upfirdn")
         self._kind, self._plan, self._u8 = kind, plan, bool(u8)          # the plan must outlive the stream handle
         self._h = C.c_void_p()
@@ -1180,4 +1181,75 @@ class OversampledChannelizerStream(Stream):
 
     def __init__(self, plan):
         assert isinstance(plan, OversampledChannelizer)
+        super().__init__(plan)
+
+
+class OversampledSynthesizer:
+    """redio_pfb_os_synth_*: the oversampled synthesis bank, the OversampledChannelizer's rows back into one stream (contract: DESIGN.md
+    5.6e).  kissfft's unnormalised inverse transform of every row of nchan channel values, then a weighted overlap-add at hop <= nchan:
+    with L = ceil(nchan * taps_per_branch / hop), T rows in give (T - L + 1) * hop complex64 samples, sample n at absolute time
+    (first_row + L - 1) * hop + n.  At hop == nchan this is the Synthesizer.  64 channels at hop 32 with 4 / 8 / 16 taps per branch are
+    one kernel (route WAVE, is_fused); every other plan runs its own inverse transform into scratch and an overlap-add pass (route
+    TWO_PASS): the same bits."""
+
+    TWO_PASS, WAVE = 0, 1
+
+    def __init__(self, proto, nchan=64, taps_per_branch=16, hop=32, fused=True):
+        t, p = _taps(proto)
+        assert len(t) == nchan * taps_per_branch
+        self.nchan, self.taps_per_branch = int(nchan), int(taps_per_branch)
+        self._h = C.c_void_p()
+        check(lib().redio_pfb_os_synth_create(C.byref(self._h), p, self.nchan, self.taps_per_branch, int(hop), REDIO_FIR_FUSED if fused else 0), "pfb_os_synth_create")
+
+    def nout(self, n_in):
+        return lib().redio_pfb_os_synth_nout(self._h, int(n_in))
+
+    @property
+    def hop(self):
+        return lib().redio_pfb_os_synth_hop(self._h)
+
+    @property
+    def route(self):
+        """what a call runs: WAVE (the 64-channel kernel at hop 32) or TWO_PASS"""
+        return lib().redio_pfb_os_synth_route(self._h)
+
+    @property
+    def is_fused(self):
+        return bool(lib().redio_pfb_os_synth_is_fused(self._h))
+
+    def set_unfused(self, unfused=True):
+        """send a WAVE plan down the two-pass route (tests and measurement): the same bits"""
+        check(lib().redio_pfb_os_synth_set_unfused(self._h, int(bool(unfused))), "pfb_os_synth_set_unfused")
+
+    def set_chunk_rows(self, rows):
+        """input rows per pass of the two-pass route (0: the 64 MiB default); for tests of the chunk seam: the same bits"""
+        check(lib().redio_pfb_os_synth_set_chunk_rows(self._h, int(rows)), "pfb_os_synth_set_chunk_rows")
+
+    def reserve(self, n_in):
+        """the two-pass route's scratch for calls of up to n_in values, so that a call never allocates, e.g. inside a Graph"""
+        check(lib().redio_pfb_os_synth_reserve(self._h, int(n_in)), "pfb_os_synth_reserve")
+
+    def __call__(self, x, first_row=0, out=None):
+        import torch
+        assert x.dtype == torch.complex64
+        n = self.nout(x.numel())
+        if out is None:
+            out = torch.empty(n, dtype=torch.complex64, device=x.device)
+        assert out.dtype == torch.complex64 and out.numel() >= n
+        check(lib().redio_pfb_os_synth_enqueue(self._h, _dev_ptr(x), x.numel(), int(first_row), _dev_ptr(out), current_stream()), "pfb_os_synth_enqueue")
+        return out.reshape(-1)[:n]
+
+    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
+        if getattr(self, "_h", None):
+            _safe_destroy("redio_pfb_os_synth_destroy", self._h)
+            self._h = None
+
+
+class OversampledSynthesizerStream(Stream):
+    """redio_pfb_os_synth_stream_*: an OversampledSynthesizer fed as a stream of channel values in messages of ANY length; L - 1 whole rows,
+    the values of a partial row and the running row index are carried, whole hops of samples come out, and any segmentation
+    concatenates to the one-shot call with first_row = 0."""
+
+    def __init__(self, plan):
+        assert isinstance(plan, OversampledSynthesizer)
         super().__init__(plan)

@@ -1,5 +1,5 @@
 """Throughput of the non-headline configs of BASELINE.json on one MI355X (own measurements; bench.py
-stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit|pfbpspecp2|pfbpspecp2split|ddc|ddcu8|upfirdn|pfbsynth|ddcupfirdn|ddcupfirdnu8|pfbos]..."""
+stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit|pfbpspecp2|pfbpspecp2split|ddc|ddcu8|upfirdn|pfbsynth|ddcupfirdn|ddcupfirdnu8|pfbos|pfbossynth]..."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, libredio_amd as R
@@ -812,3 +812,39 @@ if "pfbos" in which:
                  f"(bytes model {(8 * H / M + 8) / 16:.3f})")
         print(line)
         del plan, two, ana, out, out2, rows
+if "pfbossynth" in which:
+    # the oversampled synthesis bank (redio_pfb_os_synth_*: inverse transform per row, then the weighted overlap-add at hop H) on 2^28 channel
+    # values in, fused fold: 64 x 16 and 64 x 4 at hop 32 on the wave kernel (route 1) and the same plans through set_unfused (route 0: the
+    # inverse transform into scratch, then the overlap-add pass), 64 x 16 at hop 16 and 256 x 8 at hop 128 on route 0; and the Synthesizer of
+    # the same prototype on as many values.  The variants of a shape are timed alternately (twice each, the smaller time printed) in this one
+    # process; the two routes' outputs are compared bit for bit.  Share of 8 TB/s on 8 + 8 H / M bytes per channel value (read once, every
+    # sample written once).  The bytes say time per value / the Synthesizer's = (8 + 8 H / M) / 16: 0.75 at hop M / 2.
+    x = R.synth_iq(0x5EED0004, 0, n)
+    for M, P, H in ((64, 16, 32), (64, 4, 32), (64, 16, 16), (256, 8, 128)):
+        h = R.dsputils.lpf_corrected(M * P, 0.45 / M)
+        plan, two, syn = R.OversampledSynthesizer(h, M, P, H, fused=True), R.OversampledSynthesizer(h, M, P, H, fused=True), R.Synthesizer(h, M, P, fused=True)
+        two.set_unfused(True)
+        two.reserve(n)
+        plan.reserve(n)
+        syn.reserve(n)
+        no = plan.nout(n)
+        out = torch.empty(no, dtype=torch.complex64, device="cuda")
+        out2 = torch.empty(no, dtype=torch.complex64, device="cuda") if plan.route == 1 else None
+        outs = torch.empty(syn.nout(n), dtype=torch.complex64, device="cuda")
+        ms = {}
+        legs = {"os": lambda: plan(x, first_row=1, out=out), "two-pass": lambda: two(x, first_row=1, out=out2), "synthesizer": lambda: syn(x, out=outs)}
+        if plan.route == 0:
+            del legs["two-pass"]
+        for _ in range(2):
+            for name, f in legs.items():
+                ms[name] = min(ms.get(name, 1e30), timeit(f, n=10, warm=3))
+        b = 8 + 8 * H / M
+        line = (f"PFBOSSYNTH {M}ch P={P} hop {H} (route {plan.route}): {ms['os']:.3f} ms  {n/ms['os']/1e6:.1f} GS/s in  {b*n/ms['os']/1e6:.0f} GB/s algorithmic "
+                f"({b*n/ms['os']/1e6/8000:.1%} of 8 TB/s on {b:.0f} B/value)")
+        if plan.route == 1:
+            same = torch.equal(torch.view_as_real(out).view(torch.int32), torch.view_as_real(out2).view(torch.int32))
+            line += f" | set_unfused (route {two.route}): {ms['two-pass']:.3f} ms, route 1 / route 0 = {ms['os']/ms['two-pass']:.3f}, outputs bit-equal: {same}"
+        line += (f" | Synthesizer on as many values (route {syn.route}): {ms['synthesizer']:.3f} ms; time per value, oversampled / Synthesizer = "
+                 f"{ms['os']/ms['synthesizer']:.3f} (bytes model {(8 + 8 * H / M) / 16:.3f})")
+        print(line)
+        del plan, two, syn, out, out2, outs
