@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void pfb_branch_kernel(const float2 *__restric
 }
 
 // the branch filters alone: x = rows + P - 1 rows of M cf32, v = rows rows.  Also the second pass of the synthesis filterbank's
-// two-pass route (pfb_synth_api.hip), which runs it behind its inverse transform.
+// two-pass route (pfb_bank.hip), which runs it behind its inverse transform.
 hipError_t launch_pfb_branch(const float2 *x, const float *h, float2 *v, long rows, int M, int P, bool fused, hipStream_t st)
 {
     if (rows <= 0) return hipSuccess;

@@ -9,6 +9,7 @@
 // the second request is served by the compute unit's vector L1 (or by the XCD's L2 while the first is still in flight), not by HBM.
 // No workgroup barrier: a wave's LDS tile is its own.
 #include "fft_wave.h"
+#include "pfb_wave.h"
 #include "pfb_os_core.h"
 #include "redio_internal.h"
 #include <type_traits>
@@ -39,19 +40,7 @@ __global__ __launch_bounds__(256) void pfb_os64_kernel(const float2 *__restrict_
         for (int ti = 0; ti < PFB_TILE; ++ti) dst[ti] = x[PFBOS_H * pfbos_half(first + ti, rows, P) + (unsigned)lane];
     };
     // the transform's twiddles, once per wavefront (pfb_core.h: why not inside the tile loop): 20 scalar and 24 vector registers
-    float2 twone = tw[0], twa1[4], twa2[4], twa3[4], twc1[4], twc2[4], twc3[4];
-#pragma unroll
-    for (int k2 = 0; k2 < 4; ++k2) {
-        twa1[k2] = tw[4 * k2]; twa2[k2] = tw[8 * k2]; twa3[k2] = tw[12 * k2];
-        const int k = k2 + 4 * (lane & 3);
-        twc1[k2] = tw[k]; twc2[k2] = tw[2 * k]; twc3[k2] = tw[3 * k];
-    }
-#pragma unroll
-    for (int k2 = 0; k2 < 4; ++k2) { // kept where they are: no reload, no rematerialisation inside the loop
-        asm volatile("" : "+v"(twc1[k2].x), "+v"(twc1[k2].y), "+v"(twc2[k2].x), "+v"(twc2[k2].y), "+v"(twc3[k2].x), "+v"(twc3[k2].y));
-        asm volatile("" : "+s"(twa1[k2].x), "+s"(twa1[k2].y), "+s"(twa2[k2].x), "+s"(twa2[k2].y), "+s"(twa3[k2].x), "+s"(twa3[k2].y));
-    }
-    asm volatile("" : "+s"(twone.x), "+s"(twone.y));
+    PFB_WAVE_TWIDDLES(tw, lane);
     // exchange 1's store lane of even and of odd tile rows: the shift s_r = 32 ((F + r) & 1), folded into the index
     const int lane_ev = pfbos_x1_lane(lane, 0, fpar), lane_od = pfbos_x1_lane(lane, 1, fpar);
     // the two windows: win[par][slot], taps 0 .. P - 2 of the run's first row of each parity (never past the stream: t0 + 2 P - 3 < rows + 2 P - 3)
@@ -121,18 +110,6 @@ bool pfb_os_supported(int nchan, int taps_per_branch, size_t hop)
     return nchan == PFB_M && hop == (size_t)PFBOS_H && (taps_per_branch == 4 || taps_per_branch == 8 || taps_per_branch == 16);
 }
 
-template <int P>
-static hipError_t launch_pfb_os_t(const float2 *x, const float *h, const float2 *tw, float2 *out, long rows, int fpar, bool fused, hipStream_t s)
-{
-    const long rpw = pfbos_rows_per_wave(rows), nwaves = pfbos_waves(rows);
-    const unsigned grid = (unsigned)((nwaves + 3) / 4);
-    const size_t lds = 4 * PFB_LDS * sizeof(float2);
-    const int wide = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-    if (fused) hipLaunchKernelGGL((pfb_os64_kernel<P, true>), dim3(grid), dim3(256), lds, s, x, h, tw, out, rows, rpw, fpar, wide);
-    else hipLaunchKernelGGL((pfb_os64_kernel<P, false>), dim3(grid), dim3(256), lds, s, x, h, tw, out, rows, rpw, fpar, wide);
-    return hipGetLastError();
-}
-
 // x: 32 (rows - 1) + 64 P cf32 samples; h: 64 P taps; tw64: the 64-point forward plan's table; out: rows rows of 64 cf32;
 // first_row: F, of which only the parity matters at hop 32
 hipError_t launch_pfb_os(const float2 *x, const float *h, const float2 *tw64, float2 *out, long rows, int taps_per_branch, uint64_t first_row, bool fused,
@@ -140,12 +117,42 @@ hipError_t launch_pfb_os(const float2 *x, const float *h, const float2 *tw64, fl
 {
     if (rows <= 0) return hipSuccess;
     const int fpar = (int)(first_row & 1);
-    switch (taps_per_branch) {
-    case 16: return launch_pfb_os_t<16>(x, h, tw64, out, rows, fpar, fused, s);
-    case 8: return launch_pfb_os_t<8>(x, h, tw64, out, rows, fpar, fused, s);
-    case 4: return launch_pfb_os_t<4>(x, h, tw64, out, rows, fpar, fused, s);
-    default: return hipErrorNotSupported;
-    }
+    const long rpw = pfbos_rows_per_wave(rows), nwaves = pfbos_waves(rows);
+    const unsigned grid = (unsigned)((nwaves + 3) / 4);
+    const size_t lds = 4 * PFB_LDS * sizeof(float2);
+    const int wide = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    return pfb_wave_dispatch(taps_per_branch, fused, [&](auto p, auto f) {
+        hipLaunchKernelGGL((pfb_os64_kernel<decltype(p)::value, decltype(f)::value>), dim3(grid), dim3(256), lds, s, x, h, tw64, out, rows, rpw, fpar, wide);
+        return hipGetLastError();
+    });
+}
+
+// Route 0's first pass: pfb_branch_kernel (pfb_api.hip) with a row stride of H: v[r][(m + s_r) mod M] = fold_p x[r H + p M + m] * h[M p + m]
+// (ascending p, the reference's fold).  Rows H apart share samples only where H divides a multiple of M, so a thread is one (row, branch)
+// and walks its P taps; consecutive threads are consecutive m (coalesced loads; the store is two coalesced runs, split where the rotation
+// wraps).  f0 = (F + the pass's first row) mod M.
+template <bool FUSED>
+__global__ __launch_bounds__(256) void pfb_os_branch_kernel(const float2 *__restrict__ x, const float *__restrict__ h, float2 *__restrict__ v, long rows,
+                                                            int M, int P, long H, long f0)
+{
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= rows * M) return;
+    const long r = e / M;
+    const int m = (int)(e - r * M);
+    const float2 *col = x + r * H + m;
+    float2 acc = make_float2(0.f, 0.f);
+    for (int p = 0; p < P; ++p) acc = mac<FUSED>(col[(long)p * M], h[(long)p * M + m], acc);
+    v[r * M + pfbos_rot(m, pfbos_shift(f0, r, M, H), M)] = acc;
+}
+
+__attribute__((visibility("hidden"))) // library-internal: not in the exported symbol set
+hipError_t launch_pfb_os_branch(const float2 *x, const float *h, float2 *v, long rows, int M, int P, long H, long f0, bool fused, hipStream_t st)
+{
+    if (rows <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)((rows * M + 255) / 256);
+    if (fused) hipLaunchKernelGGL(pfb_os_branch_kernel<true>, dim3(grid), dim3(256), 0, st, x, h, v, rows, M, P, H, f0);
+    else hipLaunchKernelGGL(pfb_os_branch_kernel<false>, dim3(grid), dim3(256), 0, st, x, h, v, rows, M, P, H, f0);
+    return hipGetLastError();
 }
 
 } // namespace redio

@@ -8,6 +8,7 @@
 // f32 tile in its own LDS region, and lane = channel folds the tile's rows, in ascending order, into the sums of DESIGN.md 5.3c.
 // A sibling and not a template parameter of pfb64_kernel: that kernel keeps its name and its code.
 #include "fft_wave.h"
+#include "pfb_wave.h"
 #include "pfb_pspec_core.h"
 #include <type_traits>
 #include "redio_internal.h"
@@ -60,19 +61,7 @@ __global__ __launch_bounds__(256) void pfbspec64_kernel(const float2 *__restrict
             dst_rows[ti] = ld(xraw + PFB_M * r + (unsigned)lane);
         }
     };
-    float2 twone = tw[0], twa1[4], twa2[4], twa3[4], twc1[4], twc2[4], twc3[4];
-#pragma unroll
-    for (int k2 = 0; k2 < 4; ++k2) {
-        twa1[k2] = tw[4 * k2]; twa2[k2] = tw[8 * k2]; twa3[k2] = tw[12 * k2];
-        const int k = k2 + 4 * (lane & 3);
-        twc1[k2] = tw[k]; twc2[k2] = tw[2 * k]; twc3[k2] = tw[3 * k];
-    }
-#pragma unroll
-    for (int k2 = 0; k2 < 4; ++k2) { // kept where they are: no reload, no rematerialisation inside the loop
-        asm volatile("" : "+v"(twc1[k2].x), "+v"(twc1[k2].y), "+v"(twc2[k2].x), "+v"(twc2[k2].y), "+v"(twc3[k2].x), "+v"(twc3[k2].y));
-        asm volatile("" : "+s"(twa1[k2].x), "+s"(twa1[k2].y), "+s"(twa2[k2].x), "+s"(twa2[k2].y), "+s"(twa3[k2].x), "+s"(twa3[k2].y));
-    }
-    asm volatile("" : "+s"(twone.x), "+s"(twone.y));
+    PFB_WAVE_TWIDDLES(tw, lane);
     float2 win[P];
 #pragma unroll
     for (int p = 0; p < P - 1; ++p) win[p] = sample(ld(xraw + PFB_M * (t0 + p) + (unsigned)lane));

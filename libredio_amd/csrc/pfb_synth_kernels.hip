@@ -9,6 +9,7 @@
 // clamped per row with scalar arithmetic), keeps the filter window in registers from tile to tile, and stores one output row per wave
 // instruction.  No workgroup barrier: a wave's LDS tile is its own.
 #include "fft_wave.h"
+#include "pfb_wave.h"
 #include "pfb_synth_core.h"
 #include "redio_internal.h"
 
@@ -37,19 +38,7 @@ __global__ __launch_bounds__(256) void pfb_synth64_kernel(const float2 *__restri
         for (int ti = 0; ti < PFB_TILE; ++ti) dst[ti] = x[PFB_M * pfbs_in_row(first + ti, rows, P) + (unsigned)lane];
     };
     // the inverse transform's twiddles, once per wavefront (pfb_core.h: why not inside the tile loop): 20 scalar and 24 vector registers
-    float2 twone = tw[0], twa1[4], twa2[4], twa3[4], twc1[4], twc2[4], twc3[4];
-#pragma unroll
-    for (int k2 = 0; k2 < 4; ++k2) {
-        twa1[k2] = tw[4 * k2]; twa2[k2] = tw[8 * k2]; twa3[k2] = tw[12 * k2];
-        const int k = k2 + 4 * (lane & 3);
-        twc1[k2] = tw[k]; twc2[k2] = tw[2 * k]; twc3[k2] = tw[3 * k];
-    }
-#pragma unroll
-    for (int k2 = 0; k2 < 4; ++k2) { // kept where they are: no reload, no rematerialisation inside the loop
-        asm volatile("" : "+v"(twc1[k2].x), "+v"(twc1[k2].y), "+v"(twc2[k2].x), "+v"(twc2[k2].y), "+v"(twc3[k2].x), "+v"(twc3[k2].y));
-        asm volatile("" : "+s"(twa1[k2].x), "+s"(twa1[k2].y), "+s"(twa2[k2].x), "+s"(twa2[k2].y), "+s"(twa3[k2].x), "+s"(twa3[k2].y));
-    }
-    asm volatile("" : "+s"(twone.x), "+s"(twone.y));
+    PFB_WAVE_TWIDDLES(tw, lane);
     float2 win[P];
 #pragma unroll
     for (int p = 0; p < P; ++p) win[p] = make_float2(0.f, 0.f); // the halo's outputs are never stored: any finite start will do
@@ -105,27 +94,17 @@ bool pfb_synth_supported(int nchan, int taps_per_branch)
     return nchan == PFB_M && (taps_per_branch == 4 || taps_per_branch == 8 || taps_per_branch == 16);
 }
 
-template <int P>
-static hipError_t launch_pfb_synth_t(const float2 *x, const float *h, const float2 *tw, float2 *out, long rows, bool fused, hipStream_t s)
-{
-    const long rpw = pfbs_rows_per_wave(rows), nwaves = pfbs_waves(rows);
-    const unsigned grid = (unsigned)((nwaves + 3) / 4);
-    const size_t lds = 4 * PFB_LDS * sizeof(float2);
-    if (fused) hipLaunchKernelGGL((pfb_synth64_kernel<P, true>), dim3(grid), dim3(256), lds, s, x, h, tw, out, rows, rpw);
-    else hipLaunchKernelGGL((pfb_synth64_kernel<P, false>), dim3(grid), dim3(256), lds, s, x, h, tw, out, rows, rpw);
-    return hipGetLastError();
-}
-
 // x: rows + P - 1 rows of 64 cf32; h: 64 P taps; tw64_inv: the 64-point INVERSE plan's table; out: rows rows of 64 cf32
 hipError_t launch_pfb_synth(const float2 *x, const float *h, const float2 *tw64_inv, float2 *out, long rows, int taps_per_branch, bool fused, hipStream_t s)
 {
     if (rows <= 0) return hipSuccess;
-    switch (taps_per_branch) {
-    case 16: return launch_pfb_synth_t<16>(x, h, tw64_inv, out, rows, fused, s);
-    case 8: return launch_pfb_synth_t<8>(x, h, tw64_inv, out, rows, fused, s);
-    case 4: return launch_pfb_synth_t<4>(x, h, tw64_inv, out, rows, fused, s);
-    default: return hipErrorNotSupported;
-    }
+    const long rpw = pfbs_rows_per_wave(rows), nwaves = pfbs_waves(rows);
+    const unsigned grid = (unsigned)((nwaves + 3) / 4);
+    const size_t lds = 4 * PFB_LDS * sizeof(float2);
+    return pfb_wave_dispatch(taps_per_branch, fused, [&](auto p, auto f) {
+        hipLaunchKernelGGL((pfb_synth64_kernel<decltype(p)::value, decltype(f)::value>), dim3(grid), dim3(256), lds, s, x, h, tw64_inv, out, rows, rpw);
+        return hipGetLastError();
+    });
 }
 
 } // namespace redio

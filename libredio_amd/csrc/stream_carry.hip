@@ -24,6 +24,7 @@
 //                  window begins at a multiple of H samples of the stream, so the index of a run's first row is its first sample's stream index / H
 //     oversampled synthesis bank  W = nchan*ceil(nchan*taps_per_branch/hop)  H = nchan  unit = 1 hop (hop samples of the one stream, from rows of nchan
 //                  channel values); the running row index is carried too: a run's first value is the first of a row, its stream index / nchan
+//     (the three banks' W, H and unit are the BankCut their create entries fill in pfb_bank.hip: window, hop, unit_out)
 // so one layer serves them all.  The handle keeps the stream's unconsumed tail (fewer than W samples) on the device.
 // A call with n new samples
 //   1. appends the first min(n, W-1) new samples to the tail in a plan-owned staging buffer (one small copy),

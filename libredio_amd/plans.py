@@ -2,6 +2,7 @@
 streams only).  Inputs/outputs are torch CUDA tensors; kernels are enqueued on torch's current
 stream, nothing synchronises."""
 import ctypes as C
+import threading
 
 import numpy as np
 
@@ -10,10 +11,27 @@ from . import REDIO_FIR_COMPLEX, REDIO_FIR_FUSED, REDIO_PFB_PSPEC_BLOCK, check, 
 _pf = C.POINTER(C.c_float)
 
 
-def _safe_destroy(fn, h):
-    """Plan destructors also run at interpreter shutdown, when module globals may already be gone."""
-    try:
+_tls = threading.local()  # capturing: how many Graph captures this thread has open
+_deferred = []             # (destroy function, handle) of plans finalised on a thread while it was capturing
+
+
+def _destroy_deferred():
+    while _deferred and not getattr(_tls, "capturing", 0):
+        fn, h = _deferred.pop()
         getattr(lib(), fn)(h)
+
+
+def _safe_destroy(fn, h):
+    """Plan destructors also run at interpreter shutdown, when module globals may already be gone.  And they run wherever the
+    collector finds a plan that sat in a reference cycle (a caught exception's traceback keeps its frame's locals): inside a Graph
+    capture on this thread the destroy would free device memory, which HIP refuses on a capturing thread and answers by invalidating
+    the capture -- so it waits for the capture's end."""
+    try:
+        if getattr(_tls, "capturing", 0):
+            _deferred.append((fn, h))
+            return
+        getattr(lib(), fn)(h)
+        _destroy_deferred()
     except Exception:
         pass
 
@@ -604,10 +622,15 @@ class Graph:
         self._ctx = torch.cuda.stream(self.stream)
         self._ctx.__enter__()
         check(lib().redio_graph_begin(C.c_void_p(self.stream.cuda_stream)), "graph_begin")
+        _tls.capturing = getattr(_tls, "capturing", 0) + 1  # _safe_destroy: plans finalised on this thread wait for the capture's end
         return self
 
     def __exit__(self, et, ev, tb):
-        rc = lib().redio_graph_end(C.c_void_p(self.stream.cuda_stream), C.byref(self._g))
+        try:
+            rc = lib().redio_graph_end(C.c_void_p(self.stream.cuda_stream), C.byref(self._g))
+        finally:
+            _tls.capturing -= 1
+        _destroy_deferred()
         self._ctx.__exit__(et, ev, tb)
         self._ctx = None
         if et is None:
@@ -1047,7 +1070,63 @@ class PolyphaseSpectrum:
             self._h = None
 
 
-class Synthesizer:
+class _TwoPassBankBase:
+    """what Synthesizer, OversampledChannelizer and OversampledSynthesizer share: a subclass gives its C symbols' prefix and what a
+    call reads and returns"""
+
+    TWO_PASS, WAVE = 0, 1
+    _prefix = None
+
+    def _fn(self, name):
+        return getattr(lib(), f"redio_{self._prefix}_{name}")
+
+    def _create(self, proto, nchan, taps_per_branch, fused, *hop):
+        t, p = _taps(proto)
+        assert len(t) == nchan * taps_per_branch
+        self.nchan, self.taps_per_branch = int(nchan), int(taps_per_branch)
+        self._h = C.c_void_p()
+        check(self._fn("create")(C.byref(self._h), p, self.nchan, self.taps_per_branch, *hop, REDIO_FIR_FUSED if fused else 0), f"{self._prefix}_create")
+
+    @property
+    def route(self):
+        """what a call runs: WAVE (the 64-channel kernel; the oversampled plans: at hop 32) or TWO_PASS"""
+        return self._fn("route")(self._h)
+
+    @property
+    def is_fused(self):
+        return bool(self._fn("is_fused")(self._h))
+
+    def set_unfused(self, unfused=True):
+        """send a WAVE plan down the two-pass route (tests and measurement): the same bits"""
+        check(self._fn("set_unfused")(self._h, int(bool(unfused))), f"{self._prefix}_set_unfused")
+
+    def set_chunk_rows(self, rows):
+        """rows per pass of the two-pass route (Synthesizer, OversampledSynthesizer: input rows; OversampledChannelizer: rows) (0: the
+        64 MiB default); for tests of the chunk seam: the same bits"""
+        check(self._fn("set_chunk_rows")(self._h, int(rows)), f"{self._prefix}_set_chunk_rows")
+
+    def reserve(self, n_in):
+        """the two-pass route's scratch for calls of up to n_in samples (OversampledChannelizer) or values (Synthesizer,
+        OversampledSynthesizer), so that a call never allocates, e.g. inside a Graph"""
+        check(self._fn("reserve")(self._h, int(n_in)), f"{self._prefix}_reserve")
+
+    def _run(self, x, n, out, *first_row):
+        """enqueue on x into out (allocated here if None) of at least n complex64; returns out"""
+        import torch
+        assert x.dtype == torch.complex64
+        if out is None:
+            out = torch.empty(n, dtype=torch.complex64, device=x.device)
+        assert out.dtype == torch.complex64 and out.numel() >= n
+        check(self._fn("enqueue")(self._h, _dev_ptr(x), x.numel(), *first_row, _dev_ptr(out), current_stream()), f"{self._prefix}_enqueue")
+        return out
+
+    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
+        if getattr(self, "_h", None):
+            _safe_destroy(f"redio_{self._prefix}_destroy", self._h)
+            self._h = None
+
+
+class Synthesizer(_TwoPassBankBase):
     """redio_pfb_synth_*: the synthesis filterbank, many narrow channels into one wideband stream (contract: DESIGN.md 5.6c).  The
     Channelizer is "branch filter, then forward transform"; this is "inverse transform, then the same branch filter": rows of nchan
     complex64 channel values in (the Channelizer's ngroups = 1 layout), kissfft's unnormalised inverse transform per row, then per
@@ -1055,53 +1134,17 @@ class Synthesizer:
     one stream out.  No 1 / nchan.  64 channels with 4 / 8 / 16 taps per branch are one kernel (route WAVE, is_fused); every other plan
     runs its own inverse transform into scratch and the branch pass (route TWO_PASS): the same bits."""
 
-    TWO_PASS, WAVE = 0, 1
+    _prefix = "pfb_synth"
 
     def __init__(self, proto, nchan=64, taps_per_branch=16, fused=True):
-        t, p = _taps(proto)
-        assert len(t) == nchan * taps_per_branch
-        self.nchan, self.taps_per_branch = int(nchan), int(taps_per_branch)
-        self._h = C.c_void_p()
-        check(lib().redio_pfb_synth_create(C.byref(self._h), p, self.nchan, self.taps_per_branch, REDIO_FIR_FUSED if fused else 0), "pfb_synth_create")
+        self._create(proto, nchan, taps_per_branch, fused)
 
     def nout(self, n_in):
-        return lib().redio_pfb_synth_nout(self._h, int(n_in))
-
-    @property
-    def route(self):
-        """what a call runs: WAVE (the 64-channel kernel) or TWO_PASS"""
-        return lib().redio_pfb_synth_route(self._h)
-
-    @property
-    def is_fused(self):
-        return bool(lib().redio_pfb_synth_is_fused(self._h))
-
-    def set_unfused(self, unfused=True):
-        """send a WAVE plan down the two-pass route (tests and measurement): the same bits"""
-        check(lib().redio_pfb_synth_set_unfused(self._h, int(bool(unfused))), "pfb_synth_set_unfused")
-
-    def set_chunk_rows(self, rows):
-        """input rows per pass of the two-pass route (0: the 64 MiB default); for tests of the chunk seam: the same bits"""
-        check(lib().redio_pfb_synth_set_chunk_rows(self._h, int(rows)), "pfb_synth_set_chunk_rows")
-
-    def reserve(self, n_in):
-        """the two-pass route's scratch for calls of up to n_in values, so that a call never allocates, e.g. inside a Graph"""
-        check(lib().redio_pfb_synth_reserve(self._h, int(n_in)), "pfb_synth_reserve")
+        return self._fn("nout")(self._h, int(n_in))
 
     def __call__(self, rows, out=None):
-        import torch
-        assert rows.dtype == torch.complex64
         n = self.nout(rows.numel())
-        if out is None:
-            out = torch.empty(n, dtype=torch.complex64, device=rows.device)
-        assert out.dtype == torch.complex64 and out.numel() >= n
-        check(lib().redio_pfb_synth_enqueue(self._h, _dev_ptr(rows), rows.numel(), _dev_ptr(out), current_stream()), "pfb_synth_enqueue")
-        return out[:n]
-
-    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
-        if getattr(self, "_h", None):
-            _safe_destroy("redio_pfb_synth_destroy", self._h)
-            self._h = None
+        return self._run(rows, n, out)[:n]
 
 
 class SynthesizerStream(Stream):
@@ -1113,7 +1156,7 @@ class SynthesizerStream(Stream):
         super().__init__(plan)
 
 
-class OversampledChannelizer:
+class OversampledChannelizer(_TwoPassBankBase):
     """redio_pfb_os_*: the oversampled (weighted overlap-add) channelizer, a row of nchan channels every hop <= nchan samples (contract:
     DESIGN.md 5.6d).  The Channelizer's branch filter on the nchan * taps_per_branch samples from r * hop on, the branch sums turned by
     ((first_row + r) * hop) mod nchan places (so that channel k of every row is referred to absolute time), then the forward transform:
@@ -1121,57 +1164,21 @@ class OversampledChannelizer:
     at hop 32 with 4 / 8 / 16 taps per branch are one kernel (route WAVE, is_fused); every other plan runs a branch pass into scratch and
     its own forward transform (route TWO_PASS): the same bits."""
 
-    TWO_PASS, WAVE = 0, 1
+    _prefix = "pfb_os"
 
     def __init__(self, proto, nchan=64, taps_per_branch=16, hop=32, fused=True):
-        t, p = _taps(proto)
-        assert len(t) == nchan * taps_per_branch
-        self.nchan, self.taps_per_branch = int(nchan), int(taps_per_branch)
-        self._h = C.c_void_p()
-        check(lib().redio_pfb_os_create(C.byref(self._h), p, self.nchan, self.taps_per_branch, int(hop), REDIO_FIR_FUSED if fused else 0), "pfb_os_create")
-
-    def nrows(self, n_in):
-        return lib().redio_pfb_os_nrows(self._h, int(n_in))
+        self._create(proto, nchan, taps_per_branch, fused, int(hop))
 
     @property
     def hop(self):
-        return lib().redio_pfb_os_hop(self._h)
+        return self._fn("hop")(self._h)
 
-    @property
-    def route(self):
-        """what a call runs: WAVE (the 64-channel kernel at hop 32) or TWO_PASS"""
-        return lib().redio_pfb_os_route(self._h)
-
-    @property
-    def is_fused(self):
-        return bool(lib().redio_pfb_os_is_fused(self._h))
-
-    def set_unfused(self, unfused=True):
-        """send a WAVE plan down the two-pass route (tests and measurement): the same bits"""
-        check(lib().redio_pfb_os_set_unfused(self._h, int(bool(unfused))), "pfb_os_set_unfused")
-
-    def set_chunk_rows(self, rows):
-        """rows per pass of the two-pass route (0: the 64 MiB default); for tests of the chunk seam: the same bits"""
-        check(lib().redio_pfb_os_set_chunk_rows(self._h, int(rows)), "pfb_os_set_chunk_rows")
-
-    def reserve(self, n_in):
-        """the two-pass route's scratch for calls of up to n_in samples, so that a call never allocates, e.g. inside a Graph"""
-        check(lib().redio_pfb_os_reserve(self._h, int(n_in)), "pfb_os_reserve")
+    def nrows(self, n_in):
+        return self._fn("nrows")(self._h, int(n_in))
 
     def __call__(self, x, first_row=0, out=None):
-        import torch
-        assert x.dtype == torch.complex64
         rows = self.nrows(x.numel())
-        if out is None:
-            out = torch.empty(rows * self.nchan, dtype=torch.complex64, device=x.device)
-        assert out.dtype == torch.complex64 and out.numel() >= rows * self.nchan
-        check(lib().redio_pfb_os_enqueue(self._h, _dev_ptr(x), x.numel(), int(first_row), _dev_ptr(out), current_stream()), "pfb_os_enqueue")
-        return out.reshape(-1)[: rows * self.nchan].reshape(rows, self.nchan)
-
-    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
-        if getattr(self, "_h", None):
-            _safe_destroy("redio_pfb_os_destroy", self._h)
-            self._h = None
+        return self._run(x, rows * self.nchan, out, int(first_row)).reshape(-1)[: rows * self.nchan].reshape(rows, self.nchan)
 
 
 class OversampledChannelizerStream(Stream):
@@ -1184,7 +1191,7 @@ class OversampledChannelizerStream(Stream):
         super().__init__(plan)
 
 
-class OversampledSynthesizer:
+class OversampledSynthesizer(_TwoPassBankBase):
     """redio_pfb_os_synth_*: the oversampled synthesis bank, the OversampledChannelizer's rows back into one stream (contract: DESIGN.md
     5.6e).  kissfft's unnormalised inverse transform of every row of nchan channel values, then a weighted overlap-add at hop <= nchan:
     with L = ceil(nchan * taps_per_branch / hop), T rows in give (T - L + 1) * hop complex64 samples, sample n at absolute time
@@ -1192,57 +1199,21 @@ class OversampledSynthesizer:
     one kernel (route WAVE, is_fused); every other plan runs its own inverse transform into scratch and an overlap-add pass (route
     TWO_PASS): the same bits."""
 
-    TWO_PASS, WAVE = 0, 1
+    _prefix = "pfb_os_synth"
 
     def __init__(self, proto, nchan=64, taps_per_branch=16, hop=32, fused=True):
-        t, p = _taps(proto)
-        assert len(t) == nchan * taps_per_branch
-        self.nchan, self.taps_per_branch = int(nchan), int(taps_per_branch)
-        self._h = C.c_void_p()
-        check(lib().redio_pfb_os_synth_create(C.byref(self._h), p, self.nchan, self.taps_per_branch, int(hop), REDIO_FIR_FUSED if fused else 0), "pfb_os_synth_create")
-
-    def nout(self, n_in):
-        return lib().redio_pfb_os_synth_nout(self._h, int(n_in))
+        self._create(proto, nchan, taps_per_branch, fused, int(hop))
 
     @property
     def hop(self):
-        return lib().redio_pfb_os_synth_hop(self._h)
+        return self._fn("hop")(self._h)
 
-    @property
-    def route(self):
-        """what a call runs: WAVE (the 64-channel kernel at hop 32) or TWO_PASS"""
-        return lib().redio_pfb_os_synth_route(self._h)
-
-    @property
-    def is_fused(self):
-        return bool(lib().redio_pfb_os_synth_is_fused(self._h))
-
-    def set_unfused(self, unfused=True):
-        """send a WAVE plan down the two-pass route (tests and measurement): the same bits"""
-        check(lib().redio_pfb_os_synth_set_unfused(self._h, int(bool(unfused))), "pfb_os_synth_set_unfused")
-
-    def set_chunk_rows(self, rows):
-        """input rows per pass of the two-pass route (0: the 64 MiB default); for tests of the chunk seam: the same bits"""
-        check(lib().redio_pfb_os_synth_set_chunk_rows(self._h, int(rows)), "pfb_os_synth_set_chunk_rows")
-
-    def reserve(self, n_in):
-        """the two-pass route's scratch for calls of up to n_in values, so that a call never allocates, e.g. inside a Graph"""
-        check(lib().redio_pfb_os_synth_reserve(self._h, int(n_in)), "pfb_os_synth_reserve")
+    def nout(self, n_in):
+        return self._fn("nout")(self._h, int(n_in))
 
     def __call__(self, x, first_row=0, out=None):
-        import torch
-        assert x.dtype == torch.complex64
         n = self.nout(x.numel())
-        if out is None:
-            out = torch.empty(n, dtype=torch.complex64, device=x.device)
-        assert out.dtype == torch.complex64 and out.numel() >= n
-        check(lib().redio_pfb_os_synth_enqueue(self._h, _dev_ptr(x), x.numel(), int(first_row), _dev_ptr(out), current_stream()), "pfb_os_synth_enqueue")
-        return out.reshape(-1)[:n]
-
-    def __del__(self, _safe_destroy=_safe_destroy):  # bound at definition: module globals may be gone at shutdown
-        if getattr(self, "_h", None):
-            _safe_destroy("redio_pfb_os_synth_destroy", self._h)
-            self._h = None
+        return self._run(x, n, out, int(first_row)).reshape(-1)[:n]
 
 
 class OversampledSynthesizerStream(Stream):

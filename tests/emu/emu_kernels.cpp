@@ -429,6 +429,30 @@ extern "C" void emu_stream_split(size_t hist, size_t W, size_t H, size_t n, size
     out5[0] = s.nh; out5[1] = s.head_in; out5[2] = s.nb; out5[3] = s.off; out5[4] = s.body_in;
 }
 
+// the chunk cut of the two-pass filterbank plans (libredio_amd/csrc/pfb_bank_cut.h).  cut5: window, hop, unit_out, min_rows, row; asked:
+// what set_chunk_rows was given.  out3: the plan's chunk_rows, the rows reserve sizes the scratch for, the pass count
+#include "../../libredio_amd/csrc/pfb_bank_cut.h"
+static redio::BankCut emu_cut(const size_t *c) { return redio::BankCut{c[0], c[1], c[2], c[3], c[4]}; }
+extern "C" void emu_bank_cut_of(int family, size_t M, size_t P, size_t H, size_t *cut5) // 0: synthesis, 1: oversampled channelizer, 2: oversampled synthesis
+{
+    const redio::BankCut c = family == 0 ? redio::bank_cut_synth(M, P, H) : family == 1 ? redio::bank_cut_os(M, P, H) : redio::bank_cut_os_synth(M, P, H);
+    cut5[0] = c.window; cut5[1] = c.hop; cut5[2] = c.unit_out; cut5[3] = c.min_rows; cut5[4] = c.row;
+}
+extern "C" size_t emu_bank_units(const size_t *cut5, size_t n_in) { return redio::bank_units(emu_cut(cut5), n_in); }
+extern "C" void emu_bank_cut(const size_t *cut5, size_t asked, size_t units, size_t *out3)
+{
+    const redio::BankCut c = emu_cut(cut5);
+    out3[0] = redio::bank_chunk_rows(c, asked);
+    out3[1] = redio::bank_pass_rows(c, out3[0], units);
+    out3[2] = redio::bank_passes(c, out3[0], units);
+}
+extern "C" void emu_bank_pass(const size_t *cut5, size_t asked, size_t units, size_t i, size_t *out5)
+{
+    const redio::BankCut c = emu_cut(cut5);
+    const redio::BankPass p = redio::bank_pass(c, redio::bank_chunk_rows(c, asked), units, i);
+    out5[0] = p.first; out5[1] = p.units; out5[2] = p.in_off; out5[3] = p.rows; out5[4] = p.out_off;
+}
+
 // the resampler's position recurrence: short form (libredio_amd/csrc/src_position.h) against the library's literal expression
 #include "../../libredio_amd/csrc/src_position.h"
 extern "C" long emu_src_advance_mismatches(const double *x, const double *step, long n, long chain)

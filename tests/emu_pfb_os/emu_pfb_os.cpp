@@ -9,12 +9,13 @@
 // in.bin: 32 (rows - 1) + 64 P cf32; want.bin: rows * 64 cf32 (the rows of tests/pfb_os_ref.py).  Prints the wave count.
 //
 //   emu_pfb_os branch M P H fused rows first_row chunk in.bin taps.bin want.bin
-// The two-pass route's branch pass (pfb_os_api.hip, pfb_os_branch_kernel) in passes of `chunk` rows as redio_pfb_os_enqueue cuts them:
+// The two-pass route's branch pass (pfb_os_kernels.hip, pfb_os_branch_kernel) in passes of `chunk` rows as redio_pfb_os_enqueue cuts them (pfb_bank_cut.h):
 // every thread of every launch, its loads, the shift and the rotated store.  in.bin: H (rows - 1) + M P cf32; want.bin: rows * M cf32,
 // the rotated branch sums in front of the transform.  Prints the pass count.
 //
 // Every stream load is fenced inside [0, n_in), every LDS index inside the wave's tile, every store inside rows * M, and every output
 // must be written exactly once.  Exit status 0 only if every check held and the output has want.bin's bits.
+#include "../../libredio_amd/csrc/pfb_bank_cut.h"
 #include "../../libredio_amd/csrc/pfb_os_core.h"
 #include <cmath>
 #include <cstdio>
@@ -146,11 +147,15 @@ template <bool FUSED>
 long run_branch(const std::vector<float2> &x, const std::vector<float> &h, Out &out, long rows, int M, int P, long H, unsigned long long F, long chunk)
 {
     const long n_in = (long)x.size();
-    long passes = 0;
-    for (long c0 = 0; c0 < rows; c0 += chunk, ++passes) {
-        const long n = rows - c0 < chunk ? rows - c0 : chunk;
+    const BankCut cut = bank_cut_os((size_t)M, (size_t)P, (size_t)H);
+    const size_t chunk_rows = bank_chunk_rows(cut, (size_t)chunk);
+    const long passes = (long)bank_passes(cut, chunk_rows, (size_t)rows);
+    for (long i = 0; i < passes; ++i) {
+        const BankPass ps = bank_pass(cut, chunk_rows, (size_t)rows, (size_t)i);
+        const long c0 = (long)ps.first, n = (long)ps.units;
+        CHECK(ps.rows <= bank_pass_rows(cut, chunk_rows, (size_t)rows)); // inside the scratch that reserve sized
         const long f0 = (long)((F + (unsigned long long)c0) % (unsigned long long)M);
-        const long xo = c0 * H, vo = c0 * M; // the pass's pointers: d_in + c0 H; the scratch rows land at out + c0 M behind the transform
+        const long xo = (long)ps.in_off, vo = (long)ps.out_off; // the pass's pointers: d_in + c0 H; the scratch rows land at out + c0 M behind the transform
         const long nthreads = ((n * M + 255) / 256) * 256;
         for (long e = 0; e < nthreads; ++e) {
             if (e >= n * M) continue;
@@ -166,7 +171,7 @@ long run_branch(const std::vector<float2> &x, const std::vector<float> &h, Out &
             const long s = pfbos_shift(f0, r, M, H), k = pfbos_rot(m, s, M);
             CHECK(s >= 0 && s < M && k >= 0 && k < M);
             CHECK((unsigned long long)s == ((F + (unsigned long long)(c0 + r)) % (unsigned long long)M) * (unsigned long long)H % (unsigned long long)M);
-            CHECK(r * M + k < n * M); // inside the pass's scratch
+            CHECK(r * M + k < (long)ps.rows * M); // inside the pass's scratch
             out.store(vo + r * M + k, acc);
         }
     }

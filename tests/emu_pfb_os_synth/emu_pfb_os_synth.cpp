@@ -11,12 +11,13 @@
 //
 //   emu_pfb_os_synth ola M P H fused hops first_row chunk w.bin taps.bin want.bin
 // The two-pass route's overlap-add pass (pfb_os_synth_ola_kernel) in passes of `chunk` input rows as redio_pfb_os_synth_enqueue cuts
-// them: every thread of every launch, its column, its taps and its store.  w.bin: (hops + L - 1) * M cf32, the rows BEHIND the inverse
+// them (pfb_bank_cut.h): every thread of every launch, its column, its taps and its store.  w.bin: (hops + L - 1) * M cf32, the rows BEHIND the inverse
 // transform; want.bin: hops * H cf32.  Prints the pass count.
 //
 // Every load is fenced inside its buffer (a pass's scratch holds the pass's rows only), every LDS index inside the wave's tile, every
 // store inside the output, and every output must be written exactly once.  Exit status 0 only if every check held and the output has
 // want.bin's bits.
+#include "../../libredio_amd/csrc/pfb_bank_cut.h"
 #include "../../libredio_amd/csrc/pfb_os_synth_core.h"
 #include <cmath>
 #include <cstdio>
@@ -162,14 +163,16 @@ long run_ola(const std::vector<float2> &w, const std::vector<float> &h, Out &out
     const long L = pfboss_L(M, P, H);
     const long T = hops + L - 1;
     CHECK((long)w.size() == T * M);
-    long pass = chunk < L ? L : chunk; // redio_pfb_os_synth_set_chunk_rows: fewer than L rows count as L
-    if (pass > T) pass = T;
-    const long per = pass - L + 1;
-    long passes = 0;
-    for (long c0 = 0; c0 < hops; c0 += per, ++passes) {
-        const long n = hops - c0 < per ? hops - c0 : per;
+    const BankCut cut = bank_cut_os_synth((size_t)M, (size_t)P, (size_t)H);
+    CHECK(cut.min_rows == (size_t)L);
+    const size_t chunk_rows = bank_chunk_rows(cut, (size_t)chunk); // fewer than L rows count as L
+    const long passes = (long)bank_passes(cut, chunk_rows, (size_t)hops);
+    for (long i = 0; i < passes; ++i) {
+        const BankPass ps = bank_pass(cut, chunk_rows, (size_t)hops, (size_t)i);
+        const long c0 = (long)ps.first, n = (long)ps.units;
+        CHECK(ps.rows <= bank_pass_rows(cut, chunk_rows, (size_t)hops)); // inside the scratch that reserve sized
         const long f0 = (long)((F + (unsigned long long)c0) % (unsigned long long)M);
-        const long wo = c0 * M, wn = (n + L - 1) * M; // the pass's scratch: rows c0 .. c0 + n + L - 2 behind the transform
+        const long wo = (long)ps.in_off, wn = (long)ps.rows * M; // the pass's scratch: rows c0 .. c0 + n + L - 2 behind the transform
         CHECK(wo + wn <= (long)w.size());
         const long nout = n * H, nthreads = ((nout + 255) / 256) * 256;
         for (long e = 0; e < nthreads; ++e) {
@@ -188,7 +191,7 @@ long run_ola(const std::vector<float2> &w, const std::vector<float> &h, Out &out
                 acc = mac<FUSED>(w[(size_t)(wo + i)], h[(size_t)t], acc);
             }
             if (pfboss_k0(j, M, P, H, L)) CHECK(pfboss_offset(0, j, H, L) >= P * M); // the row left out is outside its window
-            out.store(c0 * H + e, acc);
+            out.store((long)ps.out_off + e, acc);
         }
     }
     return passes;

@@ -65,3 +65,31 @@ def test_two_pass_needs_the_reserve_and_then_captures(gpu, redio, oracle, M, P, 
         assert np.array_equal(bits(out.cpu().numpy()), bits(want))
     assert np.array_equal(bits(plan(d, out=out).cpu().numpy()), bits(want))  # and un-captured, on the same scratch
     assert redio.lib().redio_malloc_count() == count  # reserved: no enqueue allocated
+
+
+def test_a_plan_finalised_inside_a_capture_waits_for_its_end(gpu, redio, oracle):
+    """A plan left in a reference cycle (what `pytest.raises(...) as e` does to a test's locals) is finalised wherever the collector
+    next runs.  Inside a Graph capture on the same thread its destroy, which frees device memory, would invalidate the capture: it
+    waits for the capture's end, the capture replays, and the plan is destroyed then."""
+    import gc
+    from libredio_amd import plans
+    h, d, want, out = make(gpu, oracle, 64, 4, 40)
+    plan = redio.Synthesizer(h, 64, 4)
+    gc.collect()
+    gc.disable()  # the collector runs where this test says
+    try:
+        dead = redio.Synthesizer(oracle.synth_f32(9, 0, 36), 12, 3)
+        dead.reserve(12 * 20)  # route 0: it owns scratch
+        dead.me = dead
+        del dead
+        g = redio.Graph()
+        with g:
+            assert gc.collect() >= 1 and len(plans._deferred) == 1
+            plan(d, out=out)
+        assert plans._deferred == []
+    finally:
+        gc.enable()
+    out.zero_()
+    g.launch()
+    gpu.cuda.synchronize()
+    assert np.array_equal(bits(out.cpu().numpy()), bits(want))
