@@ -5,6 +5,8 @@ Every kernel here was written with 64-bit unit indices and 32-bit offsets inside
  and pushed through each operator; the oracle recomputes, from nothing but its own input window, the outputs next to every
 boundary that matters: the start, byte offset 2^32 (sample 2^29), element 2^31, element 2^32, the end.  Bit-exact, as everywhere.
 The real-input and spectrum plans read narrower views of the same memory as f32 samples and as u8 I/Q bytes (second half of this file).
+The three two-pass filterbank plans (synthesis bank, oversampled channelizer, oversampled synthesis bank) read it as samples or as rows
+of channel values, on the wave route and down route 0 through hundreds of default passes (last part of this file).
 Skipped when the device has less than 120 GB free."""
 import numpy as np
 import pytest
@@ -356,3 +358,100 @@ def test_ovsave_real_past_2_32(gpu, redio, oracle, big, nfft, ntaps):
         want = ovsave_real_ref.overlap_save_real(host_f32(oracle, b0 * hop, (b1 - b0) * hop + nfft), h, nfft)
         assert same_bits(out[o0:o0 + 1400].cpu().numpy(), want[o0 - b0 * hop: o0 - b0 * hop + 1400]), (nfft, p)
     del out
+
+
+# ---- the polyphase banks --------------------------------------------------------------------------------------------------------------------
+# The synthesis bank, the oversampled channelizer and the oversampled synthesis bank (one driver, pfb_bank.hip) on the stream, read as
+# samples or as rows of channel values.  A unit is an output row, a row, or a hop: unit u reads `window` input elements from u * hop_in
+# on and gives unit_out output elements.  Every check recomputes a few units next to a mark from their own window of the hash with
+# first_row + the window's first unit, so that the window's reference is the call's.  The wave-route shapes run twice, the second time
+# down route 0 with the chunk left alone: hundreds of default passes, input and output offsets above 2^32 elements, and there the units
+# either side of the pass seams next to every mark are compared as well.
+BANK_FIRST = 5   # first_row of every call: odd, so that the hop-32 plans turn their rows by 32 places from the start
+
+
+def bank_geometry(kind, M, P, H):
+    """(window, hop_in, unit_out, min_rows): pfb_bank_cut.h's table"""
+    L = -(-M * P // H)
+    return {"synth": (M * P, M, M, P), "os": (M * P, H, M, 1), "os_synth": (M * L, M, H, L)}[kind]
+
+
+def bank_want(oracle, kind, h, M, P, H, lo, cnt):
+    import pfb_os_ref
+    import pfb_os_synth_ref
+    import pfb_synth_ref
+    window, hop_in, _, _ = bank_geometry(kind, M, P, H)
+    x = oracle.synth_iq(SEED, lo * hop_in, (cnt - 1) * hop_in + window)
+    if kind == "synth":
+        return pfb_synth_ref.synth(x, h, M, P, True)
+    if kind == "os":
+        return pfb_os_ref.channelize(x, h, M, P, H, BANK_FIRST + lo, True).reshape(-1)
+    return pfb_os_synth_ref.synth(x, h, M, P, H, BANK_FIRST + lo, True)
+
+
+def check_bank(oracle, out, kind, h, M, P, H, units, at):
+    _, _, unit_out, _ = bank_geometry(kind, M, P, H)
+    for b in sorted({q for q in at if 0 <= q < units}):
+        lo = max(0, min(b - 2, units - 5))
+        cnt = min(5, units - lo)
+        want = bank_want(oracle, kind, h, M, P, H, lo, cnt)
+        assert same_bits(out[lo * unit_out:(lo + cnt) * unit_out].cpu().numpy(), want), (kind, M, P, H, b)
+
+
+def run_bank_past_2_32(gpu, redio, oracle, big, kind, M, P, H, n_in, routes):
+    """the call on the first n_in elements of the stream on every route of `routes`; returns (units, output elements)"""
+    window, hop_in, unit_out, min_rows = bank_geometry(kind, M, P, H)
+    h = oracle.lpf_corrected(M * P, 0.45 / M)
+    plan = {"synth": lambda: redio.Synthesizer(h, M, P), "os": lambda: redio.OversampledChannelizer(h, M, P, H),
+            "os_synth": lambda: redio.OversampledSynthesizer(h, M, P, H)}[kind]()
+    units = (n_in - window) // hop_in + 1
+    assert (plan.nrows(n_in) if kind == "os" else plan.nout(n_in) // unit_out) == units
+    x = big[:n_in]
+    at = set(marks(units, unit_out)) | set(marks(units, hop_in))   # next to the boundaries of the output and of the input
+    for route in routes:
+        plan.set_unfused(route == 0)
+        assert plan.route == route
+        seams = set()
+        if route == 0:
+            per = (64 << 20) // (M * 8) - min_rows + 1                # units per default pass (pfb_bank_cut.h)
+            assert units > 100 * per or M != 64
+            seams = {q for b in at for q in (b // per * per, (b // per + 1) * per)}
+        out = (plan(x) if kind == "synth" else plan(x, first_row=BANK_FIRST)).reshape(-1)
+        assert out.numel() == units * unit_out
+        check_bank(oracle, out, kind, h, M, P, H, units, at | seams)
+        del out
+    return units, units * unit_out
+
+
+def test_pfb_synth_past_2_32(gpu, redio, oracle, big):
+    """redio_pfb_synth_enqueue on the whole stream as 2^26 rows of 64 channel values: more than 2^32 samples out"""
+    units, nout = run_bank_past_2_32(gpu, redio, oracle, big, "synth", 64, 16, 64, N, (1, 0))
+    assert nout > 1 << 32
+
+
+def test_pfb_os_past_2_32(gpu, redio, oracle, big):
+    """redio_pfb_os_enqueue at hop 32 on the first 2^31 + 2^20 samples: more than 2^26 rows, so more than 2^32 elements out"""
+    units, nout = run_bank_past_2_32(gpu, redio, oracle, big, "os", 64, 16, 32, (1 << 31) + (1 << 20), (1, 0))
+    assert units > 1 << 26 and nout > 1 << 32
+
+
+def test_pfb_os_synth_past_2_32(gpu, redio, oracle, big):
+    """redio_pfb_os_synth_enqueue at hop 32 on the whole stream as rows: more than 2^32 elements in, more than 2^31 elements (and byte
+    2^32) out"""
+    units, nout = run_bank_past_2_32(gpu, redio, oracle, big, "os_synth", 64, 16, 32, N, (1, 0))
+    assert units * 64 > 1 << 32 and nout > 1 << 31
+
+
+def test_pfb_os_two_pass_shape_past_2_32(gpu, redio, oracle, big):
+    """a shape with no wave kernel, (100, 3, 60): 2^32 / 100 rows and a thousand more, so the output passes 2^32 elements; 512 default
+    passes of 83886 rows, where 64 MiB is no whole number of rows"""
+    rows = (1 << 32) // 100 + 1000
+    units, nout = run_bank_past_2_32(gpu, redio, oracle, big, "os", 100, 3, 60, 300 + (rows - 1) * 60 + 7, (0,))
+    assert units == rows and nout > 1 << 32
+
+
+def test_pfb_os_synth_two_pass_shape_past_2_32(gpu, redio, oracle, big):
+    """(100, 3, 60), L = 5, on the whole stream as rows of 100: more than 2^32 elements in.  A hop gives 60 samples for 100 values, so
+    the stream's 2^32 elements give 0.6 * 2^32 out: past element 2^31 and byte 2^32, short of element 2^32"""
+    units, nout = run_bank_past_2_32(gpu, redio, oracle, big, "os_synth", 100, 3, 60, N, (0,))
+    assert units * 100 > 1 << 32 and nout > 1 << 31

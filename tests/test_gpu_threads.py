@@ -201,3 +201,88 @@ def test_concurrent_polyphase_spectrum_plans(gpu, redio, oracle):
         t.join(300)
     assert not any(t.is_alive() for t in threads), "a thread did not finish"
     assert not errors, errors
+
+
+def test_concurrent_polyphase_bank_plans(gpu, redio, oracle):
+    """redio_pfb_synth_*, redio_pfb_os_*, redio_pfb_os_synth_* (one driver, pfb_bank.hip): each family on the wave route, on a two-pass
+    shape with a small chunk (plan-owned scratch and the transform behind it) and as a stream fed in twelve pieces -- nine threads, each
+    with a plan of its own on a stream of its own, unit counts that rise and fall so that scratch regrows while the other threads are
+    inside the library; two of the threads create and drop a fresh plan every iteration, so that a destroy runs while the others
+    enqueue; every result bit for bit the restatement's"""
+    import pfb_os_ref
+    import pfb_os_synth_ref
+    import pfb_synth_ref
+    errors = []
+    rows_of = [1, 3, 2, 5, 1, 4, 6, 2, 7, 3, 1, 8]   # per iteration: up and down, the largest last
+    FIRST = 3
+
+    def same(got, want):
+        return got.shape == want.shape and np.array_equal(np.ascontiguousarray(got).view(np.uint32), np.ascontiguousarray(want).view(np.uint32))
+
+    def geometry(fam, M, P, H):
+        """(window, hop, unit_out, min_rows) in elements: pfb_bank_cut.h's table"""
+        L = -(-M * P // H)
+        return {"synth": (M * P, M, M, P), "os": (M * P, H, M, 1), "os_synth": (M * L, M, H, L)}[fam]
+
+    def make(fam, h, M, P, H):
+        if fam == "synth":
+            return redio.Synthesizer(h, M, P)
+        return (redio.OversampledChannelizer if fam == "os" else redio.OversampledSynthesizer)(h, M, P, H)
+
+    def want_of(fam, x, h, M, P, H, F):
+        if fam == "synth":
+            return pfb_synth_ref.synth(x, h, M, P, True)
+        if fam == "os":
+            return pfb_os_ref.channelize(x, h, M, P, H, F, True).reshape(-1)
+        return pfb_os_synth_ref.synth(x, h, M, P, H, F, True)
+
+    def worker(how, fam, fresh, seed):
+        try:
+            s = gpu.cuda.Stream()
+            with gpu.cuda.stream(s):
+                M, P, H = (64, 4, 32) if how != "two_pass" else (100, 3, 60)
+                H = M if fam == "synth" else H
+                window, hop, unit_out, min_rows = geometry(fam, M, P, H)
+                h = oracle.synth_f32(seed, 0, M * P)
+                plan = make(fam, h, M, P, H)
+                assert plan.route == (0 if how == "two_pass" else 1)
+                if how == "stream":   # one stream in twelve pieces against the one-shot output of the whole, first_row = 0
+                    lens = [(window - hop if it == 0 else 0) + rows * hop + 7 * it for it, rows in enumerate(rows_of)]
+                    x = oracle.synth_iq(seed, 0, sum(lens))
+                    whole = want_of(fam, x, h, M, P, H, 0)
+                    d = gpu.from_numpy(x).cuda()
+                    st = {"synth": redio.SynthesizerStream, "os": redio.OversampledChannelizerStream, "os_synth": redio.OversampledSynthesizerStream}[fam](plan)
+                    pos = made = 0
+                    for it, n in enumerate(lens):
+                        got = st(d[pos: pos + n]).cpu().numpy()
+                        pos += n
+                        now = (pos - window) // hop + 1 if pos >= window else 0
+                        if not (same(got, whole[made * unit_out: now * unit_out]) and st.pending == pos - now * hop):
+                            errors.append((how, fam, it))
+                        made = now
+                    assert made * unit_out == len(whole) and made >= sum(rows_of)
+                    return
+                for it, rows in enumerate(rows_of):
+                    if fresh and it:
+                        plan = make(fam, h, M, P, H)   # the one before is dropped here: its destroy runs beside the other threads' calls
+                    units = rows * 20 + it if how == "wave" else rows * 3   # wave: up to three wavefronts, odd and even counts
+                    if how == "two_pass":
+                        plan.set_chunk_rows(min_rows + 2)                   # passes of three units
+                    x = oracle.synth_iq(seed + it, 0, (units - 1) * hop + window + 7 * it % hop)
+                    d = gpu.from_numpy(x).cuda()
+                    got = (plan(d) if fam == "synth" else plan(d, first_row=FIRST + it)).reshape(-1).cpu().numpy()
+                    want = want_of(fam, x, h, M, P, H, FIRST + it)
+                    if not (len(want) == units * unit_out and same(got, want)):
+                        errors.append((how, fam, it))
+        except Exception as e:  # noqa: BLE001
+            errors.append((how, fam, repr(e)))
+
+    jobs = [(how, fam, (how, fam) in (("wave", "synth"), ("two_pass", "os"))) for how in ("wave", "two_pass", "stream") for fam in ("synth", "os", "os_synth")]
+    threads = [threading.Thread(target=worker, args=(how, fam, fresh, 1000 * (i + 1)), daemon=True) for i, (how, fam, fresh) in enumerate(jobs)]
+    assert len(threads) == 9
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(300)
+    assert not any(t.is_alive() for t in threads), "a thread did not finish"   # reported, not waited on
+    assert not errors, errors
