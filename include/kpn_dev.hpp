@@ -980,13 +980,13 @@ inline void synthesizer_stream(Receiver<View<std::complex<float>>> u, Sender<Vie
 
 // the oversampled channelizer (redio_pfb_os_*: a row of nchan channels every hop <= nchan samples, the branch sums turned by
 // ((F + r) hop) mod nchan places in front of the transform) as a block.  Per message: every message is a stream of
-// its own, its first row is row F = 0.
+// its own, its first row is row F = 0.  one_kernel: REDIO_PFB_OS_BLOCK, the workgroup kernel (route 2) where the shape has one.
 inline void oversampled_channelizer(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<float> proto, int nchan,
-                                    int taps_per_branch, size_t hop, bool fused)
+                                    int taps_per_branch, size_t hop, bool fused, bool one_kernel = false)
 {
     using cf = std::complex<float>;
     redio_pfb_os *h = nullptr;
-    check(redio_pfb_os_create(&h, proto.data(), nchan, taps_per_branch, hop, fused ? REDIO_FIR_FUSED : 0));
+    check(redio_pfb_os_create(&h, proto.data(), nchan, taps_per_branch, hop, (fused ? REDIO_FIR_FUSED : 0) | (one_kernel ? REDIO_PFB_OS_BLOCK : 0)));
     struct G { redio_pfb_os *h; ~G() { redio_pfb_os_destroy(h); } } g{h};
     detail::run_block<cf, cf>(u, v, [&](const View<cf> &d) { return redio_pfb_os_nrows(h, d.len) * (size_t)nchan; },
                               [&](const View<cf> &d, const View<cf> &o, void *st) { return redio_pfb_os_enqueue(h, d.data(), d.len, 0, o.data(), st); });
@@ -994,11 +994,11 @@ inline void oversampled_channelizer(Receiver<View<std::complex<float>>> u, Sende
 
 // ... and as a stream: messages of any length, the unconsumed samples and the running row index carried, whole rows sent
 inline void oversampled_channelizer_stream(Receiver<View<std::complex<float>>> u, Sender<View<std::complex<float>>> v, std::vector<float> proto, int nchan,
-                                           int taps_per_branch, size_t hop, bool fused)
+                                           int taps_per_branch, size_t hop, bool fused, bool one_kernel = false)
 {
     using cf = std::complex<float>;
     redio_pfb_os *h = nullptr;
-    check(redio_pfb_os_create(&h, proto.data(), nchan, taps_per_branch, hop, fused ? REDIO_FIR_FUSED : 0));
+    check(redio_pfb_os_create(&h, proto.data(), nchan, taps_per_branch, hop, (fused ? REDIO_FIR_FUSED : 0) | (one_kernel ? REDIO_PFB_OS_BLOCK : 0)));
     redio_pfb_os_stream *s = nullptr;
     const int rc = redio_pfb_os_stream_create(&s, h);
     struct G { redio_pfb_os *h; redio_pfb_os_stream *s; ~G() { redio_pfb_os_stream_destroy(s); redio_pfb_os_destroy(h); } } g{h, s};

@@ -621,26 +621,34 @@ int redio_pfb_synth_enqueue(redio_pfb_synth *h, const void *d_rows_c32, size_t n
  * W = e^(-2 pi i / M), so a call on a later part of a stream continues an earlier one when F is the index of its first row.  F + rows
  * must not pass 2^64.  At H = M the shift is 0 and the rows are redio_pfb_enqueue's (ngroups = 1), bit for bit.
  * create: NULL h / taps, nchan < 1, taps_per_branch < 1 (what redio_pfb_create refuses), hop == 0 or hop > nchan -> REDIO_ERR_ARG;
- *   a size redio_fft_create refuses -> its error.  flags: REDIO_FIR_FUSED or 0.
+ *   a size redio_fft_create refuses -> its error.  flags: REDIO_FIR_FUSED or 0, or-ed with REDIO_PFB_OS_BLOCK for route 2.
  * redio_pfb_os_route() says what a call on the plan runs (0 for NULL):
  *   1  nchan = 64, hop = 32 with taps_per_branch in {4, 8, 16} is ONE kernel, a wavefront per run of output rows (is_fused() == 1):
  *      8 bytes read and 16 written per input sample, no scratch; it captures without a reserve.
+ *   2  with REDIO_PFB_OS_BLOCK in flags: nchan in {32, 128, 256, 512, 1024}, hop = nchan / 2 with taps_per_branch in {4, 8, 16} is
+ *      ONE kernel, a workgroup per group of row streams (the one-kernel channelizer with a hop of half a row; is_fused() stays 0, as
+ *      on redio_pfb_pspec's route 2): the same bytes, no scratch; it captures without a reserve.  Any 8-byte aligned d_in and d_out:
+ *      the kernel takes 16-byte loads and stores where the pointers allow them and 8-byte ones otherwise, never route 0.  ONE
+ *      shape is left out: 1024 channels x 16 taps, whose two register windows only fit with spills to scratch;
+ *      it stays on route 0.  On every other shape the flag is accepted and changes nothing (64 channels at hop 32 stay route 1).
  *   0  every other plan runs a branch pass (row stride H, rotated store) into plan-owned scratch and its own forward redio_fft over
  *      those rows, in chunks of at most 64 MiB of whole rows.
- * set_unfused(h, 1) sends a route-1 plan down route 0 (tests and measurement, as redio_chain_set_unfused): the same bits.
+ * set_unfused(h, 1) sends a route-1 or route-2 plan down route 0 (tests and measurement, as redio_chain_set_unfused), set_unfused(h, 0)
+ *   brings it back: the same bits.
  * reserve(h, n_in) sizes route 0's scratch (the transform's staging included) for calls of up to n_in samples on the plan's CURRENT
  *   route, after which an enqueue neither allocates nor synchronises; un-reserved it grows on first use (REDIO_ERR_NOT_RESERVED
- *   while the stream is being captured).  On route 1 it does nothing.
+ *   while the stream is being captured).  On routes 1 and 2 it does nothing.
  * enqueue: launches only, on the caller's stream; every argument is checked before anything is launched.  NULL handle or buffers,
  *   overlapping buffers (d_in == d_out included), either pointer not 8-byte aligned -> REDIO_ERR_ARG; fewer than M P samples ->
  *   REDIO_OK, no launch.  Samples behind the last row's window are not read.
  * set_chunk_rows: rows per pass of route 0 (0 restores the 64 MiB default) -- for tests of the chunk seam; the same bits. */
+#define REDIO_PFB_OS_BLOCK 4u /* redio_pfb_os_create flags: the workgroup kernel (route 2) where the shape has one */
 typedef struct redio_pfb_os redio_pfb_os;
 int redio_pfb_os_create(redio_pfb_os **h, const float *proto_taps_host, int nchan, int taps_per_branch, size_t hop, unsigned flags);
 int redio_pfb_os_destroy(redio_pfb_os *h);
 size_t redio_pfb_os_nrows(const redio_pfb_os *h, size_t n_in); /* rows of nchan cf32 out for n_in cf32 samples in */
 size_t redio_pfb_os_hop(const redio_pfb_os *h);                /* 0 for NULL */
-int redio_pfb_os_route(const redio_pfb_os *h);                 /* 1 the 64-channel wave kernel, 0 two passes; 0 for NULL */
+int redio_pfb_os_route(const redio_pfb_os *h);                 /* 1 the 64-channel wave kernel, 2 the workgroup kernel, 0 two passes; 0 for NULL */
 int redio_pfb_os_is_fused(const redio_pfb_os *h);
 int redio_pfb_os_set_unfused(redio_pfb_os *h, int unfused);
 int redio_pfb_os_set_chunk_rows(redio_pfb_os *h, size_t rows);

@@ -21,6 +21,7 @@ LIBSAMPLERATE = os.path.join(_BUILD, "libsamplerate.so")
 REDIO_FIR_COMPLEX = 1
 REDIO_FIR_FUSED = 2
 REDIO_PFB_PSPEC_BLOCK = 4
+REDIO_PFB_OS_BLOCK = 4
 REDIO_DDC_MAX_PERIOD = 65536
 
 

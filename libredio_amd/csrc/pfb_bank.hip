@@ -6,9 +6,11 @@
 //     oversampled channelizer     branch filter at row stride H with a rotated store (pfb_os_kernels.hip), then forward transform
 //     oversampled synthesis bank  inverse transform, then the weighted overlap-add at hop H (pfb_os_synth_kernels.hip)
 // Route 1 (64 channels x 4 / 8 / 16 taps per branch; the oversampled plans at hop 32): the family's wave kernel, one launch, no scratch.
-// Route 0 (every other shape, and route-1 shapes after set_unfused): the two passes through plan-owned scratch, in chunks of at most
-// 64 MiB of rows cut by pfb_bank_cut.h; a chunk's first_row advances by the units before it.  The same bits on both routes.
-// What tells the families apart is data: BankFamily (direction and order of the transform, the two launchers) and the plan's BankCut
+// Route 2 (the oversampled channelizer with REDIO_PFB_OS_BLOCK: 32 ... 1024 channels at hop M / 2, pfb_os_p2.hip): the family's workgroup
+// kernel, one launch, no scratch.
+// Route 0 (every other shape, and route-1 and route-2 shapes after set_unfused): the two passes through plan-owned scratch, in chunks of
+// at most 64 MiB of rows cut by pfb_bank_cut.h; a chunk's first_row advances by the units before it.  The same bits on every route.
+// What tells the families apart is data: BankFamily (direction and order of the transform, the launchers) and the plan's BankCut
 // (window, hop, output per unit, rows a pass needs at least).  The driver never asks which family it serves.  Each family's own code is
 // its create entry (arguments, which cut of pfb_bank_cut.h, "is there a wave kernel"), its shape function and the signature of its enqueue.
 // The carried-history streams (redio_*_stream_*) are stream_carry.hip's, like every other plan's.
@@ -28,6 +30,11 @@ hipError_t launch_pfb_branch(const float2 *x, const float *h, float2 *v, long ro
 typedef hipError_t BankWaveFn(const float2 *x, const float *h, const float2 *tw64, float2 *out, long units, int taps_per_branch, uint64_t first_row,
                               bool fused, hipStream_t s);
 typedef hipError_t BankFilterFn(const float2 *in, const float *h, float2 *out, long units, int M, int P, long H, long f0, bool fused, hipStream_t st);
+// Workgroup kernel: `units` units from x into out; tw: the M-entry table, Tord: the 512-point plan's stage-ordered copy (else null)
+typedef hipError_t BankBlockFn(const float2 *x, const float *h, const float2 *tw, const float2 *Tord, float2 *out, long units, int M, int P,
+                               uint64_t first_row, bool fused, hipStream_t s);
+bool pfb_os_p2_supported(int nchan, int taps_per_branch, size_t hop);
+BankBlockFn launch_pfb_os_p2;                                 // pfb_os_p2.hip
 BankWaveFn launch_pfb_os, launch_pfb_os_synth;                // pfb_os_kernels.hip, pfb_os_synth_kernels.hip
 BankFilterFn launch_pfb_os_synth_ola;                         // pfb_os_synth_kernels.hip
 __attribute__((visibility("hidden"))) BankFilterFn launch_pfb_os_branch; // pfb_os_kernels.hip; not in the exported symbol set
@@ -50,10 +57,11 @@ struct BankFamily {
     bool transform_first; // route 0: transform into the scratch, then filter; or filter into the scratch, then transform
     BankWaveFn *wave;
     BankFilterFn *filter;
+    BankBlockFn *block;   // route 2's kernel; null: the family has none
 };
-const BankFamily SYNTH = {1, true, synth_wave, synth_filter};
-const BankFamily OS = {0, false, launch_pfb_os, launch_pfb_os_branch};
-const BankFamily OS_SYNTH = {1, true, launch_pfb_os_synth, launch_pfb_os_synth_ola};
+const BankFamily SYNTH = {1, true, synth_wave, synth_filter, nullptr};
+const BankFamily OS = {0, false, launch_pfb_os, launch_pfb_os_branch, launch_pfb_os_p2};
+const BankFamily OS_SYNTH = {1, true, launch_pfb_os_synth, launch_pfb_os_synth_ola, nullptr};
 } // namespace
 
 struct redio_pfb_bank {
@@ -65,6 +73,7 @@ struct redio_pfb_bank {
     float *d_h;          // the prototype, M P taps
     redio_fft *fft;      // the M-point plan: one of route 0's passes, and route 1's twiddle table
     bool wave_kernel;    // the shape has the one-kernel form
+    bool block_kernel;   // the plan asked for the workgroup form and the shape has it (route 2)
     int force_unfused;   // set_unfused
     size_t chunk_rows;   // route 0: scratch rows per pass (at least cut.min_rows)
     void *d_v;           // route 0: v_cap elements, a pass's rows between the two passes
@@ -85,7 +94,7 @@ static void bank_release(redio_pfb_bank *h)
 
 template <typename Hd>
 static int bank_create(Hd **h, const BankFamily &fam, const float *proto, int nchan, int taps_per_branch, size_t hop, unsigned flags,
-                       BankCut (*cut)(size_t M, size_t P, size_t H), bool wave_kernel)
+                       BankCut (*cut)(size_t M, size_t P, size_t H), bool wave_kernel, bool block_kernel = false)
 {
     if (!h) return REDIO_ERR_ARG;
     *h = nullptr;
@@ -98,6 +107,7 @@ static int bank_create(Hd **h, const BankFamily &fam, const float *proto, int nc
     p->fam = &fam; p->cut = cut((size_t)nchan, (size_t)taps_per_branch, hop);
     p->device = dev; p->M = nchan; p->P = taps_per_branch; p->H = hop; p->flags = flags;
     p->wave_kernel = wave_kernel;
+    p->block_kernel = block_kernel && fam.block && !wave_kernel;
     p->chunk_rows = bank_chunk_rows(p->cut, 0);
     int rc = redio_fft_create(&p->fft, nchan, fam.inverse);
     const size_t nt = (size_t)nchan * taps_per_branch;
@@ -109,12 +119,16 @@ static int bank_create(Hd **h, const BankFamily &fam, const float *proto, int nc
     return REDIO_OK;
 }
 
-static int bank_route(const redio_pfb_bank *h) { return h && h->wave_kernel && !h->force_unfused ? 1 : 0; }
+static int bank_route(const redio_pfb_bank *h)
+{
+    if (!h || h->force_unfused) return 0;
+    return h->wave_kernel ? 1 : h->block_kernel ? 2 : 0;
+}
 
 static int bank_reserve(redio_pfb_bank *h, size_t n_in)
 {
     if (!h) return REDIO_ERR_ARG;
-    if (bank_route(h) == 1) return REDIO_OK;
+    if (bank_route(h) != 0) return REDIO_OK; // one launch, no scratch
     const size_t units = bank_units(h->cut, n_in);
     if (units == 0) return REDIO_OK;
     const size_t pass = bank_pass_rows(h->cut, h->chunk_rows, units);
@@ -142,6 +156,11 @@ static int bank_enqueue(redio_pfb_bank *h, const void *d_in, size_t n_in, uint64
     const bool fused = (h->flags & REDIO_FIR_FUSED) != 0;
     if (bank_route(h) == 1) {
         const hipError_t e = fam.wave((const float2 *)d_in, h->d_h, redio_fft_twiddles_dev(h->fft), (float2 *)d_out, (long)units, h->P, first_row, fused, st);
+        return e == hipErrorNotSupported ? REDIO_ERR_UNSUPPORTED : hip_rc(e);
+    }
+    if (bank_route(h) == 2) {
+        const hipError_t e = fam.block((const float2 *)d_in, h->d_h, redio_fft_twiddles_dev(h->fft), redio_fft_twiddles_pass_dev(h->fft), (float2 *)d_out,
+                                       (long)units, h->M, h->P, first_row, fused, st);
         return e == hipErrorNotSupported ? REDIO_ERR_UNSUPPORTED : hip_rc(e);
     }
     const size_t pass = bank_pass_rows(c, h->chunk_rows, units);
@@ -177,7 +196,7 @@ static int bank_enqueue(redio_pfb_bank *h, const void *d_in, size_t n_in, uint64
         return REDIO_OK;                                                                                                  \
     }                                                                                                                     \
     extern "C" int redio_##NAME##_route(const redio_##NAME *h) { return bank_route(h); }                                  \
-    extern "C" int redio_##NAME##_is_fused(const redio_##NAME *h) { return bank_route(h); }                               \
+    extern "C" int redio_##NAME##_is_fused(const redio_##NAME *h) { return bank_route(h) == 1; }                          \
     extern "C" int redio_##NAME##_set_unfused(redio_##NAME *h, int unfused)                                               \
     {                                                                                                                     \
         if (!h) return REDIO_ERR_ARG;                                                                                     \
@@ -211,8 +230,9 @@ extern "C" int redio_pfb_synth_enqueue(redio_pfb_synth *h, const void *d_in, siz
 // ---- the oversampled channelizer: a unit is a row of M channels, from the M P samples that start every H ----
 extern "C" int redio_pfb_os_create(redio_pfb_os **h, const float *proto, int nchan, int taps_per_branch, size_t hop, unsigned flags)
 {
-    return bank_create(h, OS, proto, nchan, taps_per_branch, hop, flags,
-                       bank_cut_os, pfb_os_supported(nchan, taps_per_branch, hop));
+    const bool want_block = (flags & REDIO_PFB_OS_BLOCK) != 0; // this plan's own flag
+    return bank_create(h, OS, proto, nchan, taps_per_branch, hop, flags & ~REDIO_PFB_OS_BLOCK,
+                       bank_cut_os, pfb_os_supported(nchan, taps_per_branch, hop), want_block && pfb_os_p2_supported(nchan, taps_per_branch, hop));
 }
 void redio_pfb_os_shape(const redio_pfb_os *h, int *nchan, int *taps_per_branch, size_t *hop, int *device)
 {

@@ -6,7 +6,7 @@ import threading
 
 import numpy as np
 
-from . import REDIO_FIR_COMPLEX, REDIO_FIR_FUSED, REDIO_PFB_PSPEC_BLOCK, check, lib, redio_msg
+from . import REDIO_FIR_COMPLEX, REDIO_FIR_FUSED, REDIO_PFB_OS_BLOCK, REDIO_PFB_PSPEC_BLOCK, check, lib, redio_msg
 
 _pf = C.POINTER(C.c_float)
 
@@ -1074,22 +1074,23 @@ class _TwoPassBankBase:
     """what Synthesizer, OversampledChannelizer and OversampledSynthesizer share: a subclass gives its C symbols' prefix and what a
     call reads and returns"""
 
-    TWO_PASS, WAVE = 0, 1
+    TWO_PASS, WAVE, BLOCK = 0, 1, 2
     _prefix = None
 
     def _fn(self, name):
         return getattr(lib(), f"redio_{self._prefix}_{name}")
 
-    def _create(self, proto, nchan, taps_per_branch, fused, *hop):
+    def _create(self, proto, nchan, taps_per_branch, fused, *hop, more_flags=0):
         t, p = _taps(proto)
         assert len(t) == nchan * taps_per_branch
         self.nchan, self.taps_per_branch = int(nchan), int(taps_per_branch)
         self._h = C.c_void_p()
-        check(self._fn("create")(C.byref(self._h), p, self.nchan, self.taps_per_branch, *hop, REDIO_FIR_FUSED if fused else 0), f"{self._prefix}_create")
+        check(self._fn("create")(C.byref(self._h), p, self.nchan, self.taps_per_branch, *hop, (REDIO_FIR_FUSED if fused else 0) | more_flags), f"{self._prefix}_create")
 
     @property
     def route(self):
-        """what a call runs: WAVE (the 64-channel kernel; the oversampled plans: at hop 32) or TWO_PASS"""
+        """what a call runs: WAVE (the 64-channel kernel; the oversampled plans: at hop 32), BLOCK (the OversampledChannelizer's
+        workgroup kernel, one_kernel=True) or TWO_PASS"""
         return self._fn("route")(self._h)
 
     @property
@@ -1097,7 +1098,7 @@ class _TwoPassBankBase:
         return bool(self._fn("is_fused")(self._h))
 
     def set_unfused(self, unfused=True):
-        """send a WAVE plan down the two-pass route (tests and measurement): the same bits"""
+        """send a WAVE or BLOCK plan down the two-pass route (tests and measurement), or back: the same bits"""
         check(self._fn("set_unfused")(self._h, int(bool(unfused))), f"{self._prefix}_set_unfused")
 
     def set_chunk_rows(self, rows):
@@ -1161,13 +1162,15 @@ class OversampledChannelizer(_TwoPassBankBase):
     DESIGN.md 5.6d).  The Channelizer's branch filter on the nchan * taps_per_branch samples from r * hop on, the branch sums turned by
     ((first_row + r) * hop) mod nchan places (so that channel k of every row is referred to absolute time), then the forward transform:
     (n_in - nchan * taps_per_branch) // hop + 1 rows of nchan complex64 out.  At hop == nchan these are the Channelizer's rows.  64 channels
-    at hop 32 with 4 / 8 / 16 taps per branch are one kernel (route WAVE, is_fused); every other plan runs a branch pass into scratch and
-    its own forward transform (route TWO_PASS): the same bits."""
+    at hop 32 with 4 / 8 / 16 taps per branch are one kernel (route WAVE, is_fused).  one_kernel=True (REDIO_PFB_OS_BLOCK) asks for the
+    workgroup kernel (route BLOCK, not is_fused) at 32, 128, 256, 512 or 1024 channels, hop = nchan / 2 and 4 / 8 / 16 taps per branch
+    (but 1024 x 16): one launch, no scratch, any 8-byte aligned buffers; on every other shape it changes nothing.  Every other plan runs
+    a branch pass into scratch and its own forward transform (route TWO_PASS).  The same bits on all three routes."""
 
     _prefix = "pfb_os"
 
-    def __init__(self, proto, nchan=64, taps_per_branch=16, hop=32, fused=True):
-        self._create(proto, nchan, taps_per_branch, fused, int(hop))
+    def __init__(self, proto, nchan=64, taps_per_branch=16, hop=32, fused=True, one_kernel=False):
+        self._create(proto, nchan, taps_per_branch, fused, int(hop), more_flags=REDIO_PFB_OS_BLOCK if one_kernel else 0)
 
     @property
     def hop(self):

@@ -1,5 +1,5 @@
 """Throughput of the non-headline configs of BASELINE.json on one MI355X (own measurements; bench.py
-stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit|pfbpspecp2|pfbpspecp2split|ddc|ddcu8|upfirdn|pfbsynth|ddcupfirdn|ddcupfirdnu8|pfbos|pfbossynth]..."""
+stays on configs[1]).  usage: python tools/bench_configs.py [c3|c4|fir|fft|fftr|ovsavereal|pspec|pspecu8|pspecreal|pspecrealsplit|pfbpspec|pfbpspecsplit|pfbpspecp2|pfbpspecp2split|ddc|ddcu8|upfirdn|pfbsynth|ddcupfirdn|ddcupfirdnu8|pfbos|pfbosp2|pfbossynth]..."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, libredio_amd as R
@@ -811,6 +811,36 @@ if "pfbos" in which:
         line += (f" | Channelizer on the same input: {ms['channelizer']:.3f} ms; time per output row, oversampled / Channelizer = {per_row:.3f} "
                  f"(bytes model {(8 * H / M + 8) / 16:.3f})")
         print(line)
+        del plan, two, ana, out, out2, rows
+if "pfbosp2" in which:
+    # the oversampled channelizer's workgroup kernel (route 2, REDIO_PFB_OS_BLOCK) on 2^28 input samples, fused fold, hop M / 2: the flagged
+    # plan, the same plan through set_unfused (route 0, reserved: the branch pass into scratch, then the forward transform) and the
+    # Channelizer of the same prototype (pfb_p2_kernel) on the same input.  The three are timed alternately (twice each, the smaller time
+    # printed) in this one process; the two routes' outputs are compared bit for bit.  Share of 8 TB/s on 24 B per input sample (read
+    # once, a row of M channels written every M / 2 samples).  The bytes say time per output row / the Channelizer's = (8 H / M + 8) / 16 = 0.75.
+    x = R.synth_iq(0x5EED0004, 0, n)
+    for M, P in ((32, 16), (128, 8), (256, 8), (256, 16), (512, 8), (1024, 4)):
+        H = M // 2
+        h = R.dsputils.lpf_corrected(M * P, 0.45 / M)
+        plan, two, ana = R.OversampledChannelizer(h, M, P, H, fused=True, one_kernel=True), R.OversampledChannelizer(h, M, P, H, fused=True, one_kernel=True), R.Channelizer(h, M, P, fused=True)
+        assert plan.route == 2
+        two.set_unfused(True)
+        two.reserve(n)
+        nr = plan.nrows(n)
+        out = torch.empty(nr * M, dtype=torch.complex64, device="cuda")
+        out2 = torch.empty(nr * M, dtype=torch.complex64, device="cuda")
+        rows = torch.empty((ana.nrows(n), M), dtype=torch.complex64, device="cuda")
+        ms = {}
+        legs = {"block": lambda: plan(x, first_row=1, out=out), "two-pass": lambda: two(x, first_row=1, out=out2), "channelizer": lambda: ana(x, out=rows)}
+        for _ in range(2):
+            for name, f in legs.items():
+                ms[name] = min(ms.get(name, 1e30), timeit(f, n=10, warm=3))
+        same = torch.equal(torch.view_as_real(out).view(torch.int32), torch.view_as_real(out2).view(torch.int32))
+        per_row = (ms["block"] / nr) / (ms["channelizer"] / ana.nrows(n))
+        print(f"PFBOSP2 {M}ch P={P} hop {H} (route {plan.route}): {ms['block']:.3f} ms  {n/ms['block']/1e6:.1f} GS/s in  {24*n/ms['block']/1e6:.0f} GB/s algorithmic "
+              f"({24*n/ms['block']/1e6/8000:.1%} of 8 TB/s on 24 B/sample) | set_unfused (route {two.route}): {ms['two-pass']:.3f} ms, route 2 / route 0 = "
+              f"{ms['block']/ms['two-pass']:.3f}, outputs bit-equal: {same} | Channelizer on the same input: {ms['channelizer']:.3f} ms; time per output row, "
+              f"oversampled / Channelizer = {per_row:.3f} (bytes model 0.750)", flush=True)
         del plan, two, ana, out, out2, rows
 if "pfbossynth" in which:
     # the oversampled synthesis bank (redio_pfb_os_synth_*: inverse transform per row, then the weighted overlap-add at hop H) on 2^28 channel
