@@ -141,6 +141,8 @@ extern "C" long emu_pfb_os_p2(const float2 *x, long n_valid, const float *h, int
 extern "C" long emu_pfb_os_p2_rows_per_stream(long rows, long cus, int M) { return pfbos_p2_rows_per_stream(rows, cus, M); }
 extern "C" int emu_pfb_os_p2_streams_per_group(int M) { return pfbos_p2_streams_per_group(M); }
 extern "C" int emu_pfb_os_p2_rows_per_iter(int M) { return pfbos_p2_rows_per_iter(M); }
+extern "C" long emu_pfb_os_p2_streams(long rows, long rps) { return pfbos_p2_streams(rows, rps); }
+extern "C" long emu_pfb_os_p2_groups(long rows, long rps, int M) { return pfbos_p2_groups(rows, rps, M); }
 
 #ifdef EMU_PFB_OS_P2_MAIN
 // stand-alone run (host sanitizers): a small launch of every shape and load form on a ramp, every check of emu() armed

@@ -80,3 +80,11 @@ extern "C" long emu_pfbspec_p2(const float2 *rows, long nrows_total, int M, int 
 // the launcher's own numbers, for the tests' restatement of them
 extern "C" long emu_pfbspec_p2_units_per_stream(long nunits, long K, int split, long cus, int M) { return pfbspec_p2_units_per_stream(nunits, K, split != 0, cus, M); }
 extern "C" long emu_pfbspec_p2_split_rows(long K, long cus, int M) { return pfbspec_p2_split_rows(K, cus, M); }
+extern "C" int emu_pfbspec_p2_streams_per_group(int M) { return pfbspec_p2_streams_per_group(M); }
+extern "C" int emu_pfbspec_p2_rows_per_iter(int M) { return pfbspec_p2_rows_per_iter(M); }
+// {u0, u1, t0, t1} of stream s
+extern "C" void emu_pfbspec_p2_stream(long s, long ups, long nunits, long rows, long K, int split, long *out)
+{
+    const PfbSpecP2Stream st = pfbspec_p2_stream(s, ups, nunits, rows, K, split != 0);
+    out[0] = st.u0; out[1] = st.u1; out[2] = st.t0; out[3] = st.t1;
+}

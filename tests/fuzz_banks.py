@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Randomised differential run of the three two-pass filterbank plans against their bit-exact restatements (tests/pfb_synth_ref.py,
 pfb_os_ref.py, pfb_os_synth_ref.py), beyond the fixed shapes of their own test files: the sibling of tests/fuzz_parity.py and
-tests/fuzz_spectra.py for the synthesis bank redio_pfb_synth_*, the oversampled channelizer redio_pfb_os_*, the oversampled synthesis
-bank redio_pfb_os_synth_* and their three streams, all of which run through one driver (libredio_amd/csrc/pfb_bank.hip).
+tests/fuzz_spectra.py for the synthesis bank redio_pfb_synth_*, the oversampled channelizer redio_pfb_os_* (its workgroup kernel, route 2,
+included: REDIO_PFB_OS_BLOCK, one_kernel=True), the oversampled synthesis bank redio_pfb_os_synth_* and their three streams, all of
+which run through one driver (libredio_amd/csrc/pfb_bank.hip).
 
     python tests/fuzz_banks.py [seconds] [seed] [--only FAMILY]     FAMILY: pfb_synth pfb_os pfb_os_synth bank_streams
     python tests/fuzz_banks.py --draw COUNT [seed] [--only FAMILY]  the cases a run would draw, one JSON line each; needs no GPU
@@ -10,8 +11,8 @@ bank redio_pfb_os_synth_* and their three streams, all of which run through one 
 A run first draws OPENING cases of every family, whatever the clock says, then draws families at random until the budget ends.  Plans are
 cached by shape, and every case sets the driver's state (set_unfused, set_chunk_rows, reserve) itself, so a later call on a shape meets
 the scratch an earlier call left under another route, chunk or length.  Prints one FAIL line per mismatch and a summary; exit status 1 on
-any failure.  FUZZ_TRACE=file: what the generator needs to draw the next case is written there before every case; FUZZ_STATE=file runs
-exactly that one case again.
+any failure; the summary's `runs` counts the cases per family and, as "FAMILY route R", per family and route.  FUZZ_TRACE=file: what the
+generator needs to draw the next case is written there before every case; FUZZ_STATE=file runs exactly that one case again.
 
 A case is drawn completely (every seed included) before anything runs, and running it draws nothing more: the dry mode and a run see
 the same sequence.  The route, the hop, the output length and the chunk cut of a case are computed here from the rules include/redio.h,
@@ -38,6 +39,11 @@ STREAM_KINDS = ["pfb_synth", "pfb_os", "pfb_os_synth"]     # SynthesizerStream, 
 OPENING = fs.OPENING   # cases per family before the clock is consulted
 POOL = 12              # shapes kept per family for "the same shape again"
 WAVE_M, WAVE_H, WAVE_TAPS = 64, 32, (4, 8, 16)   # the one-kernel shapes: 64 channels, 4 / 8 / 16 taps per branch, the oversampled plans at hop 32
+# the oversampled channelizer's workgroup kernel (route 2, with the plan's one_kernel flag): these channel counts at hop M / 2 with
+# the wave kernels' taps, 1024 x 16 left out (include/redio.h; tests/pfb_os_p2_ref.route)
+BLOCK_M, BLOCK_TAPS, BLOCK_LEFT_OUT = (32, 128, 256, 512, 1024), WAVE_TAPS, ((1024, 16),)
+BLOCK_MIN_ROWS = 64    # PFBOS_P2_MIN_ROWS: a row stream's floor
+NOMINAL_CUS = 256      # the CU count the geometry of a route-2 case is recorded for (an MI355X's); the rule takes any
 STAGING = 8194         # 2 17 241: a generic-radix stage beyond LDS, the transform needs a work buffer (tests/test_fft_route.py)
 CHUNK_BYTES = 64 << 20  # route 0's default pass: 64 MiB of rows
 CHUNK_KINDS = ["default", "min", "min+1", "min+small", "all", "below"]   # below: fewer rows than a pass needs count as min_rows
@@ -75,6 +81,26 @@ def passes_of(cut, M, asked, units):
 
 def wave_shape(fam, M, P, H):
     return M == WAVE_M and P in WAVE_TAPS and (fam == "pfb_synth" or H == WAVE_H)
+
+
+def block_shape(fam, M, P, H):
+    """a shape with a workgroup form: what the plan's one_kernel flag turns into route 2"""
+    return fam == "pfb_os" and M in BLOCK_M and P in BLOCK_TAPS and 2 * H == M and (M, P) not in BLOCK_LEFT_OUT
+
+
+def block_consts(M):
+    """(G, TR) of pfb_os_p2_core.h, restated: streams per workgroup, rows per stream and iteration"""
+    return (1, 4096 // M) if M >= 256 else (256 // M, 16)
+
+
+def block_geometry(M, rows, cus):
+    """(G, TR, rows per stream, streams, workgroups) of a route-2 launch over `rows` rows on `cus` CUs, restated from
+    pfb_os_p2_core.h: about four workgroups per CU, a multiple of the iteration's rows, at least the floor"""
+    G, TR = block_consts(M)
+    rps = -(-rows // (4 * cus * G))
+    rps = max(-(-rps // TR) * TR, BLOCK_MIN_ROWS)
+    streams = -(-rows // rps)
+    return G, TR, rps, streams, -(-streams // G)
 
 
 def is_prime(n):
@@ -137,14 +163,29 @@ class Gen:
             if (nrows_per_hop(M, P, H) + 1) * M * (3 if stream else 1) <= fs.POINTS:
                 return H
 
+    def block_flagged(self, fam):
+        """a shape of the workgroup kernel with the flag set, 1024 x 16 (no workgroup form: route 0) among them.  The shares: a run
+        of 6000 cases has some 1500 of pfb_os; 0.6 of its fresh shapes come from here, 24 in 25 of those have a workgroup form and
+        0.7 of those calls stay on route 2 (driver_state), some 600 cases.  The rarest conditions on them are a refusal (0.15 of the
+        calls with a row, some 80 cases), none or one row (0.07 each, 85), spiced (0.2 of the calls that are not refused, 95), the
+        1024 channels (a fifth, less its 16 taps: 95) and a cached plan met again on the other route (a quarter of the cases draw an
+        earlier shape, 0.42 of those pairs differ in route: 90), each above the 60 that are 1 % of a run.  Of the 500 bank_streams
+        cases of this kind 0.6 come from here, 0.65 of those stay on route 2 (190) and 0.35 go down route 0 (100)."""
+        M = self.pick(list(BLOCK_M))
+        P = self.pick([4, 8, 4, 8, 16] if (M, 16) in BLOCK_LEFT_OUT else list(BLOCK_TAPS))   # 1024 x 16: a fifth of the 1024s
+        taps = "lpf" if self.p(0.5) else "synth"
+        return {"kind": fam, "M": M, "P": P, "H": M // 2, "fused": self.p(0.5), "taps": taps, "tseed": self.seed(), "block": True}
+
     def shape(self, fam, stream=False):
+        if fam == "pfb_os" and self.p(0.6):
+            return self.block_flagged(fam)
         r = self.rng.random()
         if r < 0.5:
             M = WAVE_M
         elif r < 0.53 and not stream:
             M = STAGING
         else:
-            M = self.pick([32, 128, 256, 100, 48, 12, 7, 2, 1, self.i(1, 301)])
+            M = self.pick([32, 128, 256, 512, 1024, 100, 48, 12, 7, 2, 1, self.i(1, 301)])
         if M == STAGING:
             P = self.pick([1, 2, 3])
         elif M == WAVE_M and self.p(0.4):   # the wave kernels' taps more often than the list below gives them: with hop 32 half the time
@@ -153,26 +194,39 @@ class Gen:
             P = self.pick([4, 8, 16, 1, 2, 3, 5, self.i(1, 21)])
         H = M if fam == "pfb_synth" else self.hop(M, P, stream)
         taps = "lpf" if M * P >= 3 and self.p(0.5) else "synth"
-        return {"kind": fam, "M": M, "P": P, "H": H, "fused": self.p(0.5), "taps": taps, "tseed": self.seed()}
+        # the flag where there is no workgroup form (another hop, other taps, 64 channels) and, now and then, where there is one
+        block = fam == "pfb_os" and self.p(0.3)
+        return {"kind": fam, "M": M, "P": P, "H": H, "fused": self.p(0.5), "taps": taps, "tseed": self.seed(), "block": block}
 
     def driver_state(self, c, fam, units):
         """set_unfused, set_chunk_rows and reserve, drawn for every case: the plan is cached, so what an earlier case set is still there"""
         M, P, H = c["M"], c["P"], c["H"]
         min_rows = cut_of(fam, M, P, H)[3]
         wave = wave_shape(fam, M, P, H)
+        blk = c["block"] and block_shape(fam, M, P, H)
         kind = self.pick(CHUNK_KINDS)
         chunk = {"default": 0, "min": min_rows, "min+1": min_rows + 1, "min+small": min_rows + self.i(2, 8),
                  "all": max(1, units + min_rows - 1 + self.i(0, 9)), "below": self.i(1, min_rows + 1)}[kind]
-        c.update(unfused=wave and self.p(0.4), chunk_kind=kind, chunk=chunk, reserve=self.p(0.2))
+        stream = c.get("family") == "bank_streams"
+        c.update(unfused=(wave and self.p(0.4)) or (blk and self.p(0.35 if stream else 0.3)), chunk_kind=kind, chunk=chunk, reserve=self.p(0.2))
 
     def one_call(self, fam):
         c = self.shape_again(fam, lambda: self.shape(fam))
         M, P, H = c["M"], c["P"], c["H"]
         window, hop, unit_out, min_rows = cut = cut_of(fam, M, P, H)
         wave = wave_shape(fam, M, P, H)
+        blk = c["block"] and block_shape(fam, M, P, H)
         r = self.rng.random()
         if M == STAGING:
             units = self.i(0, 4)
+        elif blk:   # the workgroup kernel's launch: G streams per workgroup, TR rows per iteration, a floor of 64 rows per stream
+            G, TR = block_consts(M)
+            if r < 0.14:       # no row and one row: 7 % each
+                units = int(r >= 0.07)
+            elif r < 0.5:      # either side of an iteration, of a stream's floor and of a workgroup of such streams
+                units = self.pick([TR, BLOCK_MIN_ROWS, BLOCK_MIN_ROWS * G]) + self.i(-1, 2)
+            else:              # up to past three workgroups, with a short last stream and a short last iteration
+                units = self.i(0, 3 * BLOCK_MIN_ROWS * G + 21)
         elif r < 0.06:   # no unit and one unit: 6 % each, a uniform draw would leave them under 1 %
             units = 0
         elif r < 0.12:
@@ -185,10 +239,11 @@ class Gen:
         T = units if fam == "pfb_os" else units + min_rows - 1   # rows the call touches: first_row + T never passes 2^64
         first = 0 if fam == "pfb_synth" else self.pick([0, 1, self.i(0, 1 << 32), (1 << 32) + 5, TOP - T])
         self.driver_state(c, fam, units)
-        refusal = units > 0 and self.p(0.05)   # an output range that overlaps the input range: REDIO_ERR_ARG, nothing written
+        # an output range that overlaps the input range: REDIO_ERR_ARG, nothing written (more often on the workgroup kernel's shapes)
+        refusal = units > 0 and self.p(0.15 if blk else 0.05)
         c.update(family=fam, units=units, n=n, first_row=first, in_base=8 * self.i(0, 2), out_base=8 * self.i(0, 2),
                  refusal=refusal, overlap=self.rng.random() if refusal else 0.0, out_first=refusal and self.p(0.5),
-                 seed=self.seed(), spice=self.seed() if self.p(0.12) else 0)
+                 seed=self.seed(), spice=self.seed() if self.p(0.2 if blk else 0.12) else 0)
         c["route"] = route_of(c)
         return c
 
@@ -224,13 +279,15 @@ class Gen:
             pieces.append(ln)
             pos += ln
         again = sorted(self.i(0, pos + 1) for _ in range(self.i(0, 8))) if self.p(0.5) else None
+        c["family"] = "bank_streams"
         self.driver_state(c, kind, units_of(cut_of(kind, M, P, H), pos))
         if c["chunk_kind"] == "all":   # a piece is no whole call: keep to the chunk settings that do not depend on the length
             c.update(chunk_kind="default", chunk=0)
         c.update(family="bank_streams", pieces=pieces, again=again, n=int(pos), units=units_of(cut_of(kind, M, P, H), pos), first_row=0,
                  seed=self.seed(), spice=self.seed() if self.p(0.12) else 0)
         c["route"] = route_of(c)
-        c["route"].update(zero_piece=0 in pieces, short_piece=any(0 < v < W for v in pieces), long_piece=any(v > 2 * W for v in pieces),
+        made = [units_of(cut_of(kind, M, P, H), int(e)) for e in np.cumsum([0] + pieces)]
+        c["route"].update(odd_rows_piece=any((b - a) % 2 for a, b in zip(made[:-1], made[1:])), zero_piece=0 in pieces, short_piece=any(0 < v < W for v in pieces), long_piece=any(v > 2 * W for v in pieces),
                           odd_piece=any(v % 2 for v in pieces), reset=again is not None)
         return c
 
@@ -240,13 +297,17 @@ class Gen:
 
 def route_of(c):
     """what the driver does with this case, from the documented rules: the route (include/redio.h: 64 channels x 4 / 8 / 16 taps, the
-    oversampled plans at hop 32, unless set_unfused), the output length, and on route 0 the cut of pfb_bank_cut.h"""
+    oversampled plans at hop 32; 2 the oversampled channelizer's workgroup shapes with the plan's flag; 0 after set_unfused), the
+    launch geometry of route 2 on NOMINAL_CUS CUs, the output length, and on route 0 the cut of pfb_bank_cut.h"""
     fam, M, P, H, units = c["kind"], c["M"], c["P"], c["H"], c["units"]
     cut = cut_of(fam, M, P, H)
     wave = wave_shape(fam, M, P, H)
-    route = 1 if wave and not c["unfused"] else 0
+    blk = c["block"] and block_shape(fam, M, P, H)
+    route = 0 if c["unfused"] else 1 if wave else 2 if blk else 0
     npass, last, per = passes_of(cut, M, c["chunk"], units) if units and route == 0 else (0, 0, 0)
-    return {"wave_shape": wave, "route": route, "m64_generic": M == WAVE_M and not wave, "two_pass_shape": not wave, "nout": units * cut[2],
+    geometry = list(block_geometry(M, units, NOMINAL_CUS)) if route == 2 else None
+    return {"wave_shape": wave, "block_shape": blk, "flag_no_form": c["block"] and not blk, "geometry": geometry, "route": route,
+            "m64_generic": M == WAVE_M and not wave, "two_pass_shape": not wave and not blk, "nout": units * cut[2],
             "min_rows": cut[3], "passes": npass, "short_last": bool(npass >= 2 and last < per), "staging": M if M == STAGING else 0,
             "skips_oldest": bool(fam == "pfb_os_synth" and nrows_per_hop(M, P, H) * H > P * M)}
 
@@ -354,19 +415,30 @@ class Runner:
         R, kind = self.R, kind or c["kind"]
         cls = {"pfb_synth": R.Synthesizer, "pfb_os": R.OversampledChannelizer, "pfb_os_synth": R.OversampledSynthesizer, "pfb": R.Channelizer}[kind]
         hop = (c["H"],) if kind in ("pfb_os", "pfb_os_synth") else ()
-        key = (cls.__name__, c["M"], c["P"], *hop, c["fused"], c["taps"], c["tseed"] if c["taps"] == "synth" else 0)
-        return self.plan(key, lambda: cls(taps_of(self.O, c), c["M"], c["P"], *hop, fused=c["fused"]))
+        more = {"one_kernel": c["block"]} if kind == "pfb_os" else {}
+        key = (cls.__name__, c["M"], c["P"], *hop, c["fused"], c["taps"], c["tseed"] if c["taps"] == "synth" else 0, *more.values())
+        return self.plan(key, lambda: cls(taps_of(self.O, c), c["M"], c["P"], *hop, fused=c["fused"], **more))
 
     def set_state(self, plan, c):
         plan.set_unfused(c["unfused"])
         plan.set_chunk_rows(c["chunk"])
+        self.reserved = None
         if c["reserve"]:
+            count = self.R.lib().redio_malloc_count
+            before = count()
             plan.reserve(c["n"])
+            self.reserved = count()
+            # routes 1 and 2 have no scratch: the reserve does nothing there (include/redio.h)
+            assert not (c["kind"] == "pfb_os" and c["route"]["route"] and self.reserved != before), "a reserve on route 1 or 2 allocated"
+
+    def after_reserve(self, c):
+        """the oversampled channelizer's call behind a reserve of its length allocated nothing (route 0: the reserve took the scratch)"""
+        return c["kind"] != "pfb_os" or self.reserved is None or self.R.lib().redio_malloc_count() == self.reserved
 
     def shape_answers(self, plan, c):
         """route, is_fused, hop and the output length against this tool's own arithmetic"""
         kind, r = c["kind"], c["route"]
-        if plan.route != r["route"] or plan.is_fused != bool(r["route"]):
+        if plan.route != r["route"] or plan.is_fused != (r["route"] == 1):
             return ("route / is_fused", plan.route, plan.is_fused)
         if kind != "pfb_synth" and plan.hop != c["H"]:
             return ("hop", plan.hop)
@@ -426,6 +498,8 @@ class Runner:
         assert not len(x) or dx.data_ptr() % 16 == c["in_base"]   # (an empty view reports no address of its own)
         whole, lo = self.guarded(len(want), c["out_base"])
         got = self.call(plan, c, dx, whole[lo: lo + len(want)]).reshape(-1)
+        if not self.after_reserve(c):
+            return False, "the call behind a reserve allocated"
         if got.numel() != len(want) or not fs.same_nan(got.cpu().numpy(), want):
             return False, "values"
         if not (fs.Runner.still_nan(self.t.view_as_real(whole[:lo])) and fs.Runner.still_nan(self.t.view_as_real(whole[lo + len(want):]))):
@@ -491,6 +565,8 @@ class Runner:
         self.t.cuda.synchronize()
         brief = {k: v for k, v in c.items() if k != "route"}
         fs.check(c["family"], ok, (why, json.dumps(brief)))
+        per_route = f"{c['family']} route {c['route']['route']}"
+        fs.runs[per_route] = fs.runs.get(per_route, 0) + 1
 
 
 def main():

@@ -2,7 +2,8 @@
 """Randomised differential run of the real-input and spectrum plans against their bit-exact restatements (tests/fftr_ref.py,
 ovsave_real_ref.py, pspec_ref.py, pspec_real_ref.py, pfb_pspec_ref.py), beyond the fixed shapes of their own test files: the sibling of
 tests/fuzz_parity.py for redio_fftr_*, redio_ovsave_real_*, redio_pspec_* (cf32 and u8), redio_pspec_real_* and their streams, and for the
-polyphase spectrometer redio_pfb_pspec_* (cf32 and u8, fused and generic) and its streams.
+polyphase spectrometer redio_pfb_pspec_* (cf32 and u8; the 64-channel kernel, the workgroup kernel of REDIO_PFB_PSPEC_BLOCK and the
+generic route) and its streams.
 
     python tests/fuzz_spectra.py [seconds] [seed] [--only FAMILY]     FAMILY: fftr ovsave_real pspec pspec_u8 pspec_real streams
                                                                               pfb_pspec pfb_streams
@@ -10,7 +11,8 @@ polyphase spectrometer redio_pfb_pspec_* (cf32 and u8, fused and generic) and it
 
 A run first draws OPENING cases of every family, whatever the clock says, then draws families at random until the budget ends.  Plans are
 cached by shape, so a later call on a shape meets the scratch an earlier call left.  Prints one FAIL line per mismatch and a summary;
-exit status 1 on any failure.  FUZZ_TRACE=file: what the generator needs to draw the next case is written there before every case;
+exit status 1 on any failure; the summary's `runs` counts the cases per family and, for the polyphase spectrometer, as "FAMILY route R"
+per family and route.  FUZZ_TRACE=file: what the generator needs to draw the next case is written there before every case;
 FUZZ_STATE=file runs exactly that one case again.
 
 A case is drawn completely (every seed included) before anything runs, and running it draws nothing more: the dry mode and a run see
@@ -40,6 +42,9 @@ STAGING = {"pspec": (65536, 8194), "pspec_u8": (65536, 8194), "pspec_real": (131
 PFB_M = 64                                # the polyphase spectrometer's one-kernel channel count, with PFB_TAPS taps per branch
 PFB_TAPS = (4, 8, 16)
 PFB_ONE_KERNEL = (32, 128, 256, 512, 1024)   # channel counts the inner channelizer runs as one kernel (with PFB_TAPS), not as two passes
+PFB_BLOCK_MIN_ROWS = 64                   # PFBSPEC_P2_MIN_ROWS: a row stream of the workgroup kernel (route 2) sums at least this many rows
+PFB_BLOCK_SPLIT_GROUPS_PER_CU = 2         # PFBSPEC_P2_SPLIT_GROUPS_PER_CU: route 2's auto mode is rows mode from this many workgroups per CU
+NOMINAL_CUS = 256                         # the CU count a route-2 case's geometry is recorded for (an MI355X's); the rule takes any
 PFB_SPLIT_WAVES = 1024                    # PFBSPEC_SPLIT_WAVES: auto lets a wave own whole rows from this many waves of ceil(64 / K) rows
 
 
@@ -110,8 +115,8 @@ class Gen:
         del self.pool[fam][:-12]
         return s
 
-    def spiced(self):
-        return self.seed() if self.p(0.12) else 0
+    def spiced(self, prob=0.12):
+        return self.seed() if self.p(prob) else 0
 
     # -- the families --
     def fftr(self):
@@ -266,24 +271,42 @@ class Gen:
         # half of the shapes have 64 channels and four calls in five name their split mode: with K > 16 on about 0.58 of the shapes and the
         # fused taps on 0.79, less would leave "fused, K > 16, mode 1" (and mode 2) under 1 % of a run's cases.  Auto, at the row
         # counts of this tool, is the route of mode 2 (its threshold is test_gpu_pfb_pspec_launch.py's).
-        M = PFB_M if self.p(0.5) else self.pick([32, 128, 256, 512, 1024, 100, 7, 48, self.i(1, 300)])
-        P = self.pick([4, 8, 16, self.i(1, 20)])
+        # The workgroup kernel (route 2: the plan's flag on a one-kernel shape of the inner channelizer): a family has some 750 of a run's
+        # 6000 cases, so a condition that must hold in 60 of them needs 8 % of its family.  Of the 0.45 without 64 channels 0.85 have a
+        # workgroup channel count, 0.9 of those the kernel's taps and 0.8 of those the flag: some 205 route-2 cases per family -- 68 per
+        # split mode (drawn evenly there), 40 per channel count and family, 72 spiced (0.35 there), and 50 per family on the same shapes
+        # without the flag, down the generic route.  The two-pass shapes keep some 80 per family.
+        if self.p(0.55):
+            M = PFB_M
+        elif self.p(0.85):
+            M = self.pick(list(PFB_ONE_KERNEL))
+        else:
+            M = self.pick([100, 7, 48, self.i(1, 300)])
+        if M in PFB_ONE_KERNEL and self.p(0.6):
+            P = self.pick(list(PFB_TAPS))
+        else:
+            P = self.pick([4, 8, 16, self.i(1, 20)])
+        block = self.p(0.8 if M in PFB_ONE_KERNEL and P in PFB_TAPS else 0.2)   # elsewhere the flag changes nothing
         K = min(self.pick([1, 2, 15, 16, 17, 31, 32, 33, 40, self.i(1, 71)]), transforms_allowed(M))
         while stream and K > 1 and 3 * (K - 1 + P) + K + 1 > transforms_allowed(M):   # a piece longer than two windows stays within the bound
             K //= 2
         taps = "lpf" if M * P >= 3 and self.p(0.5) else "synth"
-        return {"M": M, "P": P, "K": K, "fir_fused": self.p(0.5), "taps": taps, "tseed": self.seed()}
+        return {"M": M, "P": P, "K": K, "fir_fused": self.p(0.5), "taps": taps, "tseed": self.seed(), "block": block}
 
     def pfb_pspec(self):
         c = self.shape_again("pfb_pspec", self._pfb_shape)
         M, P, K = c["M"], c["P"], c["K"]
         W, H = (K - 1 + P) * M, K * M
         fused = M == PFB_M and P in PFB_TAPS
-        rows = self.i(0, 3 * -(-64 // K) + 3) if fused else self.i(0, 6)   # fused: several wavefronts of ceil(64 / K) rows and a short last one
+        two = pfb_route_number(c) == 2
+        if two:   # the workgroup kernel: up to past three workgroups of G streams of ceil(64 / K) rows, and a short last stream
+            rows = self.i(0, 3 * pfb_block_consts(M)[0] * -(-PFB_BLOCK_MIN_ROWS // K) + 3)
+        else:
+            rows = self.i(0, 3 * -(-64 // K) + 3) if fused else self.i(0, 6)   # fused: several wavefronts of ceil(64 / K) rows and a short last one
         rows = min(rows, transforms_allowed(M) // K)
         n = W + (rows - 1) * H + self.i(0, H) if rows else self.i(0, W)
-        c.update(family="pfb_pspec", rows=rows, n=n, mode=self.pick([0, 1, 1, 2, 2]), base=2 * self.i(0, 8), cbase=8 * self.i(0, 2), u8_first=self.p(0.5),
-                 seed=self.seed(), spice=self.spiced())
+        c.update(family="pfb_pspec", rows=rows, n=n, mode=self.pick([0, 1, 2] if two else [0, 1, 1, 2, 2]), base=2 * self.i(0, 8), cbase=8 * self.i(0, 2),
+                 u8_first=self.p(0.5), seed=self.seed(), spice=self.spiced(0.35 if two else 0.12))
         c["route"] = pfb_route(c)
         return c
 
@@ -309,10 +332,11 @@ class Gen:
             pieces.append(ln)
             pos += ln
         again = sorted(self.i(0, pos + 1) for _ in range(self.i(0, 8))) if self.p(0.5) else None
-        route = {k: v for k, v in pfb_route(dict(c, rows=1, mode=0, base=0, cbase=0)).items() if k not in ("mode", "split", "base", "cbase")}
+        route = {k: v for k, v in pfb_route(dict(c, rows=1, mode=0, base=0, cbase=0)).items() if k not in ("mode", "split", "base", "cbase", "geometry")}
         route.update(u8=u8, zero_piece=0 in pieces, short_piece=any(0 < v < W for v in pieces), long_piece=any(v > 2 * W for v in pieces),
                      odd_piece=any(v % 2 for v in pieces), reset=again is not None)
-        c.update(family="pfb_streams", u8=u8, pieces=pieces, again=again, rows=int(pos), seed=self.seed(), spice=0 if u8 else self.spiced(),
+        c.update(family="pfb_streams", u8=u8, pieces=pieces, again=again, rows=int(pos), seed=self.seed(),
+                 spice=0 if u8 else self.spiced(0.35 if route["route"] == 2 else 0.12),
                  route=route)
         return c
 
@@ -332,13 +356,44 @@ def pspec_route(fam, c):
             "staging": N if N in STAGING.get(fam, ()) else 0}
 
 
+def pfb_route_number(c):
+    """redio_pfb_pspec_route by the rule of include/redio.h: 1 the 64-channel wave kernel, 2 the workgroup kernel (the plan's flag on 32,
+    128, 256, 512 or 1024 channels with the same taps), 0 generic"""
+    if c["M"] == PFB_M and c["P"] in PFB_TAPS:
+        return 1
+    return 2 if c["block"] and c["M"] in PFB_ONE_KERNEL and c["P"] in PFB_TAPS else 0
+
+
+def pfb_block_consts(M):
+    """(G, TR) of pfb_pspec_p2_core.h, restated: streams per workgroup, channelizer rows per stream and iteration"""
+    return (1, 4096 // M) if M >= 256 else (256 // M, 16)
+
+
+def pfb_block_geometry(M, K, rows, mode, cus):
+    """a route-2 launch over `rows` output rows on `cus` CUs, restated from pfb_pspec_p2_core.h: whether a stream owns runs of segments
+    (split), the units (rows, or segments), the units per stream (aiming at 4 cus G streams, at least 64 channelizer rows of full
+    units), the streams and the workgroups"""
+    G, TR = pfb_block_consts(M)
+    least_rows = -(-PFB_BLOCK_MIN_ROWS // K)
+    split = K > SEG and (mode == 2 or (mode == 0 and rows < PFB_BLOCK_SPLIT_GROUPS_PER_CU * cus * G * max(-(-1 // (4 * cus * G)), least_rows)))
+    units = rows * (-(-K // SEG)) if split else rows
+    ups = max(-(-units // (4 * cus * G)), -(-PFB_BLOCK_MIN_ROWS // (SEG if split else K)))
+    streams = -(-units // ups)
+    return {"G": G, "TR": TR, "split": bool(split), "units": units, "ups": ups, "streams": streams, "groups": -(-streams // G)}
+
+
 def pfb_route(c):
     """the polyphase spectrometer's route for this call, from the documented rules (include/redio.h)"""
     M, P, K = c["M"], c["P"], c["K"]
     fused = M == PFB_M and P in PFB_TAPS
     one_kernel = M in PFB_ONE_KERNEL and P in PFB_TAPS
+    number = pfb_route_number(c)
+    geometry = pfb_block_geometry(M, K, c["rows"], c["mode"], NOMINAL_CUS) if number == 2 else None
     split = K > SEG and (not fused or c["mode"] == 2 or (c["mode"] == 0 and c["rows"] < PFB_SPLIT_WAVES * -(-64 // K)))
-    return {"fused": fused, "one_kernel": one_kernel, "two_pass": not fused and not one_kernel, "m64_generic": M == PFB_M and not fused,
+    if number == 2:
+        split = geometry["split"]
+    return {"route": number, "flag_no_form": c["block"] and number != 2, "geometry": geometry,
+            "fused": fused, "one_kernel": one_kernel, "two_pass": not fused and not one_kernel, "m64_generic": M == PFB_M and not fused,
             "segments2": K > SEG, "mode": c["mode"], "split": bool(split), "fir_fused": c["fir_fused"], "base": c["base"], "cbase": c["cbase"]}
 
 
@@ -622,8 +677,8 @@ class Runner:
 
     # -- the polyphase spectrometer --
     def pfb_plan(self, c):
-        key = ("PolyphaseSpectrum", c["M"], c["P"], c["K"], c["fir_fused"], c["taps"], c["tseed"] if c["taps"] == "synth" else 0)
-        return self.plan(key, lambda: self.R.PolyphaseSpectrum(pfb_taps_of(self.O, c), c["M"], c["P"], c["K"], fused=c["fir_fused"]))
+        key = ("PolyphaseSpectrum", c["M"], c["P"], c["K"], c["fir_fused"], c["taps"], c["tseed"] if c["taps"] == "synth" else 0, c["block"])
+        return self.plan(key, lambda: self.R.PolyphaseSpectrum(pfb_taps_of(self.O, c), c["M"], c["P"], c["K"], fused=c["fir_fused"], one_kernel=c["block"]))
 
     def pfb_pspec(self, c):
         ref, M, P, K, ff = self.pfb_pspec_ref, c["M"], c["P"], c["K"], c["fir_fused"]
@@ -636,6 +691,8 @@ class Runner:
         plan.set_split(c["mode"])
         if not (plan.nrows(c["n"]) == rows == len(want) == len(want8) == c["rows"]) or plan.is_fused != c["route"]["fused"]:
             return False, ("nrows / is_fused", plan.nrows(c["n"]), rows, len(want), plan.is_fused)
+        if plan.route != c["route"]["route"]:
+            return False, ("route", plan.route)
         dx = self.dev(x, c["cbase"])
         assert dx.data_ptr() % 16 == c["cbase"]
         out = self.nans(want.size + 8)
@@ -672,7 +729,11 @@ class Runner:
         want = (ref.spectrum_u8 if u8 else ref.spectrum)(x, h, M, P, K, c["fir_fused"]).reshape(-1)
         per = 2 if u8 else 1     # elements of the device view per sample
         dx = self.dev(x)
-        st = self.R.Stream(self.pfb_plan(c), u8=u8)
+        plan = self.pfb_plan(c)
+        plan.set_split(0)   # a cached plan may come from a pfb_pspec case that named its mode
+        if plan.route != c["route"]["route"] or plan.is_fused != c["route"]["fused"]:
+            return False, ("route / is_fused", plan.route, plan.is_fused)
+        st = self.R.Stream(plan, u8=u8)
         cuts = np.concatenate([[0], np.cumsum(c["pieces"])]).astype(np.int64)
         for which, cuts in (("first pass", cuts), ("after reset", None if c["again"] is None else np.array([0] + c["again"] + [n], np.int64))):
             if cuts is None:
@@ -708,6 +769,9 @@ class Runner:
         t.cuda.synchronize()
         brief = {k: v for k, v in c.items() if k != "route"}
         check(c["family"], ok, (why, json.dumps(brief)))
+        if "route" in c["route"]:   # the polyphase spectrometer's cases: a count per family and route
+            per_route = f"{c['family']} route {c['route']['route']}"
+            runs[per_route] = runs.get(per_route, 0) + 1
 
 
 def main():

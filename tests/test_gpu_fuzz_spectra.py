@@ -1,6 +1,6 @@
 """A short, seeded run of the second randomised differential tool (tests/fuzz_spectra.py) per family: the real-input transform,
 overlap-save on real streams, the power spectrum from cf32 samples, from u8 bytes and from real samples, their streams, and the polyphase
-spectrometer (cf32 and bytes, fused and generic) and its streams, bit for bit against the restatements on random shapes, steps, windows, split modes, alignments and message cuts.  Each run starts with the tool's
+spectrometer (cf32 and bytes; the wave kernel, the workgroup kernel of one_kernel=True and the generic route) and its streams, bit for bit against the restatements on random shapes, steps, windows, split modes, alignments and message cuts.  Each run starts with the tool's
 opening round of 24 cases, so its route coverage (tests/test_spectra_fuzz_cpu.py) does not depend on the machine's speed."""
 import ast
 import os
@@ -30,3 +30,5 @@ def test_randomised_differential_run_of_the_spectrum_plans(gpu, family):
     runs = ast.literal_eval(summary[len("runs "): summary.rindex(" failures")])
     print(family, runs)
     assert runs.get(family, 0) >= 24, summary
+    if family in ("pfb_pspec", "pfb_streams"):   # the polyphase spectrometer's workgroup kernel ran: the tool's own count of its route-2 cases
+        assert runs.get(family + " route 2", 0) >= 1, summary

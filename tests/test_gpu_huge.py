@@ -7,6 +7,8 @@ boundary that matters: the start, byte offset 2^32 (sample 2^29), element 2^31, 
 The real-input and spectrum plans read narrower views of the same memory as f32 samples and as u8 I/Q bytes (second half of this file).
 The three two-pass filterbank plans (synthesis bank, oversampled channelizer, oversampled synthesis bank) read it as samples or as rows
 of channel values, on the wave route and down route 0 through hundreds of default passes (last part of this file).
+The three workgroup kernels (the Channelizer's at 32 to 1024 channels, the polyphase spectrometer's and the oversampled channelizer's
+with one_kernel=True) run on it as well: their index arithmetic is their own.
 Skipped when the device has less than 120 GB free."""
 import numpy as np
 import pytest
@@ -125,6 +127,26 @@ def test_channelizer_past_2_32(gpu, redio, oracle, big):
         got = outg[:, lo:lo + cnt, :].cpu().numpy()
         assert same_bits(np.ascontiguousarray(got.transpose(1, 0, 2)).reshape(cnt, M), want), r
     del outg
+
+
+@pytest.mark.parametrize("M,P,groups", [(32, 4, 1), (512, 16, 8), (1024, 8, 1)])
+def test_channelizer_workgroup_kernel_past_2_32(gpu, redio, oracle, big, M, P, groups):
+    """pfb_p2_kernel, the workgroup kernel of 32 to 1024 channels, on the whole stream: its index arithmetic is not the wave kernel's
+    (rows per stream, streams per workgroup, row * M + n); one shape also in the grouped layout [group][row][M / groups]"""
+    h = oracle.lpf_corrected(M * P, 0.45 / M)
+    plan = redio.Channelizer(h, M, P)
+    rows = plan.nrows(N)
+    assert rows == N // M - P + 1 and rows * M > 1 << 32 and N * 8 > 1 << 35
+    for g in sorted({1, groups}):
+        out = plan(big, ngroups=g)
+        assert out.numel() == rows * M and tuple(out.shape) == ((rows, M) if g == 1 else (g, rows, M // g))
+        for r in marks(rows, M):
+            lo = max(0, min(r - 20, rows - 40))
+            cnt = min(40, rows - lo)
+            want = oracle.pfb_channelizer(oracle.synth_iq(SEED, lo * M, (cnt + P - 1) * M), h, M, P, fused=True)[:cnt]
+            got = out[lo:lo + cnt].cpu().numpy() if g == 1 else np.ascontiguousarray(out[:, lo:lo + cnt, :].cpu().numpy().transpose(1, 0, 2)).reshape(cnt, M)
+            assert same_bits(got, want), (g, r)
+        del out
 
 
 @pytest.mark.parametrize("nfft,k", [(65536, 8193), (4096, 127), (32768, 127)])
@@ -302,6 +324,41 @@ def test_pfb_pspec_past_2_32(gpu, redio, oracle, big, M, P, K, mode, u8):
     del out
 
 
+@pytest.mark.parametrize("M,P,K,mode,u8", [(128, 8, 16, 1, False), (1024, 4, 17, 2, False), (32, 16, 4, 0, True)])
+def test_pfb_pspec_workgroup_kernel_past_2_32(gpu, redio, oracle, big, M, P, K, mode, u8):
+    """redio_pfb_pspec_enqueue with one_kernel=True (route 2) on 2^32 samples and more: a thread group per run of whole rows, per run of
+    segments (K = 17: about 2 GiB of partials, and the fold pass), and from more than 2^33 bytes of u8 I/Q.  The rows either side of the
+    row streams' boundaries next to every mark are compared as well (the launch geometry restated in tests/fuzz_spectra.py)."""
+    import fuzz_spectra
+    import pfb_pspec_ref
+    import pspec_ref
+    h = oracle.lpf_corrected(M * P, 0.45 / M)
+    W, H = pfb_pspec_ref.shape(M, P, K)
+    plan = redio.PolyphaseSpectrum(h, M, P, K, one_kernel=True)
+    plan.set_split(mode)
+    rows = plan.nrows(NV)
+    assert rows == (NV - W) // H + 1 and plan.route == 2 and not plan.is_fused
+    assert rows * K * M > 1 << 32   # channelizer rows times channels: the elements the kernel's row indices address
+    if u8:
+        raw = u8_view(gpu, big)
+        assert raw.numel() == 2 * NV > 1 << 33
+        out = plan.from_bytes(raw)
+        want_of = lambda lo, cnt: pfb_pspec_ref.spectrum_u8(host_u8(oracle, lo, cnt), h, M, P, K, True)
+    else:
+        assert NV * 8 > 1 << 35
+        out = plan(big)
+        want_of = lambda lo, cnt: pfb_pspec_ref.spectrum(oracle.synth_iq(SEED, lo, cnt), h, M, P, K, True)
+    assert tuple(out.shape) == (rows, M)
+    g = fuzz_spectra.pfb_block_geometry(M, K, rows, mode, gpu.cuda.get_device_properties(0).multi_processor_count)
+    S = -(-K // pspec_ref.SEG) if g["split"] else 1
+    assert g["split"] == (K > pspec_ref.SEG) and g["units"] == rows * S and g["groups"] > 100
+    if g["split"]:
+        assert g["units"] * M * 4 > 15 << 27   # the partials: about 2 GiB
+    seams = [q for b in marks(rows, H) for q in ((b * S // g["ups"]) * g["ups"] // S, -(-(b * S // g["ups"] + 1) * g["ups"] // S))]
+    check_rows(out, rows, W, H, want_of, seams)
+    del out
+
+
 @pytest.mark.parametrize("nfft,k,mode", [(2048, 16, 1), (2048, 16, 2), (2048, 17, 2), (4096, 4, 0)])
 def test_pspec_real_past_2_32(gpu, redio, oracle, big, nfft, k, mode):
     """redio_pspec_real_enqueue on 2^32 f32 samples and more: the fused kernel in both launch modes (one segment per row at K = 16;
@@ -398,11 +455,13 @@ def check_bank(oracle, out, kind, h, M, P, H, units, at):
         assert same_bits(out[lo * unit_out:(lo + cnt) * unit_out].cpu().numpy(), want), (kind, M, P, H, b)
 
 
-def run_bank_past_2_32(gpu, redio, oracle, big, kind, M, P, H, n_in, routes):
-    """the call on the first n_in elements of the stream on every route of `routes`; returns (units, output elements)"""
+def run_bank_past_2_32(gpu, redio, oracle, big, kind, M, P, H, n_in, routes, one_kernel=False):
+    """the call on the first n_in elements of the stream on every route of `routes`; returns (units, output elements).  one_kernel: the
+    oversampled channelizer's plan with its workgroup kernel (route 2), where the units either side of the row streams' boundaries
+    next to every mark are compared as well"""
     window, hop_in, unit_out, min_rows = bank_geometry(kind, M, P, H)
     h = oracle.lpf_corrected(M * P, 0.45 / M)
-    plan = {"synth": lambda: redio.Synthesizer(h, M, P), "os": lambda: redio.OversampledChannelizer(h, M, P, H),
+    plan = {"synth": lambda: redio.Synthesizer(h, M, P), "os": lambda: redio.OversampledChannelizer(h, M, P, H, one_kernel=one_kernel),
             "os_synth": lambda: redio.OversampledSynthesizer(h, M, P, H)}[kind]()
     units = (n_in - window) // hop_in + 1
     assert (plan.nrows(n_in) if kind == "os" else plan.nout(n_in) // unit_out) == units
@@ -416,6 +475,11 @@ def run_bank_past_2_32(gpu, redio, oracle, big, kind, M, P, H, n_in, routes):
             per = (64 << 20) // (M * 8) - min_rows + 1                # units per default pass (pfb_bank_cut.h)
             assert units > 100 * per or M != 64
             seams = {q for b in at for q in (b // per * per, (b // per + 1) * per)}
+        if route == 2:
+            import pfb_os_p2_ref as p2
+            rps = p2.rows_per_stream(units, gpu.cuda.get_device_properties(0).multi_processor_count, M)   # rows of one stream of the launch
+            assert units > 100 * rps
+            seams = {q for b in at for q in (b // rps * rps, (b // rps + 1) * rps)}
         out = (plan(x) if kind == "synth" else plan(x, first_row=BANK_FIRST)).reshape(-1)
         assert out.numel() == units * unit_out
         check_bank(oracle, out, kind, h, M, P, H, units, at | seams)
@@ -433,6 +497,15 @@ def test_pfb_os_past_2_32(gpu, redio, oracle, big):
     """redio_pfb_os_enqueue at hop 32 on the first 2^31 + 2^20 samples: more than 2^26 rows, so more than 2^32 elements out"""
     units, nout = run_bank_past_2_32(gpu, redio, oracle, big, "os", 64, 16, 32, (1 << 31) + (1 << 20), (1, 0))
     assert units > 1 << 26 and nout > 1 << 32
+
+
+@pytest.mark.parametrize("M,P,H", [(32, 16, 16), (512, 8, 256), (1024, 4, 512)])
+def test_pfb_os_workgroup_kernel_past_2_32(gpu, redio, oracle, big, M, P, H):
+    """redio_pfb_os_enqueue with one_kernel=True (route 2) at hop M / 2 on the first 2^31 + 2^20 samples: more than 2^32 elements out,
+    through half-row indices, rows per stream and row * M + n of the workgroup kernel"""
+    n_in = (1 << 31) + (1 << 20)
+    units, nout = run_bank_past_2_32(gpu, redio, oracle, big, "os", M, P, H, n_in, (2,), one_kernel=True)
+    assert units == (n_in - M * P) // H + 1 and nout == units * M > 1 << 32 and n_in * 8 > 1 << 34
 
 
 def test_pfb_os_synth_past_2_32(gpu, redio, oracle, big):

@@ -94,15 +94,82 @@ def test_chain_special_values(gpu, redio, oracle, k, d, fused):
         assert same_special(got, want), (k, d, fused, seed, where_differs(got, want))
 
 
-@pytest.mark.parametrize("M,P", [(64, 16), (64, 4), (32, 8), (256, 16), (1024, 4), (48, 5)])
-def test_channelizer_special_values(gpu, redio, oracle, M, P):
+RECIPES = ((1, sprinkle_finite, 0.01), (2, sprinkle_finite, 0.3), (3, sprinkle, 0.0005), (4, sprinkle, 0.02))
+
+
+@pytest.mark.parametrize("M,P,fused", [(64, 16, True), (64, 4, True), (32, 8, True), (256, 16, True), (1024, 4, True), (48, 5, True),
+                                       (128, 8, True), (512, 16, True), (512, 4, False)],
+                         ids=["64-16", "64-4", "32-8", "256-16", "1024-4", "48-5", "128-8", "512-16", "512-4-unfused"])
+def test_channelizer_special_values(gpu, redio, oracle, M, P, fused):
+    """every channel count of the workgroup kernel among them: 512 is the one with its own transform path (the stage-ordered twiddle copy)"""
     h = oracle.lpf_corrected(M * P, 0.45 / M)
     n = M * (P - 1 + 300) + 5
-    for seed, maker, dens in ((1, sprinkle_finite, 0.01), (2, sprinkle_finite, 0.3), (3, sprinkle, 0.0005), (4, sprinkle, 0.02)):
+    for seed, maker, dens in RECIPES:
         x = maker(oracle, seed * 13 + M, n, True, dens)
-        got = redio.Channelizer(h, M, P)(gpu.from_numpy(x).cuda()).cpu().numpy()
-        want = oracle.pfb_channelizer(x, h, M, P, fused=True)
-        assert same_special(got, want), (M, P, seed, where_differs(got, want))
+        got = redio.Channelizer(h, M, P, fused)(gpu.from_numpy(x).cuda()).cpu().numpy()
+        want = oracle.pfb_channelizer(x, h, M, P, fused=fused)
+        assert same_special(got, want), (M, P, fused, seed, where_differs(got, want))
+
+
+@pytest.mark.parametrize("M,P,fused", [(32, 16, True), (128, 4, True), (256, 8, True), (512, 8, True), (512, 8, False), (1024, 4, True)])
+def test_oversampled_channelizer_block_special_values(gpu, redio, oracle, M, P, fused):
+    """redio_pfb_os_* on its workgroup kernel (route 2): 64 G + TR + 3 rows -- more than one workgroup, a short last iteration, an odd
+    count -- with an even and an odd first row (the rows turned by M / 2 places start on the other parity)"""
+    import pfb_os_p2_ref as p2
+    import pfb_os_ref
+    H = M // 2
+    G, TR = p2.shape_consts(M)
+    rows = 64 * G + TR + 3
+    assert rows <= 600
+    h = oracle.lpf_corrected(M * P, 0.45 / M)
+    plan = redio.OversampledChannelizer(h, M, P, H, fused=fused, one_kernel=True)
+    assert plan.route == 2
+    for seed, maker, dens in RECIPES:
+        x = maker(oracle, seed * 17 + M, p2.n_in(M, P, rows), True, dens)
+        d = gpu.from_numpy(x).cuda()
+        for F in (0, 1):
+            got = plan(d, first_row=F).cpu().numpy()
+            want = pfb_os_ref.channelize(x, h, M, P, H, F, fused)
+            assert want.shape == (rows, M)
+            assert same_special(got, want), (M, P, fused, seed, F, where_differs(got, want))
+    assert plan.route == 2
+
+
+@pytest.mark.parametrize("M,P,K", [(128, 8, 5), (512, 16, 17)])
+def test_polyphase_spectrum_block_special_values(gpu, redio, oracle, M, P, K):
+    """redio_pfb_pspec_* on its workgroup kernel (route 2) in every split mode: more than one workgroup of row streams of the floor's
+    length and three rows more; at K = 17 by segments the partials and the fold pass.  A power overflows where a sample is 1e30, and a
+    row of these shapes gathers thousands of samples: under the file's four recipes most of the wanted values are inf or NaN, which
+    compare equal whatever was summed.  A fifth recipe keeps to the special values of magnitude 2 and less (signed zeros, subnormals,
+    the smallest normals, 0.5, 1), so that every wanted value is finite and its bits are the sums' own."""
+    import pfb_os_p2_ref as p2
+    import pfb_pspec_ref
+    rows = p2.shape_consts(M)[0] * -(-64 // K) + 3
+    h = oracle.lpf_corrected(M * P, 0.45 / M)
+    plan = redio.PolyphaseSpectrum(h, M, P, K, one_kernel=True)
+    assert plan.route == 2 and not plan.is_fused
+    W, H = pfb_pspec_ref.shape(M, P, K)
+
+    def sprinkle_small(oracle, seed, n, cplx, density):
+        small = SPECIALS[np.abs(SPECIALS) <= 2.0]   # (a NaN compares false: left out)
+        rng = np.random.default_rng(seed)
+        x = oracle.synth_iq(seed, 0, n)
+        w = x.view(np.float32).reshape(-1)
+        k = max(1, int(density * len(w)))
+        w[rng.integers(0, len(w), k)] = small[rng.integers(0, len(small), k)]
+        return x
+
+    for seed, maker, dens in RECIPES + ((5, sprinkle_small, 0.05),):
+        x = maker(oracle, seed * 19 + M, W + (rows - 1) * H + 5, True, dens)
+        d = gpu.from_numpy(x).cuda()
+        want = pfb_pspec_ref.spectrum(x, h, M, P, K, True)
+        assert want.shape == (rows, M)
+        print(f"recipe {seed}: {int(np.isfinite(want).sum())} of {want.size} wanted values are finite")
+        assert seed != 5 or (np.isfinite(want).all() and (want > 0).all())
+        for mode in (0, 1, 2):
+            plan.set_split(mode)
+            got = plan(d).cpu().numpy()
+            assert same_special(got, want), (M, P, K, seed, mode, where_differs(got, want))
 
 
 @pytest.mark.parametrize("nfft,k", [(1024, 127), (4096, 1025), (16384, 127), (65536, 8193), (32768, 127), (8192, 127), (2048, 513), (131072, 127), (1000, 101)])

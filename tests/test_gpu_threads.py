@@ -286,3 +286,89 @@ def test_concurrent_polyphase_bank_plans(gpu, redio, oracle):
         t.join(300)
     assert not any(t.is_alive() for t in threads), "a thread did not finish"   # reported, not waited on
     assert not errors, errors
+
+
+def test_concurrent_workgroup_kernel_plans(gpu, redio, oracle):
+    """the three workgroup kernels of the 4096-point LDS image (the Channelizer's, redio_pfb_os_* with one_kernel=True, redio_pfb_pspec_*
+    with one_kernel=True): eight threads, each with a plan of its own on a stream of its own, row counts that rise and fall -- a block
+    oversampled plan kept and one created fresh every iteration (its destroy runs beside the others' calls), block spectrometers by rows
+    and by segments with K = 17 (the partials regrow), a stream of either family fed in twelve pieces, and a plan that set_unfused flips
+    between routes 2 and 0 every iteration; every result bit for bit the restatement's"""
+    import pfb_os_ref
+    import pfb_pspec_ref
+    errors = []
+    rows_of = [1, 3, 2, 5, 1, 4, 6, 2, 7, 3, 1, 8]   # per iteration: up and down, the largest last
+    FIRST = 3
+
+    def same(got, want):
+        return got.shape == want.shape and np.array_equal(np.ascontiguousarray(got).view(np.uint32), np.ascontiguousarray(want).view(np.uint32))
+
+    def worker(kind, M, P, K, seed):
+        try:
+            s = gpu.cuda.Stream()
+            with gpu.cuda.stream(s):
+                H = M // 2
+                h = oracle.synth_f32(seed, 0, M * P)
+                if kind == "chan":
+                    plan = redio.Channelizer(h, M, P)
+                elif kind.startswith("os"):
+                    plan = redio.OversampledChannelizer(h, M, P, H, one_kernel=True)
+                    assert plan.route == 2 and not plan.is_fused
+                else:
+                    plan = redio.PolyphaseSpectrum(h, M, P, K, one_kernel=True)
+                    assert plan.route == 2 and not plan.is_fused
+                    plan.set_split({"spec_rows": 1, "spec_segments": 2}.get(kind, 0))
+                if kind in ("os_stream", "spec_stream"):   # one stream in twelve pieces against the one-shot result of the whole
+                    window, hop, per = (M * P, H, M) if kind == "os_stream" else (*pfb_pspec_ref.shape(M, P, K), M)
+                    lens = [(window - hop if it == 0 else 0) + 5 * rows * hop + 7 * it for it, rows in enumerate(rows_of)]
+                    x = oracle.synth_iq(seed, 0, sum(lens))
+                    whole = (pfb_os_ref.channelize(x, h, M, P, H, 0, True) if kind == "os_stream" else pfb_pspec_ref.spectrum(x, h, M, P, K, True)).reshape(-1)
+                    d = gpu.from_numpy(x).cuda()
+                    st = redio.OversampledChannelizerStream(plan) if kind == "os_stream" else redio.Stream(plan)
+                    pos = made = 0
+                    for it, n in enumerate(lens):
+                        got = st(d[pos: pos + n]).cpu().numpy().reshape(-1)
+                        pos += n
+                        now = (pos - window) // hop + 1 if pos >= window else 0
+                        if not (same(got, whole[made * per: now * per]) and st.pending == pos - now * hop):
+                            errors.append((kind, it))
+                        made = now
+                    assert made * per == len(whole) and made >= 5 * sum(rows_of) and plan.route == 2
+                    return
+                for it, rows in enumerate(rows_of):
+                    if kind == "chan":
+                        x = oracle.synth_iq(seed + it, 0, M * (P - 1 + rows * 20 + it) + 7 * it)
+                        got = plan(gpu.from_numpy(x).cuda()).cpu().numpy()
+                        want = oracle.pfb_channelizer(x, h, M, P, fused=True)
+                    elif kind.startswith("os"):
+                        if kind == "os_fresh" and it:
+                            plan = redio.OversampledChannelizer(h, M, P, H, one_kernel=True)   # the one before is dropped here
+                        if kind == "os_flip":
+                            plan.set_unfused(it % 2 == 1)
+                            assert plan.route == (0 if it % 2 else 2)
+                        units = rows * 20 + it   # up to 171 rows: past a stream's floor, odd and even counts
+                        x = oracle.synth_iq(seed + it, 0, (units - 1) * H + M * P + 7 * it % H)
+                        got = plan(gpu.from_numpy(x).cuda(), first_row=FIRST + it).cpu().numpy()
+                        want = pfb_os_ref.channelize(x, h, M, P, H, FIRST + it, True)
+                        assert len(want) == units
+                    else:
+                        W, Hs = pfb_pspec_ref.shape(M, P, K)
+                        x = oracle.synth_iq(seed + it, 0, W + (3 * rows - 1) * Hs + 7 * it)
+                        got = plan(gpu.from_numpy(x).cuda()).cpu().numpy()
+                        want = pfb_pspec_ref.spectrum(x, h, M, P, K, True)
+                        assert len(want) == 3 * rows
+                    if not same(got, want):
+                        errors.append((kind, it))
+        except Exception as e:  # noqa: BLE001
+            errors.append((kind, repr(e)))
+
+    jobs = [("chan", 256, 8, 0), ("os_kept", 128, 4, 0), ("os_fresh", 1024, 4, 0), ("spec_rows", 256, 8, 5), ("spec_segments", 128, 4, 17),
+            ("os_stream", 512, 8, 0), ("spec_stream", 32, 16, 3), ("os_flip", 256, 4, 0)]
+    threads = [threading.Thread(target=worker, args=(*job, 1000 * (i + 1)), daemon=True) for i, job in enumerate(jobs)]
+    assert len(threads) <= 9
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(300)
+    assert not any(t.is_alive() for t in threads), "a thread did not finish"   # reported, not waited on
+    assert not errors, errors

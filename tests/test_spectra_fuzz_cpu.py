@@ -3,7 +3,9 @@
 Generator coverage: the dry mode (`fuzz_spectra.py --draw 6000 SEED`, the seed of tests/test_gpu_fuzz_spectra.py) is run as the
 command it is, in a process that must import neither torch nor the product library, and every route combination the driver of
 pspec_api.hip (the polyphase spectrometer's entries included), the stream layer and the real-input plans distinguish has to turn up
-in at least 1 % of the cases.
+in at least 1 % of the cases; the polyphase spectrometer's workgroup kernel (route 2: the plan's one_kernel flag) per channel count,
+split mode, entry and alignment among them.  Route 2 is in the opening round of the GPU test's own runs, and the tool's restated launch
+geometry is pfb_pspec_p2_core.h's.
 
 Restatements against float64: the counterpart of test_oracle_random.py for fftr_ref, ovsave_real_ref, pspec_ref, pspec_real_ref and
 pfb_pspec_ref, on the generator's own first 400 shapes (the opening round of all eight families and as many again), unspiced.  The
@@ -14,10 +16,11 @@ numpy's transform across the branches, |.|^2 summed over K rows) is held to the 
 worst is under half of it, so the taps ask for no factor of their own.
 Worst distances over those 400 cases, as values and as fractions of their bounds (measure: max|got - exact| / max(exact) for the
 spectra, relative L2 for the transforms, the largest absolute error for overlap-save):
-    pspec        3.6e-07, 0.18 of its bound        pspec_real   3.4e-07, 0.17
+    pspec        3.6e-07, 0.18 of its bound        pspec_real   3.8e-07, 0.19
     pspec_u8     4.2e-07, 0.21                     fftr         1.5e-07, 0.07
-    ovsave_real  5.5e-07, 0.08                     streams      3.0e-07, 0.15
-    pfb_pspec    2.8e-07, 0.14                     pfb_streams  2.3e-07, 0.11"""
+    ovsave_real  8.5e-08, 0.08                     streams      3.0e-07, 0.15
+    pfb_pspec    2.7e-07, 0.13                     pfb_streams  2.7e-07, 0.14
+(the polyphase shapes are mostly workgroup-kernel ones now; before that: pfb_pspec 2.8e-07, 0.14, pfb_streams 2.3e-07, 0.11)"""
 import json
 import os
 import subprocess
@@ -54,7 +57,7 @@ def drawn():
 
 
 def plan_key(c):
-    return json.dumps({k: c[k] for k in ("family", "N", "inverse", "ntaps", "taps", "tseed", "K", "step", "window", "wseed", "M", "P", "fir_fused") if k in c}, sort_keys=True)
+    return json.dumps({k: c[k] for k in ("family", "N", "inverse", "ntaps", "taps", "tseed", "K", "step", "window", "wseed", "M", "P", "fir_fused", "block") if k in c}, sort_keys=True)
 
 
 def test_the_dry_mode_draws_what_a_run_draws(drawn):
@@ -109,6 +112,28 @@ def test_every_route_combination_is_drawn_often_enough(drawn):
     for u8 in (False, True):
         for name in ("zero_piece", "short_piece", "long_piece", "odd_piece", "reset"):
             cond[f"pfb_streams u8={u8} {name}"] = [c for c in by["pfb_streams"] if c["u8"] == u8 and r(c)[name]]
+    # the workgroup kernel (route 2): the plan's flag on a one-kernel shape of the inner channelizer
+    both = pfb + by["pfb_streams"]
+    for c in both:
+        assert r(c)["route"] == (1 if r(c)["fused"] else 2 if c["block"] and r(c)["one_kernel"] else 0), c
+    two, two_st = [c for c in pfb if r(c)["route"] == 2], [c for c in by["pfb_streams"] if r(c)["route"] == 2]
+    for M in fz.PFB_ONE_KERNEL:
+        cond[f"route 2 at {M} channels"] = [c for c in two + two_st if c["M"] == M]
+    for mode in (0, 1, 2):
+        cond[f"pfb_pspec route 2 in mode {mode}"] = [c for c in two if c["mode"] == mode]
+        for big in (False, True):   # a set test: every mode either side of K = 16, in a launch of more than one workgroup
+            assert any(c["mode"] == mode and (c["K"] > fz.SEG) == big and r(c)["geometry"]["groups"] > 1 for c in two), (mode, big)
+    cond["pfb_pspec route 2 with K > 16"] = [c for c in two if c["K"] > fz.SEG]
+    cond["pfb_pspec route 2 by segments"] = [c for c in two if r(c)["split"]]
+    cond["pfb_pspec route 2 from bytes at an odd 2-byte base"] = [c for c in two if c["base"] % 4 == 2]
+    cond["pfb_pspec route 2 with cf32 base 8"] = [c for c in two if c["cbase"] == 8]
+    cond["route 2 spiced"] = [c for c in two + two_st if c["spice"]]
+    cond["pfb_pspec route 2 in more than one workgroup"] = [c for c in two if r(c)["geometry"]["groups"] > 1]
+    cond["pfb_pspec route 2 with a short last stream"] = [c for c in two if r(c)["geometry"]["units"] % r(c)["geometry"]["ups"]]
+    cond["pfb_streams on route 2 from cf32"] = [c for c in two_st if not c["u8"]]
+    cond["pfb_streams on route 2 from u8"] = [c for c in two_st if c["u8"]]
+    cond["the flag on a shape with no block form"] = [c for c in both if r(c)["flag_no_form"]]
+    cond["a one-kernel shape without the flag, down the generic route"] = [c for c in both if r(c)["one_kernel"] and r(c)["route"] == 0]
     seen, again = {}, []
     for c in drawn:
         if c["family"] not in ("streams", "pfb_streams"):
@@ -141,6 +166,48 @@ def test_every_route_combination_is_drawn_often_enough(drawn):
             assert ntr <= 2, c
         else:
             assert ntr * (c["N"] // 2 if real else c["N"]) <= fz.POINTS, c
+
+
+def test_route_2_is_in_the_opening_rounds_of_the_gpu_runs():
+    """tests/test_gpu_fuzz_spectra.py runs the tool per family (--only) at SEED: the OPENING cases it runs whatever the machine's speed
+    hold the workgroup kernel"""
+    for fam in ("pfb_pspec", "pfb_streams"):
+        gen = fz.Gen(SEED)
+        opening = [gen.draw(f) for _, f in zip(range(fz.OPENING), fz.sequence(gen, fam))]
+        assert any(c["route"]["route"] == 2 for c in opening), fam
+
+
+def test_the_tools_block_geometry_is_the_headers(drawn):
+    """pfb_block_consts and pfb_block_geometry against libredio_amd/csrc/pfb_pspec_p2_core.h as tests/emu_pfb_pspec_p2 compiles it, on
+    the drawn route-2 cases and on devices of 1 to 304 CUs: streams per workgroup, rows per iteration, auto mode's threshold, the units
+    per stream, and the workgroup count -- the last stream of the last workgroup that owns a unit, the first slot behind the grid owns
+    none; the case's own record is the one for NOMINAL_CUS"""
+    import ctypes as C
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "emu_pfb_pspec_p2"), "-s"])
+    E = C.CDLL(os.path.join(ROOT, "tests", "_build", "libemu_pfb_pspec_p2.so"))
+    L = C.c_long
+    E.emu_pfbspec_p2_units_per_stream.argtypes, E.emu_pfbspec_p2_units_per_stream.restype = [L, L, C.c_int, L, C.c_int], L
+    E.emu_pfbspec_p2_split_rows.argtypes, E.emu_pfbspec_p2_split_rows.restype = [L, L, C.c_int], L
+    E.emu_pfbspec_p2_stream.argtypes, E.emu_pfbspec_p2_stream.restype = [L, L, L, L, L, C.c_int, C.POINTER(L)], None
+    two = [c for c in drawn if c["family"] == "pfb_pspec" and c["route"]["route"] == 2]
+    assert len(two) >= 3 * LEAST
+    for c in two:
+        M, K, rows, mode = c["M"], c["K"], c["rows"], c["mode"]
+        assert c["route"]["geometry"] == fz.pfb_block_geometry(M, K, rows, mode, fz.NOMINAL_CUS) and c["route"]["split"] == c["route"]["geometry"]["split"], c
+        for cus in (1, 2, 8, 256, 304):
+            g = fz.pfb_block_geometry(M, K, rows, mode, cus)
+            assert (g["G"], g["TR"]) == (E.emu_pfbspec_p2_streams_per_group(M), E.emu_pfbspec_p2_rows_per_iter(M)), c
+            want_split = K > fz.SEG and (mode == 2 or (mode == 0 and rows < E.emu_pfbspec_p2_split_rows(K, cus, M)))
+            assert g["split"] == want_split and g["units"] == rows * (-(-K // fz.SEG) if want_split else 1), (c, cus)
+            if not rows:
+                continue
+            assert g["ups"] == E.emu_pfbspec_p2_units_per_stream(g["units"], K, int(g["split"]), cus, M), (c, cus)
+            st = (L * 4)()
+            E.emu_pfbspec_p2_stream(g["streams"] - 1, g["ups"], g["units"], rows * K, K, int(g["split"]), st)
+            assert st[0] < st[1] == g["units"] and st[3] == rows * K, (c, cus, list(st))
+            E.emu_pfbspec_p2_stream(g["streams"], g["ups"], g["units"], rows * K, K, int(g["split"]), st)
+            assert st[0] == st[1] == g["units"] and g["groups"] == -(-g["streams"] // g["G"]), (c, cus, list(st))
 
 
 def exact_rows(x, N, K, step, window, real):
